@@ -14,10 +14,15 @@ GPUs, is --batch-per-gpu 512).
 Arithmetic ("dtype": "f32"): activations and accumulators are fp32 in HBM / registers; each product runs
 on the 16-bit matrix cores as fp16 hi + lo pair (22-bit mantissa, exact power-of-two scale per tensor) x
 the checkpoint's fp16-exact weight, fp32 accumulate -- error vs fp64 equal to an fp32-input-MFMA kernel's
-(DESIGN.md section 4).  The line also carries `fp32_input_mfma`: the same step with every product on
-v_mfma_f32_32x32x2_f32 (plan option conv_split = off), measured in the same process.
+(DESIGN.md section 4).
 
-Besides the contract line, rank 0 reports
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`, the configuration).
+--dump-outputs DIR then also writes what the last timed step returned (loss, logits, embeddings) as DIR/<name>.npy in
+float32; the inputs are seeded, so two builds can be compared output for output.
+
+--full adds everything else, measured in the same process as before:
+  fp32_input_mfma  the same step with every product on v_mfma_f32_32x32x2_f32 (plan option conv_split = off)
+  fixed_global_batch  N > 1: the metric's global batch split over the N ranks (strong scaling)
   roofline      the igemm / chain / patch launches of every 4th timed step are bracketed by HIP events on their stream; kernels are
                 grouped by instantiation (the names rocprofv3 prints) and ranked by MEASURED time share.  The
                 top kernel is reported against its own binding roof: `bound` = whichever of algorithmic
@@ -333,7 +338,7 @@ PROFILE_EVERY = 4        # the launches of every 4th timed step are bracketed by
 
 
 def timed_steps(stepper, images, y_l, g_l, steps, warmup, barrier, profiling):
-    """-> (seconds for `steps` steps, launch profile, number of steps whose launches were timed)"""
+    """-> (seconds for `steps` steps, launch profile, number of steps whose launches were timed, (loss, logits, emb) of the last step)"""
     for _ in range(warmup):
         stepper.step(images, y_l, g_l)
     barrier()
@@ -352,7 +357,26 @@ def timed_steps(stepper, images, y_l, g_l, steps, warmup, barrier, profiling):
     prof = ops.profile_end() if profiling else {}
     if not torch.isfinite(loss).item():
         raise SystemExit("non-finite loss in the timed region")
-    return dt, prof, max(sampled, 1)
+    return dt, prof, max(sampled, 1), (loss, logits, emb)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float32.  An array larger than its share of the 64 MB budget is replaced by a
+    fixed, seeded sample of its rows, whose indices are written beside it as <name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (2 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share and a.ndim >= 1:
+            n = max(1, share // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], n, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 def extra_leg(arch, dtype, Bl, steps, warmup, dev, note):
@@ -363,7 +387,7 @@ def extra_leg(arch, dtype, Bl, steps, warmup, dev, note):
     if dtype == "f16":
         images = images.half()
     sync = torch.cuda.synchronize
-    dt, prof, nprof = timed_steps(stepper, images, y_l, g_l, steps, warmup, sync, True)
+    dt, prof, nprof, _ = timed_steps(stepper, images, y_l, g_l, steps, warmup, sync, True)
     value, step_ms = Bl * steps / dt, dt / steps * 1e3
     roof = roofline_of(prof, nprof, step_ms, value, 1, arch, pmc_table(arch, Bl, dtype))
     keep = ("kernel", "bound", "achieved", "peak", "unit", "frac", "share_of_step", "launches_per_step", "avg_launch_ms",
@@ -567,10 +591,17 @@ def main():
                     help="encode in k row chunks, each chunk's all-gather in flight while the next encodes (BASELINE configs[3]'s overlap). "
                          "Default 1: measured on one MI355X at 512 images per GPU, chunking the encode costs 10 % (k = 2) / 27 % (k = 4) of the "
                          "per-GPU rate (smaller launches), the gather it would hide is 2 MiB per rank = < 0.1 % of the step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-mfma-leg", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="N = 1: skip the other configurations reported under extra_legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything besides the headline: roofline, fp32_input_mfma, extra_legs, cpu_baseline "
+                         "(N = 1), fixed_global_batch (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss, logits and embeddings to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-fp32-mfma-leg", action="store_true", help="--full: skip fp32_input_mfma")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full, N = 1: skip the other configurations reported under extra_legs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -623,10 +654,14 @@ def main():
                 dist.barrier()
         torch.cuda.synchronize()
 
-    # every igemm launch of the timed region is bracketed by HIP events (an event pair is ~4 us of stream time:
-    # ~60 launches per RN50 step = 0.25 ms of a ~30 ms step); DBMM_BENCH_PROFILE=0 times none
-    profiling = os.environ.get("DBMM_BENCH_PROFILE", "1") != "0"
-    dt, prof, nprof = timed_steps(stepper, images, y_l, g_l, args.steps, args.warmup, barrier, profiling)
+    # --full: every igemm launch of the timed region is bracketed by HIP events for the roofline (an event pair is ~4 us of stream
+    # time: ~60 launches per RN50 step = 0.25 ms of a ~30 ms step); DBMM_BENCH_PROFILE=0 times none.  A plain run times none.
+    profiling = args.full and os.environ.get("DBMM_BENCH_PROFILE", "1") != "0"
+    dt, prof, nprof, (loss, logits, emb) = timed_steps(stepper, images, y_l, g_l, args.steps, args.warmup, barrier, profiling)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the stepper: what the caller of the timed step received from its last call
+        dump_outputs(args.dump_outputs, {"loss": loss, "logits": logits, "embeddings": emb})
+    del loss, logits, emb
 
     tmax = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
     dist_info = None
@@ -643,12 +678,12 @@ def main():
     # N > 1: the north_star's own shape beside the weak-scaling line -- the metric's GLOBAL batch (RN50: 1024 = BASELINE configs[2] at
     # N = 2) split over the N ranks (strong scaling), same process group, same barriers, max over ranks
     fixed = None
-    if world > 1 and not args.batch_per_gpu and default_bl.get(args.arch) and default_bl[args.arch] % world == 0 and micro == 1:
+    if args.full and world > 1 and not args.batch_per_gpu and default_bl.get(args.arch) and default_bl[args.arch] % world == 0 and micro == 1:
         Bf = default_bl[args.arch] // world
         img_f, y_f, g_f = synthetic_batch(R, Bf, world, rank, dev)
         if args.dtype == "f16":
             img_f = img_f.half()
-        dtf, _, _ = timed_steps(stepper, img_f, y_f, g_f, args.steps, max(1, args.warmup), barrier, False)
+        dtf, _, _, _ = timed_steps(stepper, img_f, y_f, g_f, args.steps, max(1, args.warmup), barrier, False)
         tf = torch.tensor([dtf], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tf, op=dist.ReduceOp.MAX)
         fixed = {"config": {"workload": f"global batch {Bf * world} split over {world} GPUs ({Bf} images/GPU)"
@@ -661,8 +696,6 @@ def main():
     if rank == 0:
         value = B * args.steps / dt
         step_ms = dt / args.steps * 1e3
-        roof = roofline_of(prof, nprof, step_ms, value, world, args.arch, pmc_table(args.arch, Bl, args.dtype))
-        roof["timed_steps"] = nprof
         cfgs = {("RN50", 1, 1024): "the metric's configuration, CLIP-RN50 224px bs=1024 on one GPU",
                 ("RN50", 1, 512): "BASELINE configs[1]", ("RN50", 2, 512): "BASELINE configs[2]",
                 ("RN50", 2, 1024): "the metric's per-GPU batch on 2 GPUs", ("RN50", 4, 1024): "the metric's per-GPU batch on 4 GPUs",
@@ -679,17 +712,19 @@ def main():
                                    f"global batch {B}" + (f" ({cfgs[(args.arch, world, Bl)]})" if (args.arch, world, Bl) in cfgs else ""),
                        "global_batch": B, "batch_per_gpu": Bl, "parallelism": f"dp{world}",
                        "collective": "all_gather(embeddings+labels) per step" if world > 1 else "none"},
-            "roofline": roof,
         }
+        if args.full:
+            line["roofline"] = roofline_of(prof, nprof, step_ms, value, world, args.arch, pmc_table(args.arch, Bl, args.dtype))
+            line["roofline"]["timed_steps"] = nprof
         if dist_info:
             line["dist"] = dist_info
             line["config"]["weak_scaling_note"] = (f"{Bl} images per GPU at every N (the N = 1 line runs the same per-GPU batch): value(N) / (N x value(1)) "
                                                    "compares equal per-GPU work")
         if world > 1 and fixed is not None:
             line["fixed_global_batch"] = fixed
-        if world == 1 and not args.no_fp32_mfma_leg and args.arch.startswith("RN") and args.dtype == "f32":
+        if args.full and world == 1 and not args.no_fp32_mfma_leg and args.arch.startswith("RN") and args.dtype == "f32":
             line["fp32_input_mfma"] = fp32_mfma_leg(args.arch, dev, Bl, images, y_l, g_l)
-        if world == 1 and not args.no_extra_legs and args.arch == "RN50" and args.dtype == "f32" and not args.batch_per_gpu:
+        if args.full and world == 1 and not args.no_extra_legs and args.arch == "RN50" and args.dtype == "f32" and not args.batch_per_gpu:
             del stepper, model, images
             torch.cuda.empty_cache()
             legs = {}
@@ -707,7 +742,7 @@ def main():
             legs["adapter_only_bs256"] = adapter_only_leg(256, 1024, dev)
             legs["adapter_only_bs1024"] = adapter_only_leg(1024, 1024, dev)
             line["extra_legs"] = legs
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd, D, paths)
         print(json.dumps(line), flush=True)
     if world > 1:

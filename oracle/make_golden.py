@@ -11,6 +11,7 @@ torchvision / visualizer_supcon and .cuda() patched to identity.
 
     python oracle/make_golden.py            # writes tests/golden/
 """
+import gzip
 import importlib.util
 import json
 import os
@@ -194,6 +195,11 @@ def gen_tokens():
     np.savez_compressed(os.path.join(GOLD, "tokens.npz"), tokens=rows)
     with open(os.path.join(GOLD, "tokens_prompts.json"), "w") as f:
         json.dump(prompts, f, indent=0)
+    # the merges table the tokenizer tests read: its header line and the 48,894 merges both tokenizers use (the rest of the
+    # published file is never read)
+    lines = gzip.open(os.path.join(REF, "clip", "bpe_simple_vocab_16e6.txt.gz")).read().decode("utf-8").split("\n")
+    with open(os.path.join(GOLD, "bpe_simple_vocab_16e6_merges.txt.gz"), "wb") as f:
+        f.write(gzip.compress(("\n".join(lines[:49152 - 256 - 2 + 1]) + "\n").encode("utf-8"), compresslevel=9, mtime=0))
     print(f"[tokens] {len(prompts)} prompts, sot={sot} eot={eot}")
 
 
@@ -364,7 +370,11 @@ def gen_adapter(FM, D=1024, Bs=(4, 256, 1024), fname="adapter.npz"):
                 with torch.no_grad():
                     record(tag + "/eval", {"logits": ma(x), "logits_spurious": ma.forward_spurious(x)})
         print(f"[adapter] D={D} B={B} done")
-    np.savez_compressed(os.path.join(GOLD, fname), **out)
+    # the stage-1 adapter (two large weight matrices) goes to a companion file so that each committed fixture stays under
+    # 1 MiB; the tests' golden() joins <name>.npz with its <name>.part*.npz
+    stem = os.path.join(GOLD, fname[:-len(".npz")])
+    np.savez_compressed(stem + ".npz", **{k: v for k, v in out.items() if not k.startswith("stage1/")})
+    np.savez_compressed(stem + ".part1.npz", **{k: v for k, v in out.items() if k.startswith("stage1/")})
     return FM
 
 

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -28,10 +29,29 @@ def pytest_collection_modifyitems(config, items):
             item.add_marker(skip)
 
 
+class _JoinedNpz:
+    """one fixture stored as <name>.npz plus <name>.part*.npz (each committed file stays under 1 MiB): the NpzFile
+    interface the tests use, `files` and item lookup"""
+
+    def __init__(self, parts):
+        self._by_key = {k: p for p in parts for k in p.files}
+        self.files = list(self._by_key)
+
+    def __getitem__(self, key):
+        return self._by_key[key][key]
+
+    def __contains__(self, key):
+        return key in self._by_key
+
+
 @pytest.fixture(scope="session")
 def golden():
     def load(name):
-        return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+        path = os.path.join(GOLDEN, name)
+        parts = sorted(glob.glob(path[:-len(".npz")] + ".part*.npz")) if name.endswith(".npz") else []
+        if not parts:
+            return np.load(path, allow_pickle=False)
+        return _JoinedNpz([np.load(p, allow_pickle=False) for p in [path] + parts])
     return load
 
 

@@ -74,3 +74,42 @@ def test_failing_rank_fails_the_parent():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-such-flag"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert p.returncode != 0
+
+
+def test_full_and_dump_outputs_are_options_and_steps_must_be_positive(tmp_path):
+    """--full and --dump-outputs DIR parse (dry run, no GPU); --steps 0 is refused before anything runs"""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(DBMM_BENCH_DRYRUN="1")
+    bench_py = os.path.join(ROOT, "bench.py")
+    p = subprocess.run([sys.executable, bench_py, "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
+                        "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert line["steps"] == 3 and line["warmup"] == 1
+    p = subprocess.run([sys.executable, bench_py, "--gpus", "1", "--steps", "0"], env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
+def test_dump_outputs_float32_within_budget(bench, tmp_path, monkeypatch):
+    """what --dump-outputs writes: one float32 .npy per output; an output over its share of the budget becomes a fixed, seeded
+    sample of its rows with the row indices beside it (float64)"""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 16)
+    emb = torch.arange(512 * 64, dtype=torch.float64).view(512, 64)           # 128 KiB as float32: over the budget
+    outs = {"loss": torch.tensor(1.5), "logits": torch.ones(512, 2, dtype=torch.float16), "embeddings": emb}
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    bench.dump_outputs(str(tmp_path / "b"), outs)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["embeddings.npy", "embeddings_rows.npy", "logits.npy", "loss.npy"]
+    total = 0
+    for nm in names:
+        a, b = np.load(tmp_path / "a" / nm), np.load(tmp_path / "b" / nm)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)      # the same sample every run
+        total += a.nbytes
+    assert total <= 1 << 16
+    assert np.load(tmp_path / "a" / "loss.npy").shape == () and np.load(tmp_path / "a" / "logits.npy").shape == (512, 2)
+    rows = np.load(tmp_path / "a" / "embeddings_rows.npy").astype(np.int64)
+    sample = np.load(tmp_path / "a" / "embeddings.npy")
+    assert 0 < len(rows) < 512 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(sample, emb.numpy()[rows].astype(np.float32))

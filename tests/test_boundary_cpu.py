@@ -13,33 +13,22 @@ import torch
 from conftest import GOLDEN
 from dbmm_amd import adapter, optim, synth
 from dbmm_amd.clip import clip as dclip
-from dbmm_amd.clip import simple_tokenizer
 from dbmm_amd.clip.model import build_model
 
 
-def _bpe_path():
-    """the OpenAI merges table is data this repository does not ship: $DBMM_BPE_PATH, ~/.cache/clip,
-    or (build container only) the reference checkout's copy"""
-    try:
-        return simple_tokenizer.default_bpe()
-    except FileNotFoundError:
-        p = "/root/reference/clip/bpe_simple_vocab_16e6.txt.gz"
-        return p if os.path.isfile(p) else None
-
-
-needs_bpe = pytest.mark.skipif(_bpe_path() is None, reason="bpe_simple_vocab_16e6.txt.gz (OpenAI CLIP merges table, not "
-                               "shipped) not found: set DBMM_BPE_PATH")
+# the OpenAI CLIP merges table (bpe_simple_vocab_16e6.txt.gz) cut to what a tokenizer reads of it: the header line and the
+# first 48,894 merges (oracle/make_golden.py writes it beside tokens.npz)
+BPE_MERGES = os.path.join(GOLDEN, "bpe_simple_vocab_16e6_merges.txt.gz")
 
 
 @pytest.fixture()
 def tokenizer(monkeypatch):
-    monkeypatch.setenv("DBMM_BPE_PATH", _bpe_path())
+    monkeypatch.setenv("DBMM_BPE_PATH", BPE_MERGES)
     monkeypatch.setattr(dclip, "_tokenizer", None)
     yield
     dclip._tokenizer = None
 
 
-@needs_bpe
 def test_tokenize_bit_exact_vs_reference_tokenizer(golden, tokenizer):
     """clip.tokenize (clip/clip.py:197-237) == the reference SimpleTokenizer's id rows, 18 prompts: the
     16 class / spurious / group prompts of both datasets, one with apostrophes, digits, double
@@ -52,7 +41,6 @@ def test_tokenize_bit_exact_vs_reference_tokenizer(golden, tokenizer):
     assert np.array_equal(dclip.tokenize(prompts[0]).numpy(), want[:1])        # a bare string is one row
 
 
-@needs_bpe
 def test_tokenize_overflow_and_truncate(tokenizer):
     long = " ".join(["photo"] * 100)
     with pytest.raises(RuntimeError, match="too long for context length"):       # clip/clip.py:234

@@ -165,15 +165,15 @@ def test_rccl_runs_the_collectives_of_the_step_on_one_gpu(tmp_path):
 
 
 def test_bench_starts_its_own_ranks(tmp_path):
-    """the driver's command shape, `python bench.py --gpus 2 ...` with no launcher environment: the parent starts two ranks (gloo
-    rehearsal: both on this GPU), rank 0's line carries the dist block and the fixed-global-batch leg, return code 0"""
+    """the driver's command shape, `python bench.py --gpus 2 ... --full` with no launcher environment: the parent starts two ranks
+    (gloo rehearsal: both on this GPU), rank 0's line carries the dist block and the fixed-global-batch leg, return code 0"""
     import json
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(DBMM_DIST_BACKEND="gloo", DBMM_BENCH_PROFILE="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"], env=env,
-                       capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
+                       env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
