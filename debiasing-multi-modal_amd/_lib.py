@@ -40,6 +40,7 @@ KERNEL_SOURCES = (
     ("avgpool2_f16", ("conv_f16.hip", "common.h")),
     ("stem_s2", ("resnet_ops.hip", "common.h")), ("attnpool", ("resnet_ops.hip", "common.h")),
     ("adapter_step", ("adapter_step.hip", "common.h")),
+    ("linear_", ("linear_step.hip", "common.h")),
 )
 
 
@@ -168,6 +169,10 @@ _SIGS = {
     "dbmm_sgd_momentum": [_L, _P, _P, _P, _P, _F, _F, _F, _I, _P],
     "dbmm_workspace_bytes_adapter_train_step": [_L, _L, _L, _I],
     "dbmm_adapter_train_step": [_P] * 26 + [_F, _P, _F, _F, _F, _F, _I, _P, _P, _P, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_linear_train_step": [_L, _L, _L],
+    "dbmm_linear_train_step": [_P] * 6 + [_F, _F, _F, _I, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_linear_ce_fwd": [_L],
+    "dbmm_linear_ce_fwd": [_P] * 7 + [_L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_preprocess": [_L, _L],
     "dbmm_resize_crop_normalize_u8": [_P, _L, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _Z, _P],
     "dbmm_resize_crop_normalize_u8_batch": [_P, _L, _L, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _Z, _P],
@@ -185,6 +190,8 @@ _RESTYPES = {
     "dbmm_debug_last_igemm": None,
     "dbmm_workspace_bytes_adapter_bwd": c_size_t,
     "dbmm_workspace_bytes_adapter_train_step": c_size_t,
+    "dbmm_workspace_bytes_linear_train_step": c_size_t,
+    "dbmm_workspace_bytes_linear_ce_fwd": c_size_t,
 }
 
 EXPORTS = tuple(_SIGS)

@@ -33,6 +33,40 @@ class LinearClassifier(nn.Module):
     def forward(self, features):
         return _LinearFn.apply(features, self.fc.weight, self.fc.bias)
 
+    def loss(self, features, labels, use_group=False, spurious=False):
+        """eval forward (validate, final_main.py:655-713): (mean CE, logits, per-row CE) in one launch.  The reference's
+        LinearClassifier has no prompts, so `use_group` / `spurious` cannot apply to it."""
+        if use_group or spurious:
+            raise ValueError("LinearClassifier has no group / spurious prompts (final_main.py:43-49)")
+        with torch.no_grad():
+            return ops.linear_ce_fwd(features.detach().contiguous(), labels.contiguous(), self.fc.weight.detach(), self.fc.bias.detach())
+
+    def train_step(self, features, labels, optimizer, use_group=False):
+        """The step body of train_one_epoch (final_main.py:455-466) for the linear probe -- logits, mean CE, backward and the
+        SGD-momentum update -- as ONE C call (one kernel launch up to the library's one-launch batch size).  Uses the optimiser's
+        lr / momentum / weight_decay and its `momentum_buffer` state, so it mixes freely with `loss.backward(); optimizer.step()`.
+        Requires train mode.  Returns (mean CE, logits, per-row CE), all on the device."""
+        if use_group:
+            raise ValueError("LinearClassifier.forward takes no use_group (final_main.py:43-49)")
+        if not self.training:
+            raise RuntimeError("train_step needs classifier.train()")
+        w, b = self.fc.weight, self.fc.bias
+        owned = [p for g in optimizer.param_groups for p in g["params"]]
+        if len(optimizer.param_groups) != 1 or len(owned) != 2 or {id(p) for p in owned} != {id(w), id(b)}:
+            raise RuntimeError("train_step: the optimiser must hold exactly fc.weight and fc.bias in one param group")
+        group = optimizer.param_groups[0]
+        first = False
+        bufs = []
+        for p in (w, b):
+            st = optimizer.state[p]
+            if st.get("momentum_buffer") is None:
+                st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                first = True
+            bufs.append(st["momentum_buffer"])
+        with torch.no_grad():
+            return ops.linear_train_step(features.detach().contiguous(), labels.contiguous(), w.data, b.data, bufs[0], bufs[1],
+                                         group["lr"], group.get("momentum", 0.0), group.get("weight_decay", 0.0), first)
+
 
 class _LinearFn(torch.autograd.Function):
     @staticmethod

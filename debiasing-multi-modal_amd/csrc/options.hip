@@ -48,6 +48,9 @@ const OptDef kOpts[DBMM_OPT_COUNT] = {
     {"mha_short", 1},          // attention cores: sequences of at most 64 tokens on two-wave workgroups (0: the four-wave ones, half of them idle)
     {"f16_conv_8ph", 1},       // fp16 mode 3x3 convs with Cout % 256 == 0 on conv3x3_f16_8ph_kernel (0: conv3x3_f16_kernel)
     {"conv1x1_res_stream", 1}, // conv3 + residual with K = 256 and >= 131,072 rows on conv1x1_res_stream_kernel (0: the 128 x 128 tiles)
+    {"linear_step_one_launch_max_b", 512}, // linear-probe step: batches up to this size in one launch (in-launch slab reduction), larger
+                               // ones in two (row partials, then a reduce + SGD launch gridded over the weight); same-box crossover
+                               // at D = 1024 between 512 (28.2 vs 30.6 us) and 1024 rows (38.8 vs 33.3 us)
 };
 
 std::atomic<int> g_val[DBMM_OPT_COUNT];

@@ -780,6 +780,72 @@ def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature
     return loss[B], logits, loss[:B]
 
 
+_linear_ws = {}
+
+
+def _linear_workspace(dev, nbytes):
+    ws = _linear_ws.get(dev.index)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _empty((nbytes + 3) // 4, device=dev, dtype=torch.float32)
+        _linear_ws[dev.index] = ws
+    return ws
+
+
+def _linear_operands(x, labels, w, b, extra=()):
+    """the shapes, dtypes and devices the linear-probe kernels assume, checked before anything launches"""
+    require_cuda(x, labels, w, b, *extra)
+    if x.dim() != 2 or w.dim() != 2 or b.dim() != 1 or labels.dim() != 1:
+        raise _lib.DbmmError(f"linear probe: x [B, D], labels [B], w [C, D], b [C] expected; got {tuple(x.shape)}, {tuple(labels.shape)}, "
+                             f"{tuple(w.shape)}, {tuple(b.shape)}")
+    B, D = x.shape
+    C = w.shape[0]
+    for t in (x, w, b) + tuple(extra):
+        _f32c(t)
+    if labels.dtype != torch.int64 or not labels.is_contiguous():
+        raise _lib.DbmmError("linear probe: labels must be a contiguous int64 tensor")
+    if w.shape[1] != D or b.numel() != C or labels.numel() != B:
+        raise _lib.DbmmError(f"linear probe: x [{B}, {D}] against w {tuple(w.shape)}, b {tuple(b.shape)}, labels {tuple(labels.shape)}")
+    if B < 1 or not (1 <= C <= 8) or D % 4 or not (4 <= D <= 1024):
+        raise _lib.DbmmError(f"linear probe kernels serve B >= 1, C <= 8 classes, D % 4 == 0 and D <= 1024; got B={B} C={C} D={D}")
+    if any(t.device != x.device for t in (labels, w, b) + tuple(extra)):
+        raise _lib.DbmmError("linear probe: all operands must be on one device")
+    return B, D, C
+
+
+def linear_train_step(x, labels, w, b, m_w, m_b, lr, momentum, weight_decay, first_step):
+    """one fused linear-probe training step (dbmm_linear_train_step): w, b, m_w, m_b updated in place.
+    Returns (mean CE 0-dim, logits [B, C], per-row CE [B]), all on the device."""
+    B, D, C = _linear_operands(x, labels, w, b, (m_w, m_b))
+    if m_w.shape != w.shape or m_b.shape != b.shape:
+        raise _lib.DbmmError(f"linear probe: momentum buffers {tuple(m_w.shape)}, {tuple(m_b.shape)} for w {tuple(w.shape)}, b {tuple(b.shape)}")
+    dev = x.device
+    L = _lib.lib()
+    ws = _linear_workspace(dev, L.dbmm_workspace_bytes_linear_train_step(B, D, C))
+    logits = _empty((B, C), device=dev, dtype=torch.float32)
+    loss = _empty((B + 1,), device=dev, dtype=torch.float32)        # per-row losses, then their mean: one allocation
+    rc = L.dbmm_linear_train_step(x.data_ptr(), labels.data_ptr(), w.data_ptr(), b.data_ptr(), m_w.data_ptr(), m_b.data_ptr(),
+                                  float(lr), float(momentum), float(weight_decay), int(first_step), logits.data_ptr(),
+                                  loss.data_ptr(), loss.data_ptr() + 4 * B, B, D, C, ws.data_ptr(), ws.numel() * 4, stream())
+    if rc:
+        check(rc, "linear_train_step")
+    return loss[B], logits, loss[:B]
+
+
+def linear_ce_fwd(x, labels, w, b):
+    """the linear probe's eval forward (dbmm_linear_ce_fwd): (mean CE 0-dim, logits [B, C], per-row CE [B])"""
+    B, D, C = _linear_operands(x, labels, w, b)
+    dev = x.device
+    L = _lib.lib()
+    ws = _linear_workspace(dev, L.dbmm_workspace_bytes_linear_ce_fwd(B))
+    logits = _empty((B, C), device=dev, dtype=torch.float32)
+    loss = _empty((B + 1,), device=dev, dtype=torch.float32)
+    rc = L.dbmm_linear_ce_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), labels.data_ptr(), logits.data_ptr(), loss.data_ptr(),
+                              loss.data_ptr() + 4 * B, B, D, C, ws.data_ptr(), ws.numel() * 4, stream())
+    if rc:
+        check(rc, "linear_ce_fwd")
+    return loss[B], logits, loss[:B]
+
+
 def gather_rows(table, idx):
     """out[i] = table[idx[i]] for a device-resident [N, D] fp32 table and int64 indices."""
     require_cuda(table, idx)

@@ -86,6 +86,33 @@ def _results(counts, n_places=2):
     return adapter.get_results(meters, partial(adapter.get_y_p, n_places=n_places))
 
 
+def _train_pass(table, classifier, optimizer, batch_size, target, use_group, indices, shuffle, lr_hook, counts, loss_sum, counted=True):
+    """one loader pass of steps; `counted`: the pass adds to the epoch's loss sum and group counters.  Returns the pass's batches."""
+    n = len(table) if indices is None else len(indices)
+    batches = _epoch_batches(n, batch_size, shuffle, indices)
+    dev = table.device
+    for step, idx in enumerate(batches):
+        idx = idx.to(dev, non_blocking=True)
+        emb, labels, groups = table.batch(idx, target)
+        if use_group:
+            labels = groups
+        if lr_hook is not None:
+            lr_hook(step, len(batches))
+        loss, logits, _ = classifier.train_step(emb, labels, optimizer, use_group)
+        if counted:
+            loss_sum += loss.double() * idx.numel()                  # losses.update(loss.item(), bsz)
+            adapter.group_counts(logits, labels, groups, table.n_groups, counts)
+    return batches
+
+
+def _train_results(table, counts, loss_sum, n):
+    c = counts.cpu().numpy()
+    total = int(c[:, 0].sum())
+    res = _results(c, table.n_places)
+    group_acc = {k: np.round(res[k], 4) for k in NEW_ORDER_FOR_PRINT[1:]}
+    return c, (loss_sum.item() / n, int(c[:, 1].sum()) / total, group_acc)
+
+
 def train_epoch(table, classifier, optimizer, batch_size, target="class", use_group=False, indices=None,
                 shuffle=True, lr_hook=None, stats=None):
     """One epoch of train_one_epoch / train_reg_seq_one_epoch.  `indices` restricts the epoch to a
@@ -95,34 +122,43 @@ def train_epoch(table, classifier, optimizer, batch_size, target="class", use_gr
     the integer (n, correct) counters [G, 2] and the row order of the epoch."""
     classifier.train()
     n = len(table) if indices is None else len(indices)
-    batches = _epoch_batches(n, batch_size, shuffle, indices)
     dev = table.device
     counts = torch.zeros((table.n_groups, 2), dtype=torch.int64, device=dev)
     loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
-    for step, idx in enumerate(batches):
-        idx = idx.to(dev, non_blocking=True)
-        emb, labels, groups = table.batch(idx, target)
-        if use_group:
-            labels = groups
-        if lr_hook is not None:
-            lr_hook(step, len(batches))
-        loss, logits, _ = classifier.train_step(emb, labels, optimizer, use_group)
-        loss_sum += loss.double() * idx.numel()                      # losses.update(loss.item(), bsz)
-        adapter.group_counts(logits, labels, groups, table.n_groups, counts)
-    c = counts.cpu().numpy()
-    total = int(c[:, 0].sum())
-    res = _results(c, table.n_places)
-    group_acc = {k: np.round(res[k], 4) for k in NEW_ORDER_FOR_PRINT[1:]}
+    batches = _train_pass(table, classifier, optimizer, batch_size, target, use_group, indices, shuffle, lr_hook, counts, loss_sum)
+    c, out = _train_results(table, counts, loss_sum, n)
     if stats is not None:
         stats.update(counts=c, order=torch.cat(batches).numpy())
-    return loss_sum.item() / n, int(c[:, 1].sum()) / total, group_acc
+    return out
+
+
+def train_reg_epoch(train_table, reg_table, classifier, optimizer, batch_size, reg_rows, reg_batch_size, reg_shuffle, target="class",
+                    group_prompt=True, lr_hook=None, stats=None):
+    """One epoch of train_reg_one_epoch (final_main.py:498-569): the shuffled train split on the class prompts, then -- same
+    optimiser, same epoch -- the reg loader (`reg_rows` of `reg_table`, shuffled or not), on the group prompts with group labels
+    when `group_prompt`.  `lr_hook(step, n_steps)` restarts with each loader like the reference's warmup_learning_rate(opt, epoch,
+    idx, len(dataloader)).  Loss, accuracy and group counters accumulate over the batches scored on the class prompts only (the
+    train loader, and the reg loader when not `group_prompt`); one host sync per epoch.  `stats` receives the counters, the row
+    order (train rows, then the reg loop's rows) and the number of train rows."""
+    classifier.train()
+    dev = train_table.device
+    counts = torch.zeros((train_table.n_groups, 2), dtype=torch.int64, device=dev)
+    loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
+    b1 = _train_pass(train_table, classifier, optimizer, batch_size, target, False, None, True, lr_hook, counts, loss_sum)
+    b2 = _train_pass(reg_table, classifier, optimizer, reg_batch_size, target, group_prompt, reg_rows, reg_shuffle, lr_hook, counts, loss_sum,
+                     counted=not group_prompt)
+    n = len(train_table) + (0 if group_prompt else len(reg_rows))
+    c, out = _train_results(train_table, counts, loss_sum, n)
+    if stats is not None:
+        stats.update(counts=c, order=torch.cat(b1 + b2).numpy(), n_train_rows=len(train_table))
+    return out
 
 
 @torch.no_grad()
 def validate(table, classifier, batch_size, train_group_ratio, target="class", indices=None, spurious=False, stats=None):
     """validate / validate_zs (final_main.py:655-803): eval-mode forward, CE, group accuracies and
-    the train-ratio-weighted mean.  A LinearClassifier (tl_method linear_probing) is scored by validate_zs's
-    own branch (:730-761): normalised raw embeddings @ column-normalised text / T -- pass `zs_text` via zeroshot()."""
+    the train-ratio-weighted mean.  A LinearClassifier is scored through its own head (LinearClassifier.loss); its
+    zero-shot scores are validate_zs's own branch, validate_zs_linear_probing below."""
     classifier.eval()
     n = len(table) if indices is None else len(indices)
     dev = table.device
@@ -169,9 +205,9 @@ def validate_zs_linear_probing(table, text_embedding_dir, temperature, batch_siz
 
 
 def train_all_epochs(opt, train_table, val_table, test_table, input_dim=None, log=None):
-    """The training schedule of the reference's driver (final_main.py:805-1046) for the adapter methods -- `adapter`,
-    `adapter_reg_seq`, `adapter_reg_seq_alter`, with or without `--add_adapter`, `--balance_val`, `--continue_from_best` -- on
-    device-resident tables, every step one fused C call:
+    """The training schedule of the reference's driver (final_main.py:805-1046) -- `linear_probing` and `adapter_reg`
+    (_train_linear_probing / _train_adapter_reg below), and the adapter methods `adapter`, `adapter_reg_seq`, `adapter_reg_seq_alter`,
+    with or without `--add_adapter`, `--balance_val`, `--continue_from_best` -- on device-resident tables, every step one fused C call:
 
       stage 1 (epoch <= epochs_feature_learning): train_one_epoch on the train split (:935), lr by adjust_learning_rate + warm-up;
       switch (epoch == efl + 1): restart from the best model so far (:941-943), MultipleAdapter over it with a fresh Adapter and
@@ -189,8 +225,12 @@ def train_all_epochs(opt, train_table, val_table, test_table, input_dim=None, lo
     from copy import deepcopy
 
     from . import optim as O
+    if opt.tl_method == "linear_probing":
+        return _train_linear_probing(opt, train_table, val_table, test_table, input_dim, log)
+    if opt.tl_method == "adapter_reg":
+        return _train_adapter_reg(opt, train_table, val_table, test_table, input_dim, log)
     if opt.tl_method not in ("adapter", "adapter_reg_seq", "adapter_reg_seq_alter"):
-        raise ValueError(f"train_all_epochs covers the adapter methods, not tl_method={opt.tl_method!r}")
+        raise ValueError(f"train_all_epochs covers linear_probing and the adapter methods, not tl_method={opt.tl_method!r}")
     two_stage = opt.tl_method != "adapter"
     dev = train_table.device
     D = input_dim or train_table.embeddings.shape[1]
@@ -269,3 +309,106 @@ def train_all_epochs(opt, train_table, val_table, test_table, input_dim=None, lo
     rec(kind="validate_zs", target="spurious", loss=zss[0], acc=zss[1], group_acc=zss[2], **st)
     rec(kind="final", best_epoch=best_epoch, best_model=best_model)
     return (train_accs[best_epoch - 1], val_accs[best_epoch - 1], test_accs[best_epoch - 1]), (zs[2], zss[2])
+
+
+def _select_and_finish(rec, train_accs, val_accs, test_accs, best_epoch, best_model, zs, zss):
+    """records the zero-shot pair ((loss, acc, group acc, stats) each) and returns what train_all_epochs returns"""
+    rec(kind="validate_zs", target="class", loss=zs[0], acc=zs[1], group_acc=zs[2], **zs[3])
+    rec(kind="validate_zs", target="spurious", loss=zss[0], acc=zss[1], group_acc=zss[2], **zss[3])
+    rec(kind="final", best_epoch=best_epoch, best_model=best_model)
+    return (train_accs[best_epoch - 1], val_accs[best_epoch - 1], test_accs[best_epoch - 1]), (zs[2], zss[2])
+
+
+def _train_linear_probing(opt, train_table, val_table, test_table, input_dim, log):
+    """tl_method linear_probing (the reference's default): set_model's LinearClassifier(D, n_cls) (final_main.py:306-308), drawn on
+    the CPU from the global torch RNG, trained by train_one_epoch on the plain loaders (no reg split), validated on the WHOLE val
+    split, the best worst-group model kept; the zero-shot pair is validate_zs's linear_probing branch (raw embeddings against the
+    class / spurious prompts: the CLIP baseline, independent of the trained head)."""
+    from copy import deepcopy
+
+    from . import optim as O
+    dev = train_table.device
+    D = input_dim or train_table.embeddings.shape[1]
+    ratio = train_table.group_ratio.numpy()
+    rec = (lambda **k: log.append(k)) if log is not None else (lambda **k: None)
+    classifier = adapter.LinearClassifier(D, opt.n_cls)
+    rec(kind="init", state={k: v.clone() for k, v in classifier.state_dict().items()})
+    classifier = classifier.to(dev)
+    optimizer = O.set_optimizer(opt, classifier)
+    best_acc, best_epoch, best_model = 0, 0, None
+    train_accs, val_accs, test_accs = [], [], []
+    bs_eval = max(opt.batch_size, 4096)
+    for epoch in range(1, opt.epochs + 1):
+        O.adjust_learning_rate(opt, optimizer, epoch)
+        st = {}
+        hook = lambda i, n, e=epoch: O.warmup_learning_rate(opt, e, i, n, optimizer)
+        loss, acc, gacc = train_epoch(train_table, classifier, optimizer, opt.batch_size, target=opt.train_target, lr_hook=hook, stats=st)
+        rec(kind="train1", epoch=epoch, loss=loss, acc=acc, group_acc=gacc, **st)
+        train_accs.append(gacc)
+        st = {}
+        vloss, vacc, vg = validate(val_table, classifier, bs_eval, ratio, target=opt.train_target, stats=st)
+        rec(kind="validate", epoch=epoch, split="val", loss=vloss, acc=vacc, group_acc=vg, **st)
+        val_accs.append(vg)
+        if vg["worst_acc"] > best_acc:
+            best_acc, best_epoch, best_model = vg["worst_acc"], epoch, deepcopy(classifier)
+        st = {}
+        tloss, tacc, tg = validate(test_table, classifier, bs_eval, ratio, target="class", stats=st)
+        rec(kind="validate", epoch=epoch, split="test", loss=tloss, acc=tacc, group_acc=tg, **st)
+        test_accs.append(tg)
+    st, sts = {}, {}
+    zs = validate_zs_linear_probing(test_table, opt.text_embedding_dir, opt.zs_temperature, bs_eval, ratio, target="class", stats=st)
+    zss = validate_zs_linear_probing(test_table, opt.text_spurious_embedding_dir, opt.zs_temperature, bs_eval, ratio, target="spurious",
+                                     stats=sts)
+    return _select_and_finish(rec, train_accs, val_accs, test_accs, best_epoch, best_model, zs + (st,), zss + (sts,))
+
+
+def _train_adapter_reg(opt, train_table, val_table, test_table, input_dim, log):
+    """tl_method adapter_reg: one CustomCLIP(Adapter) and one optimiser for the whole run; every epoch is train_reg_one_epoch
+    (final_main.py:498-569, called at :924-931): the train split on the class prompts, then the reg half of the val split -- re-balanced
+    per epoch by balance_val (global numpy RNG; DataLoader(shuffle=False) with the adjusted batch) or the reg loader itself (shuffled,
+    batch_size_reg) -- on the group prompts with group labels, or on the class prompts under --use_cls_prompt_in_reg.  lr by
+    adjust_learning_rate and warmup_learning_rate, whose batch index and count restart with each loader.  Validation on the other half."""
+    from copy import deepcopy
+
+    from . import optim as O
+    dev = train_table.device
+    D = input_dim or train_table.embeddings.shape[1]
+    reg_idx, val_idx = adapter.stratified_split_indices(val_table.group_array, 0.5)
+    ratio = train_table.group_ratio.numpy()
+    rec = (lambda **k: log.append(k)) if log is not None else (lambda **k: None)
+    classifier = adapter.CustomCLIP(adapter.Adapter(D, opt.adapter_feat_dim), opt.text_embedding_dir, opt.text_spurious_embedding_dir,
+                                    opt.text_group_embedding_dir, temperature=opt.zs_temperature)
+    rec(kind="init", state={k: v.clone() for k, v in classifier.adapter.state_dict().items()})
+    classifier = classifier.to(dev)
+    optimizer = O.set_optimizer(opt, classifier)
+    best_acc, best_epoch, best_model = 0, 0, None
+    train_accs, val_accs, test_accs = [], [], []
+    bs_eval = max(opt.batch_size_reg, 4096)
+    use_group = not opt.use_cls_prompt_in_reg
+    for epoch in range(1, opt.epochs + 1):
+        O.adjust_learning_rate(opt, optimizer, epoch)
+        if opt.balance_val:                                              # DataLoader(balanced_subset, shuffle=False, batch_size=adjusted)
+            balanced, bs_reg = adapter.balance_val_indices(val_table.group_array[reg_idx], val_table.n_groups, opt.batch_size_reg)
+            rows, shuffle, bs = reg_idx[balanced], False, bs_reg
+        else:                                                            # the reg loader itself: shuffle=True
+            rows, shuffle, bs = reg_idx, True, opt.batch_size_reg
+        st = {}
+        hook = lambda i, n, e=epoch: O.warmup_learning_rate(opt, e, i, n, optimizer)
+        loss, acc, gacc = train_reg_epoch(train_table, val_table, classifier, optimizer, opt.batch_size, rows, bs, shuffle,
+                                          target=opt.train_target, group_prompt=use_group, lr_hook=hook, stats=st)
+        rec(kind="train_reg", epoch=epoch, use_group=use_group, loss=loss, acc=acc, group_acc=gacc, **st)
+        train_accs.append(gacc)
+        st = {}
+        vloss, vacc, vg = validate(val_table, classifier, bs_eval, ratio, target=opt.train_target, indices=val_idx, stats=st)
+        rec(kind="validate", epoch=epoch, split="val", loss=vloss, acc=vacc, group_acc=vg, **st)
+        val_accs.append(vg)
+        if vg["worst_acc"] > best_acc:
+            best_acc, best_epoch, best_model = vg["worst_acc"], epoch, deepcopy(classifier)
+        st = {}
+        tloss, tacc, tg = validate(test_table, classifier, bs_eval, ratio, target="class", stats=st)
+        rec(kind="validate", epoch=epoch, split="test", loss=tloss, acc=tacc, group_acc=tg, **st)
+        test_accs.append(tg)
+    st, sts = {}, {}
+    zs = validate(test_table, best_model, bs_eval, ratio, target="class", stats=st)
+    zss = validate(test_table, best_model, bs_eval, ratio, target="spurious", spurious=True, stats=sts)
+    return _select_and_finish(rec, train_accs, val_accs, test_accs, best_epoch, best_model, zs + (st,), zss + (sts,))

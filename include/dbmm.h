@@ -541,6 +541,26 @@ int dbmm_adapter_train_step(const float* x, const int64_t* labels, float* w1, fl
                             int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* One training step of the linear probe (final_main.py:43-49 LinearClassifier, trained at :426-496) in one call:
+ * logits = x W^T + b, per-row CE and its mean, dlogits = (softmax - onehot) / B, dW = dlogits^T x, db = colsum dlogits, then
+ * dbmm_sgd_momentum's update of w, b and their momentum buffers m_w, m_b in place.  x [B][D], labels int64 [B] in [0, C),
+ * w / m_w [C][D], b / m_b [C]; outputs logits [B][C], loss_rows [B], loss_mean [1].  C <= 8, D % 4 == 0, D <= 1024, any B >= 1.
+ * Every sum runs in a fixed order: identical inputs give identical bits.  One kernel launch (after a 4-byte memset of the
+ * workspace's ticket counter) up to the batch size of the option linear_step_one_launch_max_b, two launches above it.
+ * x, w, m_w and the workspace 16-byte aligned; workspace = dbmm_workspace_bytes_linear_train_step(B, D, C) bytes (0: bad shape). */
+size_t dbmm_workspace_bytes_linear_train_step(int64_t B, int64_t D, int64_t C);
+int dbmm_linear_train_step(const float* x, const int64_t* labels, float* w, float* b, float* m_w, float* m_b,
+                           float lr, float momentum, float weight_decay, int first_step,
+                           float* logits, float* loss_rows, float* loss_mean,
+                           int64_t B, int64_t D, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The linear probe's eval forward (validate, final_main.py:655-713): logits, per-row CE and the mean, no update.  Same shapes and
+ * rules as dbmm_linear_train_step; workspace = dbmm_workspace_bytes_linear_ce_fwd(B) bytes. */
+size_t dbmm_workspace_bytes_linear_ce_fwd(int64_t B);
+int dbmm_linear_ce_fwd(const float* x, const float* w, const float* b, const int64_t* labels,
+                       float* logits, float* loss_rows, float* loss_mean, int64_t B, int64_t D, int64_t C,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* out[i][:] = table[idx[i]][:] -- batch assembly from a device-resident embedding table
  * (replaces the DataLoader + per-item DataFrame lookups of data/ *_embeddings*.py) */
 int dbmm_gather_rows(const float* table, const int64_t* idx, float* out, int64_t n_rows,
