@@ -39,7 +39,8 @@ KERNEL_SOURCES = (
     ("conv3x3_f16", ("conv_f16.hip", "common.h")), ("conv1x1_f16", ("conv_f16.hip", "common.h")), ("stem_s2_f16", ("conv_f16.hip", "common.h")),
     ("avgpool2_f16", ("conv_f16.hip", "common.h")),
     ("stem_s2", ("resnet_ops.hip", "common.h")), ("attnpool", ("resnet_ops.hip", "common.h")),
-    ("adapter_step", ("adapter_step.hip", "common.h")),
+    ("adapter_step", ("adapter_step.hip", "adapter_bodies.inc", "common.h")),
+    ("sweep_", ("adapter_sweep.hip", "adapter_bodies.inc", "common.h")),
     ("linear_", ("linear_step.hip", "common.h")),
 )
 
@@ -169,6 +170,11 @@ _SIGS = {
     "dbmm_sgd_momentum": [_L, _P, _P, _P, _P, _F, _F, _F, _I, _P],
     "dbmm_workspace_bytes_adapter_train_step": [_L, _L, _L, _I],
     "dbmm_adapter_train_step": [_P] * 26 + [_F, _P, _F, _F, _F, _F, _I, _P, _P, _P, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_adapter_sweep_step": [_L, _L, _L, _L, _I],
+    "dbmm_adapter_sweep_step": [_P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _F, _P, _F, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _I, _L, _L, _L, _L, _L,
+                                _P, _Z, _P],
+    "dbmm_workspace_bytes_adapter_sweep_eval": [_L, _L, _L, _L, _I],
+    "dbmm_adapter_sweep_eval": [_P, _L, _P, _L, _P, _P, _P, _P, _F, _P, _F, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_linear_train_step": [_L, _L, _L],
     "dbmm_linear_train_step": [_P] * 6 + [_F, _F, _F, _I, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_linear_ce_fwd": [_L],
@@ -191,6 +197,8 @@ _RESTYPES = {
     "dbmm_workspace_bytes_adapter_bwd": c_size_t,
     "dbmm_workspace_bytes_adapter_train_step": c_size_t,
     "dbmm_workspace_bytes_linear_train_step": c_size_t,
+    "dbmm_workspace_bytes_adapter_sweep_step": c_size_t,
+    "dbmm_workspace_bytes_adapter_sweep_eval": c_size_t,
     "dbmm_workspace_bytes_linear_ce_fwd": c_size_t,
 }
 

@@ -392,6 +392,181 @@ class MultipleAdapter(CustomCLIP):
 
 
 # ---------------------------------------------------------------------------------------
+# stacked adapters of a seed sweep (trainer.train_sweep, csrc/adapter_sweep.hip)
+# ---------------------------------------------------------------------------------------
+
+def _adapter_tensors(ad):
+    """the nine tensors of an Adapter in the order of the C ABI's stacked arrays"""
+    l0, bn, l3 = ad.layers[0], ad.layers[1], ad.layers[3]
+    return [l0.weight, l0.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, l3.weight, l3.bias]
+
+
+_TRAINABLE = (0, 1, 2, 3, 7, 8)          # w1, b1, gamma, beta, w2, b2 among the nine
+
+
+class SweepAdapters:
+    """R adapters of one sweep group as stacked contiguous tensors: `new` -- the nine tensors of the trainable adapters
+    (w1 [R, H, D], b1, gamma, beta, running_mean, running_var [R, H], num_batches_tracked int64 [R], w2 [R, D, H], b2 [R, D]) --,
+    `mom` their six momentum buffers, optionally `old`, the nine tensors of the frozen old adapters of R MultipleAdapters, and the
+    shared prompt matrices.  One `step` trains all replicas in the launches of one single-run step, `evaluate` scores them on the
+    same rows; `replica(r)` gives replica r back as an ordinary CustomCLIP / MultipleAdapter (the reference's state-dict keys).
+    A second stacked set holds each replica's best model: `snapshot(mask)` / `restore(mask)` copy the masked replicas to / from it
+    (best-model selection and --continue_from_best); a replica's best model may be of either kind, whatever the others are."""
+
+    def __init__(self, new, old, D, H, device, text_dirs, temperature=0.01, ebd_weight=0.5):
+        self.new, self.old = new, old
+        self.R, self.D, self.H, self.device = new[0].shape[0], D, H, torch.device(device)
+        self.text_dirs, self.temperature, self.ebd_weight = tuple(text_dirs), temperature, ebd_weight
+        self.mom = [torch.zeros_like(self.new[i]) for i in _TRAINABLE]
+        self.first_step = True
+        self.best_new = self.best_old = None
+        self.best_has_old = [False] * self.R
+        self.has_best = [False] * self.R
+        self._args = {}
+        self._tn = {}
+
+    @classmethod
+    def from_modules(cls, modules, device="cuda"):
+        """from R CustomCLIP modules (stage 1) or R MultipleAdapter modules (old_cls.adapter frozen, new_adapter trained)"""
+        multi = isinstance(modules[0], MultipleAdapter)
+        if any(isinstance(m, MultipleAdapter) != multi for m in modules):
+            raise ValueError("SweepAdapters.from_modules: all replicas must be of one kind")
+        news = [m.new_adapter if multi else m.adapter for m in modules]
+        olds = [m.old_cls.adapter for m in modules] if multi else None
+        m0 = modules[0]
+        D, H = _adapter_tensors(news[0])[0].shape[1], _adapter_tensors(news[0])[0].shape[0]
+        return cls(cls._stack(news, device), cls._stack(olds, device) if olds else None, D, H, device,
+                   (m0.text_embedding_dir, m0.text_spurious_embedding_dir, m0.text_group_embedding_dir), m0.temperature,
+                   getattr(m0, "ebd_weight", 0.5))
+
+    @staticmethod
+    def _stack(adapters, device):
+        per = [[t.detach() for t in _adapter_tensors(a)] for a in adapters]
+        return [torch.stack([p[i] for p in per]).to(device).contiguous() for i in range(9)]
+
+    # ---- the two stage switches of train_all_epochs -----------------------------------------------------------------
+    def reset_optimizer(self):
+        """a fresh optimiser over the trainable set (set_optimizer_reg): momentum starts over"""
+        for m in self.mom:
+            m.zero_()
+        self.first_step = True
+
+    def add_adapters(self, new_adapters, init_near_identity):
+        """MultipleAdapter(classifier, new_adapter, init_near_identity) for every replica: the current adapters become the frozen
+        old ones, `new_adapters` (R fresh Adapter modules) the trainable ones -- loaded with the old state dicts (parameters and
+        BatchNorm buffers) when `init_near_identity`"""
+        if self.old is not None:
+            raise RuntimeError("SweepAdapters.add_adapters: the replicas already are MultipleAdapters")
+        self.old = self.new
+        self.new = [t.clone() for t in self.old] if init_near_identity else self._stack(new_adapters, self.device)
+        self._args = {}
+        self.reset_optimizer()
+
+    # ---- best models ------------------------------------------------------------------------------------------------
+    def snapshot(self, mask):
+        """best[r] = deepcopy(model r) for the replicas with mask[r]"""
+        rs = [r for r in range(self.R) if mask[r]]
+        if not rs:
+            return
+        if self.best_new is None:
+            self.best_new = [torch.zeros_like(t) for t in self.new]
+        if self.old is not None and self.best_old is None:
+            self.best_old = [torch.zeros_like(t) for t in self.old]
+            self._args.pop("best", None)
+        ix = torch.as_tensor(rs, device=self.device)
+        for dst, src in zip(self.best_new, self.new):
+            dst[ix] = src[ix]
+        if self.old is not None:
+            for dst, src in zip(self.best_old, self.old):
+                dst[ix] = src[ix]
+        for r in rs:
+            self.has_best[r], self.best_has_old[r] = True, self.old is not None
+        self._args.pop("best", None)
+
+    def restore(self, mask):
+        """model r = deepcopy(best[r]) for the replicas with mask[r] (--continue_from_best; only before add_adapters)"""
+        rs = [r for r in range(self.R) if mask[r]]
+        if any(not self.has_best[r] for r in rs):
+            raise RuntimeError("SweepAdapters.restore: a replica has no best model yet")
+        if any(self.best_has_old[r] for r in rs) or self.old is not None:
+            raise RuntimeError("SweepAdapters.restore: only plain (stage-1) best models can be continued from")
+        if rs:
+            ix = torch.as_tensor(rs, device=self.device)
+            for dst, src in zip(self.new, self.best_new):
+                dst[ix] = src[ix]
+
+    def subset(self, rs, best=False):
+        """a SweepAdapters of (copies of) the replicas `rs`, of their best models when `best`; they must be of one kind"""
+        new, old = (self.best_new, self.best_old) if best else (self.new, self.old)
+        kinds = {self.best_has_old[r] for r in rs} if best else {self.old is not None}
+        if len(kinds) != 1:
+            raise ValueError("SweepAdapters.subset: replicas of both kinds")
+        ix = torch.as_tensor(list(rs), device=self.device)
+        return SweepAdapters([t[ix].contiguous() for t in new], [t[ix].contiguous() for t in old] if kinds.pop() else None, self.D, self.H,
+                             self.device, self.text_dirs, self.temperature, self.ebd_weight)
+
+    def replica(self, r, best=False):
+        """replica r (its best model when `best`) as an ordinary module on the sweep's device, in eval mode"""
+        new, old = (self.best_new, self.best_old) if best else (self.new, self.old)
+        with_old = self.best_has_old[r] if best else self.old is not None
+        if best and not self.has_best[r]:
+            return None
+
+        def build(stack):
+            ad = Adapter(self.D, self.H)
+            with torch.no_grad():
+                for dst, src in zip(_adapter_tensors(ad), stack):
+                    dst.copy_(src[r])
+            return ad
+        prev = torch.get_rng_state()                 # Adapter() draws its initial weights: the caller's random stream is left alone
+        try:
+            m = CustomCLIP(build(old if with_old else new), *self.text_dirs, temperature=self.temperature)
+            if with_old:
+                import contextlib, io
+                with contextlib.redirect_stdout(io.StringIO()):
+                    m = MultipleAdapter(m, build(new), init_near_identity=False, ebd_weight=self.ebd_weight)
+        finally:
+            torch.set_rng_state(prev)
+        return m.to(self.device).eval()
+
+    # ---- the two batched calls ----------------------------------------------------------------------------------------
+    def text(self, which):
+        """column-normalised [C, D] prompt matrix: "class", "spurious" or "group" """
+        tn = self._tn.get(which)
+        if tn is None:
+            path = self.text_dirs[{"class": 0, "spurious": 1, "group": 2}[which]]
+            tn = ops.text_colnorm(get_text_embedding(path).to(self.device).contiguous().float())
+            self._tn[which] = tn
+        return tn
+
+    def _call_args(self, best=False):
+        key = "best" if best else "cur"
+        a = self._args.get(key)
+        if a is None:
+            if best:
+                a = ops.adapter_sweep_args(self.R, self.D, self.H, self.best_new, None, self.best_old if self.best_has_old[0] else None)
+            else:
+                a = ops.adapter_sweep_args(self.R, self.D, self.H, self.new, self.mom, self.old)
+            self._args[key] = a
+        return a
+
+    def step(self, table, idx, labels, groups, which, lrs, momentum, weight_decay, counts, loss_sum, counted=True):
+        """one training step of every replica on rows idx[r] of `table` against the `which` prompts.  Returns (mean CE [R], logits
+        [R, B, C], per-row CE [R, B])"""
+        out = ops.adapter_sweep_step(table, idx, labels, groups, self._call_args(), self.ebd_weight, self.text(which), self.temperature, lrs,
+                                     momentum, weight_decay, self.first_step, counts, loss_sum, counted)
+        self.first_step = False
+        return out
+
+    def evaluate(self, table, idx, labels, groups, which, counts, loss_sum, row0=0, n=None, best=False):
+        """eval-mode forward of every replica (of the best models when `best`: they must be of one kind) over the same rows"""
+        if best and len({self.best_has_old[r] for r in range(self.R)}) != 1:
+            raise ValueError("SweepAdapters.evaluate(best=True): best models of both kinds; evaluate subset()s")
+        return ops.adapter_sweep_eval(table, idx, labels, groups, self._call_args(best), self.ebd_weight, self.text(which), self.temperature,
+                                      counts, loss_sum, row0, n)
+
+
+# ---------------------------------------------------------------------------------------
 # metrics (final_main.py:383-412, demo/util.py:18-46)
 # ---------------------------------------------------------------------------------------
 

@@ -19,6 +19,8 @@ int dbmm_adapter_bwd_fast(const float* x, const float* dz, const float* h, const
 
 namespace {
 
+#include "adapter_bodies.inc"
+
 // ---- BatchNorm1d(H) statistics over the batch: 8 columns x 32 row-lanes per block ---------
 __global__ __launch_bounds__(256) void bn1d_stats_kernel(const float* __restrict__ h, int B, int H, float eps,
                                                          float momentum, float* __restrict__ mean_o,
@@ -168,66 +170,7 @@ __global__ __launch_bounds__(256) void text_colnorm_kernel(const float* __restri
     for (int i = threadIdx.x; i < D; i += 256) tn[(long long)c * D + i] = text[(long long)i * C + c] * inv;
 }
 
-// ---- fused row L2-norm + logits + CE: one wave per row -------------------------------------
-// forward of one row by one wave (every lane ends up with the row's logits lg[] and 1 / ||z||); lane 0 writes the outputs
-template <int CMAX>
-__device__ __forceinline__ void ce_fwd_row(const float* __restrict__ z, const float* __restrict__ z_old, float w_old, const float* __restrict__ tn,
-                                           const long long* __restrict__ labels, float invT, float* __restrict__ logits,
-                                           float* __restrict__ loss_rows, long long* __restrict__ pred, float* __restrict__ inv_norm, int row,
-                                           int lane, int D4, int C, float (&lg)[CMAX], float& inv) {
-    const f32x4* zr = (const f32x4*)z + (long long)row * D4;
-    const f32x4* zo = z_old ? (const f32x4*)z_old + (long long)row * D4 : nullptr;
-    float ss = 0.f, sso = 0.f, dot[CMAX], doto[CMAX];
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) { dot[c] = 0.f; doto[c] = 0.f; }
-    for (int i = lane; i < D4; i += 64) {
-        const f32x4 v = zr[i];
-        ss += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-        f32x4 vo = {0.f, 0.f, 0.f, 0.f};
-        if (zo) { vo = zo[i]; sso += (vo[0] * vo[0] + vo[1] * vo[1]) + (vo[2] * vo[2] + vo[3] * vo[3]); }
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            if (c < C) {
-                const f32x4 t = ((const f32x4*)tn)[(long long)c * D4 + i];
-                dot[c] += (v[0] * t[0] + v[1] * t[1]) + (v[2] * t[2] + v[3] * t[3]);
-                if (zo) doto[c] += (vo[0] * t[0] + vo[1] * t[1]) + (vo[2] * t[2] + vo[3] * t[3]);
-            }
-        }
-    }
-    ss = wave_sum(ss);
-    inv = 1.f / sqrtf(ss);
-    float invo = 0.f;
-    if (zo) invo = 1.f / sqrtf(wave_sum(sso));
-    float mx = -INFINITY;
-    int am = 0;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-        lg[c] = -INFINITY;
-        if (c < C) {
-            const float d = wave_sum(dot[c]) * inv;
-            float f = d;
-            if (zo) f = w_old * (wave_sum(doto[c]) * invo) + (1.f - w_old) * d;
-            lg[c] = f * invT;
-            if (lg[c] > mx) { mx = lg[c]; am = c; }
-        }
-    }
-    if (lane == 0) {
-        if (inv_norm) inv_norm[row] = inv;
-        if (logits) for (int c = 0; c < C; ++c) logits[(long long)row * C + c] = lg[c];
-        if (pred) pred[row] = am;
-        if (loss_rows && labels) {
-            float se = 0.f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) if (c < C) se += expf(lg[c] - mx);
-            const int y = (int)labels[row];
-            float ly = 0.f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) if (c == y) ly = lg[c];
-            loss_rows[row] = (mx + logf(se)) - ly;
-        }
-    }
-}
-
+// ---- fused row L2-norm + logits + CE: one wave per row (ce_fwd_row / ce_bwd_row: adapter_bodies.inc) ----------------
 template <int CMAX>
 __global__ __launch_bounds__(256) void l2norm_sim_ce_fwd_kernel(
     const float* __restrict__ z, const float* __restrict__ z_old, float w_old, const float* __restrict__ tn,
@@ -236,7 +179,7 @@ __global__ __launch_bounds__(256) void l2norm_sim_ce_fwd_kernel(
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= B) return;
     float lg[CMAX], inv;
-    ce_fwd_row<CMAX>(z, z_old, w_old, tn, labels, invT, logits, loss_rows, pred, inv_norm, row, lane, D4, C, lg, inv);
+    ce_fwd_row<CMAX>(z, z_old, w_old, tn, labels, invT, logits, loss_rows, pred, inv_norm, row, lane, D4, C, lg, inv, row);
 }
 
 __global__ __launch_bounds__(256) void mean_reduce_kernel(const float* __restrict__ x, int n, float* __restrict__ out) {
@@ -249,47 +192,6 @@ __global__ __launch_bounds__(256) void mean_reduce_kernel(const float* __restric
     if (threadIdx.x == 0) *out = ((red[0] + red[1]) + (red[2] + red[3])) / (float)n;
 }
 
-// backward of one row by one wave: dz from the row's logits `lgv` (read back or still in registers), its label and 1 / ||z||
-template <int CMAX>
-__device__ __forceinline__ void ce_bwd_row(const float* __restrict__ z, float inv, float w_new, const float* __restrict__ tn, const float (&lgv)[CMAX],
-                                           const long long* __restrict__ labels, const float* __restrict__ dlogits, float invT, float gscale,
-                                           float* __restrict__ dz, int row, int lane, int D4, int C) {
-    float dl[CMAX];
-    if (dlogits) {   // upstream gradient given (autograd path): dl = dlogits / T * blend weight
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) dl[c] = (c < C) ? dlogits[(long long)row * C + c] * invT * w_new : 0.f;
-    } else {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) { dl[c] = (c < C) ? lgv[c] : -INFINITY; mx = fmaxf(mx, dl[c]); }
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) { dl[c] = (c < C) ? expf(dl[c] - mx) : 0.f; se += dl[c]; }
-        const int y = (int)labels[row];
-        const float k = gscale * invT * w_new;   // d loss / d (feat . tn[c]) incl. blend weight
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) dl[c] = (dl[c] / se - (c == y ? 1.f : 0.f)) * k;
-    }
-    const f32x4* zr = (const f32x4*)z + (long long)row * D4;
-    float fd = 0.f;
-    for (int i = lane; i < D4; i += 64) {
-        f32x4 df = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) if (c < C) df += dl[c] * ((const f32x4*)tn)[(long long)c * D4 + i];
-        const f32x4 f = zr[i] * inv;
-        fd += (f[0] * df[0] + f[1] * df[1]) + (f[2] * df[2] + f[3] * df[3]);
-    }
-    fd = wave_sum(fd);
-    f32x4* dzr = (f32x4*)dz + (long long)row * D4;
-    for (int i = lane; i < D4; i += 64) {
-        f32x4 df = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) if (c < C) df += dl[c] * ((const f32x4*)tn)[(long long)c * D4 + i];
-        const f32x4 f = zr[i] * inv;
-        dzr[i] = (df - f * fd) * inv;
-    }
-}
-
 template <int CMAX>
 __global__ __launch_bounds__(256) void l2norm_sim_ce_bwd_kernel(
     const float* __restrict__ z, const float* __restrict__ inv_norm, float w_new, const float* __restrict__ tn,
@@ -300,7 +202,7 @@ __global__ __launch_bounds__(256) void l2norm_sim_ce_bwd_kernel(
     float lgv[CMAX];
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) lgv[c] = (logits && c < C) ? logits[(long long)row * C + c] : -INFINITY;
-    ce_bwd_row<CMAX>(z, inv_norm[row], w_new, tn, lgv, labels, dlogits, invT, gscale, dz, row, lane, D4, C);
+    ce_bwd_row<CMAX>(z, inv_norm[row], w_new, tn, lgv, labels, dlogits, invT, gscale, dz, row, lane, D4, C, row);
 }
 
 // the one-call step: forward and backward of a row in ONE launch (both are row-local; the logits stay in registers).  Same
@@ -313,8 +215,8 @@ __global__ __launch_bounds__(256) void l2norm_sim_ce_fwdbwd_kernel(
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= B) return;
     float lg[CMAX], inv;
-    ce_fwd_row<CMAX>(z, z_old, w_old, tn, labels, invT, logits, loss_rows, nullptr, nullptr, row, lane, D4, C, lg, inv);
-    ce_bwd_row<CMAX>(z, inv, w_new, tn, lg, labels, nullptr, invT, gscale, dz, row, lane, D4, C);
+    ce_fwd_row<CMAX>(z, z_old, w_old, tn, labels, invT, logits, loss_rows, nullptr, nullptr, row, lane, D4, C, lg, inv, row);
+    ce_bwd_row<CMAX>(z, inv, w_new, tn, lg, labels, nullptr, invT, gscale, dz, row, lane, D4, C, row);
 }
 
 // ---- multi-tensor SGD with momentum ---------------------------------------------------------
@@ -327,18 +229,7 @@ struct SgdArgs {
 };
 __global__ __launch_bounds__(256) void sgd_kernel(const SgdArgs a, float lr, float mu, float wd, int first) {
     const int t = blockIdx.y;
-    float* p = a.p[t]; const float* g = a.g[t]; float* m = a.m[t];
-    const long long n = a.n[t];
-    const int ns = a.ns[t];
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float w = p[i];
-        float gv = g[i];
-        for (int sidx = 1; sidx < ns; ++sidx) gv += g[(long long)sidx * n + i];
-        const float gi = fmaf(wd, w, gv);
-        const float b = first ? gi : fmaf(mu, m[i], gi);
-        m[i] = b;
-        p[i] = w - lr * b;
-    }
+    sgd_body(blockIdx, gridDim, a.p[t], a.g[t], a.m[t], a.n[t], a.ns[t], lr, mu, wd, first);
 }
 
 // ---- update_dict counters --------------------------------------------------------------------

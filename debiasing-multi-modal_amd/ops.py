@@ -780,6 +780,144 @@ def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature
     return loss[B], logits, loss[:B]
 
 
+_sweep_ws = {}
+
+
+def _sweep_workspace(dev, nbytes):
+    ws = _sweep_ws.get(dev.index)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _empty(max((nbytes + 3) // 4, 4), device=dev, dtype=torch.float32)     # 0 bytes: a shape the library will refuse by name
+        _sweep_ws[dev.index] = ws
+    return ws
+
+
+def adapter_sweep_args(R, D, H, new, bufs, old=None):
+    """the pointer arrays of dbmm_adapter_sweep_step / _eval, built and shape-checked once: `new` / `old` are the nine stacked tensors
+    (w1 [R, H, D], b1, gamma, beta, running_mean, running_var [R, H], nbt int64 [R], w2 [R, D, H], b2 [R, D]) of R adapters, `bufs`
+    the six stacked momentum buffers in the order (w1, b1, gamma, beta, w2, b2), or None (evaluation only); `old` may be None.
+    Valid while those tensors keep their storage (the arrays hold raw addresses, the tuple keeps the tensors alive)."""
+    sizes = (R * H * D, R * H, R * H, R * H, R * H, R * H, R, R * D * H, R * D)
+    names = ("w1", "b1", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked", "w2", "b2")
+
+    def stack(ts, what):
+        ts = list(ts)
+        if len(ts) != 9:
+            raise _lib.DbmmError(f"adapter sweep: {what} must be the nine stacked tensors, got {len(ts)}")
+        require_cuda(*ts)
+        for i, (t, n, nm) in enumerate(zip(ts, sizes, names)):
+            _sized(f"adapter sweep {what}.{nm}", t, n)
+            want = torch.int64 if i == 6 else torch.float32
+            if t.dtype != want or not t.is_contiguous():
+                raise _lib.DbmmError(f"adapter sweep {what}.{nm}: expected a contiguous {want} tensor")
+        return (ctypes.c_void_p * 9)(*[t.data_ptr() for t in ts]), ts
+
+    P, keep = stack(new, "params")
+    Bf = None
+    if bufs is not None:
+        bufs = list(bufs)
+        if len(bufs) != 6:
+            raise _lib.DbmmError("adapter sweep: six momentum buffers expected")
+        require_cuda(*bufs)
+        for t, i in zip(bufs, (0, 1, 2, 3, 7, 8)):
+            _sized(f"adapter sweep momentum.{names[i]}", t, sizes[i])
+            _f32c(t)
+        Bf = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in bufs])
+        keep = keep + bufs
+    O = None
+    if old is not None:
+        O, k2 = stack(old, "old")
+        keep = keep + k2
+    return dict(P=P, Bf=Bf, O=O, R=R, D=D, H=H, keep=keep)
+
+
+def _sweep_tables(table, labels, groups, args):
+    require_cuda(table, labels, groups)
+    _f32c(table)
+    if table.dim() != 2 or table.shape[1] != args["D"]:
+        raise _lib.DbmmError(f"adapter sweep: table {tuple(table.shape)} for adapters of width {args['D']}")
+    for nm, t in (("labels", labels), ("groups", groups)):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise _lib.DbmmError(f"adapter sweep: {nm} must be a contiguous int64 tensor")
+        _sized(f"adapter sweep {nm}", t, table.shape[0])
+
+
+def _sweep_metrics(counts, loss_sum, R):
+    require_cuda(counts, loss_sum)
+    if counts.dtype != torch.int64 or not counts.is_contiguous() or counts.dim() != 3 or counts.shape[0] != R or counts.shape[2] != 2:
+        raise _lib.DbmmError(f"adapter sweep: counts must be a contiguous int64 [R, G, 2] tensor, got {tuple(counts.shape)} {counts.dtype}")
+    if loss_sum.dtype != torch.float64 or not loss_sum.is_contiguous():
+        raise _lib.DbmmError("adapter sweep: loss_sum must be a contiguous float64 tensor")
+    _sized("adapter sweep loss_sum", loss_sum, R)
+    return counts.shape[1]
+
+
+def adapter_sweep_step(table, idx, labels, groups, args, ebd_weight, tn, temperature, lrs, momentum, weight_decay, first_step, counts, loss_sum,
+                       counted=True):
+    """one training step of R replicas in the launches of one (dbmm_adapter_sweep_step): replica r trains on rows idx[r] of `table`
+    ([N, D] fp32; labels / groups int64 [N]); `args` from adapter_sweep_args(); `lrs` R host floats; counts int64 [R, G, 2] and
+    loss_sum float64 [R] are accumulated in place when `counted`.  Returns (mean CE [R], logits [R, B, C], per-row CE [R, B])."""
+    R, D, H = args["R"], args["D"], args["H"]
+    if args["Bf"] is None:
+        raise _lib.DbmmError("adapter sweep step: adapter_sweep_args() was built without momentum buffers")
+    _sweep_tables(table, labels, groups, args)
+    require_cuda(idx, tn)
+    if idx.dtype != torch.int64 or not idx.is_contiguous() or idx.dim() != 2:
+        raise _lib.DbmmError("adapter sweep step: idx must be a contiguous int64 [R, B] tensor")
+    _f32c(tn)
+    if tn.dim() != 2 or tn.shape[1] != D:
+        raise _lib.DbmmError(f"adapter sweep: prompt matrix {tuple(tn.shape)} for width {D}")
+    G = _sweep_metrics(counts, loss_sum, R)
+    if len(lrs) != R:
+        raise _lib.DbmmError(f"adapter sweep step: {len(lrs)} learning rates for {R} replicas")
+    B, C = idx.shape[1], tn.shape[0]
+    dev = table.device
+    L = _lib.lib()
+    ws = _sweep_workspace(dev, L.dbmm_workspace_bytes_adapter_sweep_step(R, B, D, H, int(args["O"] is not None)))
+    logits = _empty((R, B, C), device=dev, dtype=torch.float32)
+    loss = _empty((R, B + 1), device=dev, dtype=torch.float32)          # [:, :B] would not be contiguous: rows first, then the R means
+    loss = loss.view(-1)
+    LR = (ctypes.c_float * R)(*[float(v) for v in lrs])
+    rc = L.dbmm_adapter_sweep_step(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(),
+                                   args["P"], args["Bf"], args["O"], float(ebd_weight), tn.data_ptr(), float(temperature), LR, float(momentum),
+                                   float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * R * B,
+                                   counts.data_ptr(), loss_sum.data_ptr(), G, int(counted), R, B, D, H, C, ws.data_ptr(), ws.numel() * 4, stream())
+    if rc:
+        check(rc, "adapter_sweep_step")
+    return loss[R * B:], logits, loss[:R * B].view(R, B)
+
+
+def adapter_sweep_eval(table, idx, labels, groups, args, ebd_weight, tn, temperature, counts, loss_sum, row0=0, n=None):
+    """the eval-mode forward of R replicas over the same rows (dbmm_adapter_sweep_eval): rows idx (int64 [B]) of `table`, or
+    idx None: rows row0 .. row0 + n - 1.  counts int64 [R, G, 2] and loss_sum float64 [R] are accumulated in place.  Returns
+    (logits [R, B, C], per-row CE [R, B])."""
+    R, D, H = args["R"], args["D"], args["H"]
+    _sweep_tables(table, labels, groups, args)
+    require_cuda(tn)
+    _f32c(tn)
+    if tn.dim() != 2 or tn.shape[1] != D:
+        raise _lib.DbmmError(f"adapter sweep: prompt matrix {tuple(tn.shape)} for width {D}")
+    if idx is not None:
+        require_cuda(idx)
+        if idx.dtype != torch.int64 or not idx.is_contiguous() or idx.dim() != 1:
+            raise _lib.DbmmError("adapter sweep eval: idx must be a contiguous int64 [B] tensor")
+        B = idx.shape[0]
+    else:
+        B = table.shape[0] - row0 if n is None else n
+    G = _sweep_metrics(counts, loss_sum, R)
+    C = tn.shape[0]
+    dev = table.device
+    L = _lib.lib()
+    ws = _sweep_workspace(dev, L.dbmm_workspace_bytes_adapter_sweep_eval(R, B, D, H, int(args["O"] is not None)))
+    logits = _empty((R, B, C), device=dev, dtype=torch.float32)
+    rows = _empty((R, B), device=dev, dtype=torch.float32)
+    rc = L.dbmm_adapter_sweep_eval(table.data_ptr(), table.shape[0], ptr(idx), row0, labels.data_ptr(), groups.data_ptr(), args["P"], args["O"],
+                                   float(ebd_weight), tn.data_ptr(), float(temperature), logits.data_ptr(), rows.data_ptr(), counts.data_ptr(),
+                                   loss_sum.data_ptr(), G, R, B, D, H, C, ws.data_ptr(), ws.numel() * 4, stream())
+    if rc:
+        check(rc, "adapter_sweep_eval")
+    return logits, rows
+
+
 _linear_ws = {}
 
 

@@ -412,3 +412,361 @@ def _train_adapter_reg(opt, train_table, val_table, test_table, input_dim, log):
     zs = validate(test_table, best_model, bs_eval, ratio, target="class", stats=st)
     zss = validate(test_table, best_model, bs_eval, ratio, target="spurious", spurious=True, stats=sts)
     return _select_and_finish(rec, train_accs, val_accs, test_accs, best_epoch, best_model, zs + (st,), zss + (sts,))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# seed sweeps (run_multiple/final_main_iteration_wb.py, final_main_iteration_ca.py): R runs in lock-step, one launch for all
+# ---------------------------------------------------------------------------------------------------------------------
+
+class ReplicaStreams:
+    """The global torch and numpy random streams of R runs that advance in lock-step.  In the reference each seed's run owns the
+    two global streams from set_seed to its end; here every replica keeps its own saved pair of states, swapped in around each
+    host-side draw: `run(r, fn, *args)` calls fn with replica r's streams installed and saves them again.  The draws themselves
+    are the ordinary functions (module constructors, dataloader_shuffle_order, balance_val_indices), unchanged."""
+
+    def __init__(self, seeds):
+        from . import optim as O
+        self.states = []
+        for s in seeds:
+            O.set_seed(s)
+            self.states.append((torch.get_rng_state(), np.random.get_state()))
+
+    def run(self, r, fn, *args, **kwargs):
+        t, n = self.states[r]
+        torch.set_rng_state(t)
+        np.random.set_state(n)
+        try:
+            return fn(*args, **kwargs)
+        finally:
+            self.states[r] = (torch.get_rng_state(), np.random.get_state())
+
+
+def _sweep_replicas(opt, seeds, learning_rates):
+    """(opt of the replica, seed) pairs, learning-rate-major like final_main_iteration_ca.py's loops"""
+    from copy import copy
+    if learning_rates is None:
+        return [(opt, s) for s in seeds]
+    out = []
+    for lr in learning_rates:
+        o = copy(opt)
+        o.learning_rate = lr
+        o.learning_rate_reg = lr * getattr(opt, "lr_multiple", 1.0)
+        out += [(o, s) for s in seeds]
+    return out
+
+
+class _Lr:
+    """what the schedule helpers of optim.py need of an optimiser: param_groups with an 'lr'"""
+    def __init__(self, lr):
+        self.param_groups = [{"lr": lr}]
+
+    @property
+    def lr(self):
+        return self.param_groups[0]["lr"]
+
+
+def _eval_results(table, c, loss_sum, n, ratio):
+    """the tail of validate() from the counters of one replica"""
+    res = _results(c, table.n_places)
+    indiv = [res[f"acc_{g // table.n_places}_{g % table.n_places}"] for g in range(table.n_groups)]
+    res["weighted_mean_acc"] = (np.array(indiv) * np.array(ratio)).sum()
+    group_acc = {k: np.round(res[k], 4) for k in NEW_ORDER_FOR_PRINT}
+    return loss_sum / n, int(c[:, 1].sum()) / int(c[:, 0].sum()), group_acc
+
+
+def _sweep_train_pass(streams, sweep, table, orders_fn, batch_size, target, use_group, lr_fn, momentum, weight_decay):
+    """one loader pass of every replica: `orders_fn(r)` draws replica r's row order (under its own streams), all orders go to the
+    device in ONE upload, then n_steps batched steps; lr_fn(step, n_steps) -> the R learning rates.  Returns (counts [R, G, 2] numpy,
+    loss sums [R] numpy, orders) after the pass's one host sync."""
+    R, dev = sweep.R, table.device
+    orders = [streams.run(r, orders_fn, r) for r in range(R)]
+    n = len(orders[0])
+    if any(len(o) != n for o in orders):
+        raise RuntimeError("sweep: replicas of one group must have passes of equal length")
+    idx = torch.stack(orders).to(dev, non_blocking=True)                          # [R, n]: the pass's one index upload
+    n_full, rem = divmod(n, batch_size)
+    steps = []
+    if n_full:
+        full = idx[:, :n_full * batch_size].view(R, n_full, batch_size).permute(1, 0, 2).contiguous()       # [n_steps, R, B]
+        steps += [full[i] for i in range(n_full)]
+    if rem:
+        if rem < 2:
+            raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d)")
+        steps.append(idx[:, n_full * batch_size:].contiguous())
+    counts = torch.zeros((R, table.n_groups, 2), dtype=torch.int64, device=dev)
+    loss_sum = torch.zeros((R,), dtype=torch.float64, device=dev)
+    labels = table.targets_group if use_group else table.labels(target)
+    which = "group" if use_group else "class"
+    for i, b in enumerate(steps):
+        sweep.step(table.embeddings, b, labels, table.targets_group, which, lr_fn(i, len(steps)), momentum, weight_decay, counts, loss_sum)
+    return counts.cpu().numpy(), loss_sum.cpu().numpy(), [o.numpy() for o in orders]
+
+
+def _sweep_validate(streams, sweep, table, batch_size, target, indices_dev, n, spurious=False, best=False, draw=True):
+    """validate() for every replica: every replica's stream advances by the one draw a loader pass makes; the rows are the same
+    for all replicas.  Returns (counts [R, G, 2], loss sums [R]) as numpy arrays."""
+    R, dev = sweep.R, table.device
+    if draw:
+        for r in range(R):
+            streams.run(r, lambda: torch.empty((), dtype=torch.int64).random_())
+    counts = torch.zeros((R, table.n_groups, 2), dtype=torch.int64, device=dev)
+    loss_sum = torch.zeros((R,), dtype=torch.float64, device=dev)
+    labels = table.labels(target)
+    which = "spurious" if spurious else "class"
+    for i in range(0, n, batch_size):
+        m = min(batch_size, n - i)
+        if indices_dev is not None:
+            sweep.evaluate(table.embeddings, indices_dev[i:i + m], labels, table.targets_group, which, counts, loss_sum, best=best)
+        else:
+            sweep.evaluate(table.embeddings, None, labels, table.targets_group, which, counts, loss_sum, row0=i, n=m, best=best)
+    return counts.cpu().numpy(), loss_sum.cpu().numpy()
+
+
+def train_sweep(opt, train_table, val_table, test_table, seeds, learning_rates=None, log=None):
+    """A seed sweep as one batched run: returns, per replica, exactly what `train_all_epochs` returns for that replica run alone
+    after `optim.set_seed(seed)`.  Replicas are (learning rate, seed) pairs, learning-rate-major; with `learning_rates` given,
+    replica (lr, seed) runs with learning_rate = lr and learning_rate_reg = lr * opt.lr_multiple, like final_main_iteration_ca.py.
+
+    Batched path -- tl_method `adapter`, `adapter_reg_seq`, `adapter_reg_seq_alter`, with or without --add_adapter, --balance_val,
+    --continue_from_best, --init_near_identity (the main branch of train_all_epochs), on the adapter's fast shape (hidden width 128,
+    D % 128 == 0) and at least two replicas: all replicas advance in lock-step, every training step and every evaluation batch is one
+    replica-batched call (adapter.SweepAdapters; up to 16 replicas per group of launches, more are split into groups), each pass
+    uploads its row orders once and synchronises with the host once, best-model selection runs per replica on the host.
+    Sequential path -- `adapter_reg`, `linear_probing`, other shapes and a single replica: replica by replica through
+    train_all_epochs on the same tables.  `contrastive_adapter` raises like train_all_epochs.
+
+    Each replica keeps its own pair of global random streams (ReplicaStreams), so its initial weights, batch orders and balanced
+    subsets are those of its own sequential run.  `log` (a list) receives one list of records per replica (train_all_epochs' records)."""
+    from . import optim as O
+    replicas = _sweep_replicas(opt, list(seeds), learning_rates)
+    D = train_table.embeddings.shape[1]
+    batched = (opt.tl_method in ("adapter", "adapter_reg_seq", "adapter_reg_seq_alter") and len(replicas) >= 2
+               and opt.adapter_feat_dim == 128 and D % 128 == 0 and bool(ops.get_option("adapter_step_fused")))
+    if opt.tl_method not in ("adapter", "adapter_reg_seq", "adapter_reg_seq_alter", "adapter_reg", "linear_probing"):
+        raise ValueError(f"train_sweep covers linear_probing and the adapter methods, not tl_method={opt.tl_method!r}")
+    if not batched:
+        out = []
+        for o, s in replicas:
+            O.set_seed(s)
+            lg = [] if log is not None else None
+            out.append(train_all_epochs(o, train_table, val_table, test_table, log=lg))
+            if log is not None:
+                log.append(lg)
+        return out
+    out = []
+    for i in range(0, len(replicas), 16):
+        out += _train_sweep_group(replicas[i:i + 16], train_table, val_table, test_table, log)
+    return out
+
+
+def _train_sweep_group(replicas, train_table, val_table, test_table, log):
+    """train_all_epochs' main branch for up to 16 replicas in lock-step; statement for statement the sequential schedule, with
+    every per-replica host decision (learning rate, best model) taken per replica"""
+    from . import optim as O
+    opts = [o for o, _ in replicas]
+    opt = opts[0]
+    R = len(replicas)
+    two_stage = opt.tl_method != "adapter"
+    dev = train_table.device
+    D = train_table.embeddings.shape[1]
+    reg_idx = val_idx = val_idx_dev = None
+    if two_stage:
+        reg_idx, val_idx = adapter.stratified_split_indices(val_table.group_array, 0.5)
+        val_idx_dev = torch.as_tensor(val_idx, dtype=torch.int64).to(dev)
+    n_val = len(val_table) if val_idx is None else len(val_idx)
+    ratio = train_table.group_ratio.numpy()
+    logs = [[] for _ in range(R)]
+    rec = lambda r, **k: logs[r].append(k)
+    streams = ReplicaStreams([s for _, s in replicas])
+
+    def new_clip():
+        return adapter.CustomCLIP(adapter.Adapter(D, opt.adapter_feat_dim), opt.text_embedding_dir, opt.text_spurious_embedding_dir,
+                                  opt.text_group_embedding_dir, temperature=opt.zs_temperature)
+    mods = [streams.run(r, new_clip) for r in range(R)]
+    for r in range(R):
+        rec(r, kind="init", state={k: v.clone() for k, v in mods[r].adapter.state_dict().items()})
+    sweep = adapter.SweepAdapters.from_modules(mods, dev)
+    lr1 = [_Lr(o.learning_rate) for o in opts]
+    lr2 = None
+    best_acc, best_epoch = [0] * R, [0] * R
+    train_accs, val_accs, test_accs = [[] for _ in range(R)], [[] for _ in range(R)], [[] for _ in range(R)]
+    bs_eval = max(opt.batch_size_reg if two_stage else opt.batch_size, 4096)
+    efl = getattr(opt, "epochs_feature_learning", None) if two_stage else None
+    for epoch in range(1, opt.epochs + 1):
+        for r in range(R):
+            O.adjust_learning_rate(opts[r], lr1[r], epoch)
+        balanced = None
+        if two_stage and opt.balance_val:
+            balanced = [streams.run(r, adapter.balance_val_indices, val_table.group_array[reg_idx], val_table.n_groups, opt.batch_size_reg)
+                        for r in range(R)]
+        stage2 = two_stage and epoch > efl
+        if not stage2:
+            def lrs(i, n, e=epoch):
+                for r in range(R):
+                    O.warmup_learning_rate(opts[r], e, i, n, lr1[r])
+                return [l.lr for l in lr1]
+            n_train = len(train_table)
+            c, ls, orders = _sweep_train_pass(streams, sweep, train_table, lambda r: dataloader_shuffle_order(n_train), opt.batch_size,
+                                              opt.train_target, False, lrs, opt.momentum, opt.weight_decay)
+            kind, extra, n_rows = "train1", {}, n_train
+        else:
+            if epoch == efl + 1:
+                if opt.continue_from_best:
+                    sweep.restore([True] * R)
+                if opt.add_adapter:
+                    fresh = [streams.run(r, adapter.Adapter, D, opt.adapter_feat_dim) for r in range(R)]
+                    for r in range(R):
+                        rec(r, kind="init", state={k: v.clone() for k, v in fresh[r].state_dict().items()})
+                    sweep.add_adapters(fresh, opt.init_near_identity)
+                else:
+                    sweep.reset_optimizer()
+                lr2 = [_Lr(o.learning_rate_reg) for o in opts]
+            for r in range(R):
+                O.adjust_learning_rate_reg(opts[r], lr2[r], epoch)
+            if opt.tl_method == "adapter_reg_seq_alter":
+                use_group = (epoch % 2) == 0
+            else:
+                use_group = not opt.use_cls_prompt_in_reg
+
+            def lrs(i, n, e=epoch):
+                for r in range(R):
+                    O.warmup_learning_rate_reg(opts[r], e - efl, i, n, lr2[r])
+                return [l.lr for l in lr2]
+            if balanced is not None:
+                bs = balanced[0][1]
+
+                def order(r):
+                    torch.empty((), dtype=torch.int64).random_()             # the un-shuffled loader's base-seed draw
+                    return torch.as_tensor(np.asarray(reg_idx[balanced[r][0]]), dtype=torch.int64)
+            else:
+                bs = opt.batch_size_reg
+
+                def order(r):
+                    return torch.as_tensor(np.asarray(reg_idx), dtype=torch.int64)[dataloader_shuffle_order(len(reg_idx))]
+            c, ls, orders = _sweep_train_pass(streams, sweep, val_table, order, bs, opt.train_target, use_group, lrs, opt.momentum,
+                                              opt.weight_decay)
+            kind, extra, n_rows = "train2", {"use_group": use_group}, len(orders[0])
+        for r in range(R):
+            total = int(c[r][:, 0].sum())
+            res = _results(c[r], train_table.n_places)
+            gacc = {k: np.round(res[k], 4) for k in NEW_ORDER_FOR_PRINT[1:]}
+            rec(r, kind=kind, epoch=epoch, loss=float(ls[r]) / n_rows, acc=int(c[r][:, 1].sum()) / total, group_acc=gacc, counts=c[r],
+                order=orders[r], **extra)
+            train_accs[r].append(gacc)
+        vc, vl = _sweep_validate(streams, sweep, val_table, bs_eval, opt.train_target, val_idx_dev, n_val)
+        better = [False] * R
+        for r in range(R):
+            vloss, vacc, vg = _eval_results(val_table, vc[r], float(vl[r]), n_val, ratio)
+            rec(r, kind="validate", epoch=epoch, split="val", loss=vloss, acc=vacc, group_acc=vg, counts=vc[r])
+            val_accs[r].append(vg)
+            if vg["worst_acc"] > best_acc[r]:
+                best_acc[r], best_epoch[r], better[r] = vg["worst_acc"], epoch, True
+        sweep.snapshot(better)
+        tc, tl = _sweep_validate(streams, sweep, test_table, bs_eval, "class", None, len(test_table))
+        for r in range(R):
+            tloss, tacc, tg = _eval_results(test_table, tc[r], float(tl[r]), len(test_table), ratio)
+            rec(r, kind="validate", epoch=epoch, split="test", loss=tloss, acc=tacc, group_acc=tg, counts=tc[r])
+            test_accs[r].append(tg)
+    if not all(sweep.has_best):
+        raise RuntimeError("train_sweep: a replica never had a worst-group accuracy above 0, so it has no best model")
+    # zero-shot scores of the best models: both kinds may occur in one sweep (a best epoch before / after the adapters were added)
+    zs, zss = [None] * R, [None] * R
+    for _ in range(2):                                                        # two validate passes: every replica's stream advances twice
+        for r in range(R):
+            streams.run(r, lambda: torch.empty((), dtype=torch.int64).random_())
+    for kind in (False, True):
+        rs = [r for r in range(R) if sweep.best_has_old[r] == kind]
+        if not rs:
+            continue
+        whole = len(rs) == R
+        sub = sweep if whole else sweep.subset(rs, best=True)
+        for spurious, dst in ((False, zs), (True, zss)):
+            cc, ll = _sweep_validate(streams, sub, test_table, bs_eval, "spurious" if spurious else "class", None, len(test_table),
+                                     spurious=spurious, best=whole, draw=False)
+            for k, r in enumerate(rs):
+                dst[r] = _eval_results(test_table, cc[k], float(ll[k]), len(test_table), ratio) + (cc[k],)
+    out = []
+    for r in range(R):
+        rec(r, kind="validate_zs", target="class", loss=zs[r][0], acc=zs[r][1], group_acc=zs[r][2], counts=zs[r][3])
+        rec(r, kind="validate_zs", target="spurious", loss=zss[r][0], acc=zss[r][1], group_acc=zss[r][2], counts=zss[r][3])
+        # the best model as an ordinary module is only built for a caller who asked for the records (a host-side copy per replica)
+        rec(r, kind="final", best_epoch=best_epoch[r], best_model=sweep.replica(r, best=True) if log is not None else None)
+        e = best_epoch[r] - 1
+        out.append(((train_accs[r][e], val_accs[r][e], test_accs[r][e]), (zs[r][2], zss[r][2])))
+    if log is not None:
+        log.extend(logs)
+    return out
+
+
+def sweep_frame(results):
+    """The table of the reference's sweep drivers (final_main_iteration_wb.py:1136-1161, :1193) from the per-seed results of
+    train_sweep / train_all_epochs, in run order: per block the per-seed rows 1 .. n, `<block>_mean`, `<block>_std`; blocks in the
+    order test, spurious zero-shot, train, val, target zero-shot; rounded to 4 places.  Built with the reference's own pandas
+    statements, so it has its property that a block's std row is taken after the mean row was appended (the sample standard deviation
+    of the n values and their mean)."""
+    import pandas as pd
+
+    def block(dicts, tag):
+        df = pd.concat([pd.DataFrame(d, index=[i + 1]) for i, d in enumerate(dicts)])
+        df = pd.concat([df, pd.DataFrame(df.mean().to_dict(), index=[tag + "_mean"])])
+        return pd.concat([df, pd.DataFrame(df.std().to_dict(), index=[tag + "_std"])])
+    tr = block([r[0][0] for r in results], "tr")
+    val = block([r[0][1] for r in results], "val")
+    test = block([r[0][2] for r in results], "test")
+    zt = block([r[1][0] for r in results], "zs_tg")
+    zsp = block([r[1][1] for r in results], "zs_spu")
+    return pd.concat([test, zsp, tr, val, zt]).round(4)
+
+
+def sweep_result_name(opt):
+    """file name (without .csv) of the reference's sweep drivers (final_main_iteration_wb.py:1166-1191)"""
+    name = f"ds_{opt.dataset}_tl_{opt.tl_method}_bs_{opt.batch_size}_lr_{opt.learning_rate}"
+    if "reg" in opt.tl_method:
+        name += f"_lrr{opt.learning_rate_reg}_bsr{opt.batch_size_reg}"
+        if opt.balance_val:
+            name += "_balval"
+        if opt.tl_method != "adapter_reg_seq_alter":
+            name += "_CP" if opt.use_cls_prompt_in_reg else "_GP"
+        if opt.add_adapter:
+            name += "_MA" + ("+ni" if opt.init_near_identity else "+rn")
+        if opt.continue_from_best and "seq" in opt.tl_method:
+            name += "_cont"
+    if getattr(opt, "resample_ce", False):
+        name += "_rs"
+    return name
+
+
+def run_sweep(opt, tables, out_dir):
+    """The two sweep drivers of the reference on device-resident tables (`tables` = (train, val, test) EmbeddingTables).
+    With opt.lr_list / opt.bs_list / opt.bsr_list (comma-separated strings or sequences; final_main_iteration_ca.py:1167-1186) the
+    (batch size, reg batch size) groups run one after the other and every group trains all lr_list x opt.random_seeds replicas as
+    one batched sweep; without them it is final_main_iteration_wb.py: opt.random_seeds at opt's own settings.  Writes one CSV per
+    (lr, bs, bsr) under `out_dir`, named like the reference's, and returns {file path: frame}."""
+    import os
+    from copy import copy
+
+    def as_list(v, conv):
+        if v is None:
+            return None
+        return [conv(x) for x in (v.split(",") if isinstance(v, str) else v)]
+    seeds = list(opt.random_seeds)[:getattr(opt, "num_iter", len(opt.random_seeds))]
+    lrs = as_list(getattr(opt, "lr_list", None), float)
+    bss = as_list(getattr(opt, "bs_list", None), int) or [opt.batch_size]
+    bsrs = as_list(getattr(opt, "bsr_list", None), int) or [opt.batch_size_reg]
+    if lrs is not None and opt.tl_method == "adapter":
+        bsrs = [128]
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for bs in bss:
+        for bsr in bsrs:
+            o = copy(opt)
+            o.batch_size, o.batch_size_reg = bs, bsr
+            results = train_sweep(o, *tables, seeds, learning_rates=lrs)
+            for k, lr in enumerate(lrs if lrs is not None else [None]):
+                if lr is not None:
+                    o.learning_rate, o.learning_rate_reg = lr, lr * getattr(opt, "lr_multiple", 1.0)
+                frame = sweep_frame(results[k * len(seeds):(k + 1) * len(seeds)])
+                path = os.path.join(out_dir, sweep_result_name(o) + ".csv")
+                frame.to_csv(path)
+                written[path] = frame
+    return written

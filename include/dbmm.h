@@ -541,6 +541,35 @@ int dbmm_adapter_train_step(const float* x, const int64_t* labels, float* w1, fl
                             int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* Replica-batched adapter step (csrc/adapter_sweep.hip): R <= 16 independent runs of one sweep group take one training step in
+ * the launches of ONE dbmm_adapter_train_step (8, or 11 with a frozen old adapter), the replica being a grid dimension.  Fast shape
+ * only (H == 128, D % 128 == 0; else DBMM_E_UNSUPPORTED); replica r's results are the bits dbmm_adapter_train_step gives for r alone.
+ *   table [n_rows][D], labels / groups [n_rows]: one shared embedding table; idx [idx_R][idx_B] (= [R][B], else DBMM_E_SHAPE): replica
+ *     r trains on rows idx[r][:], read in place (indices are clamped into the table; repeats are legal)
+ *   params: 9 device pointers to stacked [R, ...] tensors (w1, b1, gamma, beta, running_mean, running_var, nbt int64 [R], w2, b2);
+ *     bufs: the 6 stacked momentum buffers (w1, b1, gamma, beta, w2, b2); old: 9 pointers of the frozen adapters, or NULL.  The
+ *     three arrays and lr [R] are HOST arrays, read during the call (the learning rates travel as kernel arguments)
+ *   logits [R][B][C], loss_rows [R][B], loss_mean [R]: outputs.  counted != 0: counts int64 [R][G][2] += (n, correct) per group and
+ *     loss_sum double [R] += (double)loss_mean * B, by the step's own launches.  B < 2: DBMM_E_SHAPE (train-mode BatchNorm1d). */
+size_t dbmm_workspace_bytes_adapter_sweep_step(int64_t R, int64_t B, int64_t D, int64_t H, int with_old);
+int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B,
+                            const int64_t* labels, const int64_t* groups, void* const* params, float* const* bufs,
+                            void* const* old, float ebd_weight, const float* tn, float temperature, const float* lr,
+                            float momentum, float weight_decay, int first_step, float* logits, float* loss_rows,
+                            float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted, int64_t R,
+                            int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
+/* Replica-batched evaluation forward: eval-mode adapters (running statistics; old + new blend when `old`), cosine logits, per-row
+ * CE, group counters and the float64 loss sum (loss_sum[r] += sum_b (double)loss_rows[r][b], fixed order) of R replicas over the
+ * SAME B rows: idx [B] rows of the table, or idx == NULL: rows row0 .. row0 + B - 1.  5 launches (8 with `old`). */
+size_t dbmm_workspace_bytes_adapter_sweep_eval(int64_t R, int64_t B, int64_t D, int64_t H, int with_old);
+int dbmm_adapter_sweep_eval(const float* table, int64_t n_rows, const int64_t* idx, int64_t row0, const int64_t* labels,
+                            const int64_t* groups, void* const* params, void* const* old, float ebd_weight,
+                            const float* tn, float temperature, float* logits, float* loss_rows, int64_t* counts,
+                            double* loss_sum, int64_t G, int64_t R, int64_t B, int64_t D, int64_t H, int64_t C,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* One training step of the linear probe (final_main.py:43-49 LinearClassifier, trained at :426-496) in one call:
  * logits = x W^T + b, per-row CE and its mean, dlogits = (softmax - onehot) / B, dW = dlogits^T x, db = colsum dlogits, then
  * dbmm_sgd_momentum's update of w, b and their momentum buffers m_w, m_b in place.  x [B][D], labels int64 [B] in [0, C),
