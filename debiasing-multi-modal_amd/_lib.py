@@ -41,7 +41,8 @@ KERNEL_SOURCES = (
     ("stem_s2", ("resnet_ops.hip", "common.h")), ("attnpool", ("resnet_ops.hip", "common.h")),
     ("adapter_step", ("adapter_step.hip", "adapter_bodies.inc", "common.h")),
     ("sweep_", ("adapter_sweep.hip", "adapter_bodies.inc", "common.h")),
-    ("linear_", ("linear_step.hip", "common.h")),
+    ("linear_sweep_", ("linear_sweep.hip", "linear_bodies.inc", "common.h")),
+    ("linear_", ("linear_step.hip", "linear_bodies.inc", "common.h")),
 )
 
 
@@ -179,6 +180,10 @@ _SIGS = {
     "dbmm_linear_train_step": [_P] * 6 + [_F, _F, _F, _I, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_linear_ce_fwd": [_L],
     "dbmm_linear_ce_fwd": [_P] * 7 + [_L, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_linear_sweep_step": [_L, _L, _L, _L],
+    "dbmm_linear_sweep_step": [_P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _I, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_linear_sweep_eval": [_L, _L],
+    "dbmm_linear_sweep_eval": [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_preprocess": [_L, _L],
     "dbmm_resize_crop_normalize_u8": [_P, _L, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _Z, _P],
     "dbmm_resize_crop_normalize_u8_batch": [_P, _L, _L, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _Z, _P],
@@ -200,6 +205,8 @@ _RESTYPES = {
     "dbmm_workspace_bytes_adapter_sweep_step": c_size_t,
     "dbmm_workspace_bytes_adapter_sweep_eval": c_size_t,
     "dbmm_workspace_bytes_linear_ce_fwd": c_size_t,
+    "dbmm_workspace_bytes_linear_sweep_step": c_size_t,
+    "dbmm_workspace_bytes_linear_sweep_eval": c_size_t,
 }
 
 EXPORTS = tuple(_SIGS)

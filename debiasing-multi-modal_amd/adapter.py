@@ -392,7 +392,7 @@ class MultipleAdapter(CustomCLIP):
 
 
 # ---------------------------------------------------------------------------------------
-# stacked adapters of a seed sweep (trainer.train_sweep, csrc/adapter_sweep.hip)
+# stacked adapters / linear probes of a seed sweep (trainer.train_sweep, csrc/adapter_sweep.hip, csrc/linear_sweep.hip)
 # ---------------------------------------------------------------------------------------
 
 def _adapter_tensors(ad):
@@ -564,6 +564,77 @@ class SweepAdapters:
             raise ValueError("SweepAdapters.evaluate(best=True): best models of both kinds; evaluate subset()s")
         return ops.adapter_sweep_eval(table, idx, labels, groups, self._call_args(best), self.ebd_weight, self.text(which), self.temperature,
                                       counts, loss_sum, row0, n)
+
+
+class SweepLinear:
+    """R LinearClassifiers of one sweep group as stacked contiguous tensors: `w` [R, C, D], `b` [R, C], and their momentum buffers
+    `mom_w`, `mom_b` (one SGD optimiser per replica for the whole run).  One `step` trains all replicas in the launch of one
+    single-run step (csrc/linear_sweep.hip), `evaluate` scores them on the same rows; `replica(r)` gives replica r back as an
+    ordinary LinearClassifier (the reference's state-dict keys fc.weight / fc.bias).  A second stacked pair holds each replica's
+    best model: `snapshot(mask)` copies the masked replicas into it (best-model selection)."""
+
+    def __init__(self, w, b, device):
+        self.w, self.b = w, b
+        self.R, self.C, self.D = w.shape
+        self.device = torch.device(device)
+        self.mom_w, self.mom_b = torch.zeros_like(w), torch.zeros_like(b)
+        self.first_step = True
+        self.best_w = self.best_b = None
+        self.has_best = [False] * self.R
+
+    @classmethod
+    def from_modules(cls, modules, device="cuda"):
+        """from R LinearClassifier modules of one shape"""
+        if any(not isinstance(m, LinearClassifier) for m in modules):
+            raise ValueError("SweepLinear.from_modules: LinearClassifier modules expected")
+        if len({tuple(m.fc.weight.shape) for m in modules}) != 1:
+            raise ValueError("SweepLinear.from_modules: all replicas must be of one shape")
+        w = torch.stack([m.fc.weight.detach() for m in modules]).to(device).contiguous()
+        b = torch.stack([m.fc.bias.detach() for m in modules]).to(device).contiguous()
+        return cls(w, b, device)
+
+    def snapshot(self, mask):
+        """best[r] = deepcopy(model r) for the replicas with mask[r]"""
+        rs = [r for r in range(self.R) if mask[r]]
+        if not rs:
+            return
+        if self.best_w is None:
+            self.best_w, self.best_b = torch.zeros_like(self.w), torch.zeros_like(self.b)
+        ix = torch.as_tensor(rs, device=self.device)
+        self.best_w[ix] = self.w[ix]
+        self.best_b[ix] = self.b[ix]
+        for r in rs:
+            self.has_best[r] = True
+
+    def replica(self, r, best=False):
+        """replica r (its best model when `best`; None if it has none) as an ordinary module on the sweep's device, in eval mode"""
+        if best and not self.has_best[r]:
+            return None
+        w, b = (self.best_w, self.best_b) if best else (self.w, self.b)
+        prev = torch.get_rng_state()                 # nn.Linear draws its initial weights: the caller's random stream is left alone
+        try:
+            m = LinearClassifier(self.D, self.C)
+        finally:
+            torch.set_rng_state(prev)
+        with torch.no_grad():
+            m.fc.weight.copy_(w[r])
+            m.fc.bias.copy_(b[r])
+        return m.to(self.device).eval()
+
+    def step(self, table, idx, labels, groups, lrs, momentum, weight_decay, counts, loss_sum, counted=True):
+        """one training step of every replica on rows idx[r] of `table`.  Returns (mean CE [R], logits [R, B, C], per-row CE [R, B])"""
+        out = ops.linear_sweep_step(table, idx, labels, groups, self.w, self.b, self.mom_w, self.mom_b, lrs, momentum, weight_decay,
+                                    self.first_step, counts, loss_sum, counted)
+        self.first_step = False
+        return out
+
+    def evaluate(self, table, idx, labels, groups, counts, loss_sum, row0=0, n=None, best=False):
+        """eval forward of every replica (of the best models when `best`) over the same rows.  Returns (logits [R, B, C], per-row
+        CE [R, B])"""
+        if best and not all(self.has_best):
+            raise ValueError("SweepLinear.evaluate(best=True): a replica has no best model yet")
+        w, b = (self.best_w, self.best_b) if best else (self.w, self.b)
+        return ops.linear_sweep_eval(table, idx, labels, groups, w, b, counts, loss_sum, row0, n)
 
 
 # ---------------------------------------------------------------------------------------

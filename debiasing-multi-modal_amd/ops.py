@@ -984,6 +984,91 @@ def linear_ce_fwd(x, labels, w, b):
     return loss[B], logits, loss[:B]
 
 
+def _linear_sweep_operands(table, labels, groups, w, b, extra=()):
+    """the stacked operands of the replica-batched linear-probe calls: table [N, D], labels / groups int64 [N], w [R, C, D], b [R, C]
+    (and momentum buffers of the same shapes), all contiguous on one device.  Returns (R, C, D)."""
+    require_cuda(table, labels, groups, w, b, *extra)
+    if table.dim() != 2 or w.dim() != 3 or b.dim() != 2:
+        raise _lib.DbmmError(f"linear sweep: table [N, D], w [R, C, D], b [R, C] expected; got {tuple(table.shape)}, {tuple(w.shape)}, "
+                             f"{tuple(b.shape)}")
+    R, C, D = w.shape
+    for t in (table, w, b) + tuple(extra):
+        _f32c(t)
+    if table.shape[1] != D or tuple(b.shape) != (R, C):
+        raise _lib.DbmmError(f"linear sweep: table {tuple(table.shape)} and b {tuple(b.shape)} against w {tuple(w.shape)}")
+    if not (1 <= R <= 16) or not (1 <= C <= 8) or D % 4 or not (4 <= D <= 1024):
+        raise _lib.DbmmError(f"linear sweep kernels serve 1..16 replicas, C <= 8 classes, D % 4 == 0 and D <= 1024; got R={R} C={C} D={D}")
+    for nm, t in (("labels", labels), ("groups", groups)):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise _lib.DbmmError(f"linear sweep: {nm} must be a contiguous int64 tensor")
+        _sized(f"linear sweep {nm}", t, table.shape[0])
+    if any(t.device != table.device for t in (labels, groups, w, b) + tuple(extra)):
+        raise _lib.DbmmError("linear sweep: all operands must be on one device")
+    return R, C, D
+
+
+def linear_sweep_step(table, idx, labels, groups, w, b, m_w, m_b, lrs, momentum, weight_decay, first_step, counts, loss_sum, counted=True):
+    """one training step of R linear probes in the launches of one (dbmm_linear_sweep_step): replica r trains on rows idx[r] of
+    `table` ([N, D] fp32; labels / groups int64 [N]); w / m_w [R, C, D] and b / m_b [R, C] are updated in place; `lrs` R host floats;
+    counts int64 [R, G, 2] and loss_sum float64 [R] are accumulated in place when `counted`.  Returns (mean CE [R], logits
+    [R, B, C], per-row CE [R, B])."""
+    R, C, D = _linear_sweep_operands(table, labels, groups, w, b, (m_w, m_b))
+    if m_w.shape != w.shape or m_b.shape != b.shape:
+        raise _lib.DbmmError(f"linear sweep: momentum buffers {tuple(m_w.shape)}, {tuple(m_b.shape)} for w {tuple(w.shape)}, b {tuple(b.shape)}")
+    require_cuda(idx)
+    if idx.dtype != torch.int64 or not idx.is_contiguous() or idx.dim() != 2 or idx.shape[0] != R or idx.shape[1] < 1:
+        raise _lib.DbmmError("linear sweep step: idx must be a contiguous int64 [R, B] tensor")
+    if idx.device != table.device:
+        raise _lib.DbmmError(f"linear sweep step: idx is on {idx.device}, the table on {table.device}")
+    G = _sweep_metrics(counts, loss_sum, R)
+    if len(lrs) != R:
+        raise _lib.DbmmError(f"linear sweep step: {len(lrs)} learning rates for {R} replicas")
+    B = idx.shape[1]
+    dev = table.device
+    L = _lib.lib()
+    ws = _sweep_workspace(dev, L.dbmm_workspace_bytes_linear_sweep_step(R, B, D, C))
+    logits = _empty((R, B, C), device=dev, dtype=torch.float32)
+    loss = _empty((R * (B + 1),), device=dev, dtype=torch.float32)      # the R x B per-row losses, then the R means: one allocation
+    LR = (ctypes.c_float * R)(*[float(v) for v in lrs])
+    rc = L.dbmm_linear_sweep_step(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(),
+                                  w.data_ptr(), b.data_ptr(), m_w.data_ptr(), m_b.data_ptr(), LR, float(momentum), float(weight_decay),
+                                  int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * R * B, counts.data_ptr(),
+                                  loss_sum.data_ptr(), G, int(counted), R, B, D, C, ws.data_ptr(), ws.numel() * 4, stream())
+    if rc:
+        check(rc, "linear_sweep_step")
+    return loss[R * B:], logits, loss[:R * B].view(R, B)
+
+
+def linear_sweep_eval(table, idx, labels, groups, w, b, counts, loss_sum, row0=0, n=None):
+    """the eval forward of R linear probes over the same rows (dbmm_linear_sweep_eval): rows idx (int64 [B]) of `table`, or idx
+    None: rows row0 .. row0 + n - 1.  counts int64 [R, G, 2] and loss_sum float64 [R] are accumulated in place.  Returns (logits
+    [R, B, C], per-row CE [R, B])."""
+    R, C, D = _linear_sweep_operands(table, labels, groups, w, b)
+    if idx is not None:
+        require_cuda(idx)
+        if idx.dtype != torch.int64 or not idx.is_contiguous() or idx.dim() != 1 or idx.shape[0] < 1:
+            raise _lib.DbmmError("linear sweep eval: idx must be a contiguous int64 [B] tensor")
+        if idx.device != table.device:
+            raise _lib.DbmmError(f"linear sweep eval: idx is on {idx.device}, the table on {table.device}")
+        B = idx.shape[0]
+    else:
+        B = table.shape[0] - row0 if n is None else n
+        if row0 < 0 or B < 1 or row0 + B > table.shape[0]:
+            raise _lib.DbmmError(f"linear sweep eval: rows row0={row0} .. row0 + n - 1 (n={B}) are not inside the table of {table.shape[0]} rows")
+    G = _sweep_metrics(counts, loss_sum, R)
+    dev = table.device
+    L = _lib.lib()
+    ws = _sweep_workspace(dev, L.dbmm_workspace_bytes_linear_sweep_eval(R, B))
+    logits = _empty((R, B, C), device=dev, dtype=torch.float32)
+    rows = _empty((R, B), device=dev, dtype=torch.float32)
+    rc = L.dbmm_linear_sweep_eval(table.data_ptr(), table.shape[0], ptr(idx), row0, labels.data_ptr(), groups.data_ptr(), w.data_ptr(),
+                                  b.data_ptr(), logits.data_ptr(), rows.data_ptr(), counts.data_ptr(), loss_sum.data_ptr(), G, R, B, D, C,
+                                  ws.data_ptr(), ws.numel() * 4, stream())
+    if rc:
+        check(rc, "linear_sweep_eval")
+    return logits, rows
+
+
 def gather_rows(table, idx):
     """out[i] = table[idx[i]] for a device-resident [N, D] fp32 table and int64 indices."""
     require_cuda(table, idx)

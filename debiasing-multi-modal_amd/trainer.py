@@ -474,11 +474,15 @@ def _eval_results(table, c, loss_sum, n, ratio):
     return loss_sum / n, int(c[:, 1].sum()) / int(c[:, 0].sum()), group_acc
 
 
-def _sweep_train_pass(streams, sweep, table, orders_fn, batch_size, target, use_group, lr_fn, momentum, weight_decay):
+def _sweep_train_pass(streams, sweep, table, orders_fn, batch_size, target, use_group, lr_fn, momentum, weight_decay, counted=True, acc=None,
+                      sync=True):
     """one loader pass of every replica: `orders_fn(r)` draws replica r's row order (under its own streams), all orders go to the
-    device in ONE upload, then n_steps batched steps; lr_fn(step, n_steps) -> the R learning rates.  Returns (counts [R, G, 2] numpy,
-    loss sums [R] numpy, orders) after the pass's one host sync."""
+    device in ONE upload, then n_steps batched steps; lr_fn(step, n_steps) -> the R learning rates.  `sweep`: SweepAdapters (scored on
+    the group prompts when `use_group`, else the class prompts) or SweepLinear.  `counted`: the pass adds to the loss sums and group
+    counters; `acc` = (counts, loss sums) device tensors of an epoch made of several passes (fresh ones if None).  Returns (counts
+    [R, G, 2] numpy, loss sums [R] numpy, orders, acc) after the pass's one host sync; the two arrays are None without `sync`."""
     R, dev = sweep.R, table.device
+    linear = isinstance(sweep, adapter.SweepLinear)
     orders = [streams.run(r, orders_fn, r) for r in range(R)]
     n = len(orders[0])
     if any(len(o) != n for o in orders):
@@ -490,16 +494,21 @@ def _sweep_train_pass(streams, sweep, table, orders_fn, batch_size, target, use_
         full = idx[:, :n_full * batch_size].view(R, n_full, batch_size).permute(1, 0, 2).contiguous()       # [n_steps, R, B]
         steps += [full[i] for i in range(n_full)]
     if rem:
-        if rem < 2:
+        if rem < 2 and not linear:
             raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d)")
         steps.append(idx[:, n_full * batch_size:].contiguous())
-    counts = torch.zeros((R, table.n_groups, 2), dtype=torch.int64, device=dev)
-    loss_sum = torch.zeros((R,), dtype=torch.float64, device=dev)
+    if acc is None:
+        acc = (torch.zeros((R, table.n_groups, 2), dtype=torch.int64, device=dev), torch.zeros((R,), dtype=torch.float64, device=dev))
+    counts, loss_sum = acc
     labels = table.targets_group if use_group else table.labels(target)
-    which = "group" if use_group else "class"
+    prompts = () if linear else ("group" if use_group else "class",)
     for i, b in enumerate(steps):
-        sweep.step(table.embeddings, b, labels, table.targets_group, which, lr_fn(i, len(steps)), momentum, weight_decay, counts, loss_sum)
-    return counts.cpu().numpy(), loss_sum.cpu().numpy(), [o.numpy() for o in orders]
+        sweep.step(table.embeddings, b, labels, table.targets_group, *prompts, lr_fn(i, len(steps)), momentum, weight_decay, counts, loss_sum,
+                   counted=counted)
+    orders = [o.numpy() for o in orders]
+    if not sync:
+        return None, None, orders, acc
+    return counts.cpu().numpy(), loss_sum.cpu().numpy(), orders, acc
 
 
 def _sweep_validate(streams, sweep, table, batch_size, target, indices_dev, n, spurious=False, best=False, draw=True):
@@ -512,13 +521,13 @@ def _sweep_validate(streams, sweep, table, batch_size, target, indices_dev, n, s
     counts = torch.zeros((R, table.n_groups, 2), dtype=torch.int64, device=dev)
     loss_sum = torch.zeros((R,), dtype=torch.float64, device=dev)
     labels = table.labels(target)
-    which = "spurious" if spurious else "class"
+    prompts = () if isinstance(sweep, adapter.SweepLinear) else ("spurious" if spurious else "class",)
     for i in range(0, n, batch_size):
         m = min(batch_size, n - i)
         if indices_dev is not None:
-            sweep.evaluate(table.embeddings, indices_dev[i:i + m], labels, table.targets_group, which, counts, loss_sum, best=best)
+            sweep.evaluate(table.embeddings, indices_dev[i:i + m], labels, table.targets_group, *prompts, counts, loss_sum, best=best)
         else:
-            sweep.evaluate(table.embeddings, None, labels, table.targets_group, which, counts, loss_sum, row0=i, n=m, best=best)
+            sweep.evaluate(table.embeddings, None, labels, table.targets_group, *prompts, counts, loss_sum, row0=i, n=m, best=best)
     return counts.cpu().numpy(), loss_sum.cpu().numpy()
 
 
@@ -527,21 +536,28 @@ def train_sweep(opt, train_table, val_table, test_table, seeds, learning_rates=N
     after `optim.set_seed(seed)`.  Replicas are (learning rate, seed) pairs, learning-rate-major; with `learning_rates` given,
     replica (lr, seed) runs with learning_rate = lr and learning_rate_reg = lr * opt.lr_multiple, like final_main_iteration_ca.py.
 
-    Batched path -- tl_method `adapter`, `adapter_reg_seq`, `adapter_reg_seq_alter`, with or without --add_adapter, --balance_val,
-    --continue_from_best, --init_near_identity (the main branch of train_all_epochs), on the adapter's fast shape (hidden width 128,
-    D % 128 == 0) and at least two replicas: all replicas advance in lock-step, every training step and every evaluation batch is one
-    replica-batched call (adapter.SweepAdapters; up to 16 replicas per group of launches, more are split into groups), each pass
-    uploads its row orders once and synchronises with the host once, best-model selection runs per replica on the host.
-    Sequential path -- `adapter_reg`, `linear_probing`, other shapes and a single replica: replica by replica through
-    train_all_epochs on the same tables.  `contrastive_adapter` raises like train_all_epochs.
+    Batched path -- at least two replicas and
+      * tl_method `adapter`, `adapter_reg_seq`, `adapter_reg_seq_alter`, with or without --add_adapter, --balance_val,
+        --continue_from_best, --init_near_identity (the main branch of train_all_epochs), and `adapter_reg` (with or without
+        --balance_val, --use_cls_prompt_in_reg), on the adapter's fast shape (hidden width 128, D % 128 == 0): adapter.SweepAdapters;
+      * tl_method `linear_probing` with n_cls <= 8, D % 4 == 0 and D <= 1024: adapter.SweepLinear.
+    All replicas advance in lock-step, every training step and every evaluation batch is one replica-batched call (up to 16 replicas
+    per group of launches, more are split into groups), each pass uploads its row orders once and synchronises with the host once,
+    best-model selection runs per replica on the host.
+    Sequential path -- other shapes and a single replica: replica by replica through train_all_epochs on the same tables.
+    `contrastive_adapter` raises like train_all_epochs.
 
     Each replica keeps its own pair of global random streams (ReplicaStreams), so its initial weights, batch orders and balanced
     subsets are those of its own sequential run.  `log` (a list) receives one list of records per replica (train_all_epochs' records)."""
     from . import optim as O
     replicas = _sweep_replicas(opt, list(seeds), learning_rates)
     D = train_table.embeddings.shape[1]
-    batched = (opt.tl_method in ("adapter", "adapter_reg_seq", "adapter_reg_seq_alter") and len(replicas) >= 2
-               and opt.adapter_feat_dim == 128 and D % 128 == 0 and bool(ops.get_option("adapter_step_fused")))
+    if opt.tl_method == "linear_probing":
+        group, batched = _train_linear_sweep_group, len(replicas) >= 2 and 1 <= opt.n_cls <= 8 and D % 4 == 0 and D <= 1024
+    else:
+        group = _train_adapter_reg_sweep_group if opt.tl_method == "adapter_reg" else _train_sweep_group
+        batched = (opt.tl_method in ("adapter", "adapter_reg", "adapter_reg_seq", "adapter_reg_seq_alter") and len(replicas) >= 2
+                   and opt.adapter_feat_dim == 128 and D % 128 == 0 and bool(ops.get_option("adapter_step_fused")))
     if opt.tl_method not in ("adapter", "adapter_reg_seq", "adapter_reg_seq_alter", "adapter_reg", "linear_probing"):
         raise ValueError(f"train_sweep covers linear_probing and the adapter methods, not tl_method={opt.tl_method!r}")
     if not batched:
@@ -555,7 +571,7 @@ def train_sweep(opt, train_table, val_table, test_table, seeds, learning_rates=N
         return out
     out = []
     for i in range(0, len(replicas), 16):
-        out += _train_sweep_group(replicas[i:i + 16], train_table, val_table, test_table, log)
+        out += group(replicas[i:i + 16], train_table, val_table, test_table, log)
     return out
 
 
@@ -606,8 +622,8 @@ def _train_sweep_group(replicas, train_table, val_table, test_table, log):
                     O.warmup_learning_rate(opts[r], e, i, n, lr1[r])
                 return [l.lr for l in lr1]
             n_train = len(train_table)
-            c, ls, orders = _sweep_train_pass(streams, sweep, train_table, lambda r: dataloader_shuffle_order(n_train), opt.batch_size,
-                                              opt.train_target, False, lrs, opt.momentum, opt.weight_decay)
+            c, ls, orders, _ = _sweep_train_pass(streams, sweep, train_table, lambda r: dataloader_shuffle_order(n_train), opt.batch_size,
+                                                 opt.train_target, False, lrs, opt.momentum, opt.weight_decay)
             kind, extra, n_rows = "train1", {}, n_train
         else:
             if epoch == efl + 1:
@@ -643,8 +659,8 @@ def _train_sweep_group(replicas, train_table, val_table, test_table, log):
 
                 def order(r):
                     return torch.as_tensor(np.asarray(reg_idx), dtype=torch.int64)[dataloader_shuffle_order(len(reg_idx))]
-            c, ls, orders = _sweep_train_pass(streams, sweep, val_table, order, bs, opt.train_target, use_group, lrs, opt.momentum,
-                                              opt.weight_decay)
+            c, ls, orders, _ = _sweep_train_pass(streams, sweep, val_table, order, bs, opt.train_target, use_group, lrs, opt.momentum,
+                                                 opt.weight_decay)
             kind, extra, n_rows = "train2", {"use_group": use_group}, len(orders[0])
         for r in range(R):
             total = int(c[r][:, 0].sum())
@@ -696,6 +712,173 @@ def _train_sweep_group(replicas, train_table, val_table, test_table, log):
     if log is not None:
         log.extend(logs)
     return out
+
+
+def _sweep_finish(R, logs, log, best_epoch, best_model_fn, train_accs, val_accs, test_accs, zs, zss):
+    """the tail of a lock-step schedule: the zero-shot pair ((loss, acc, group acc, counts) per replica) and the final record of every
+    replica, and what train_all_epochs returns for each"""
+    out = []
+    for r in range(R):
+        logs[r].append(dict(kind="validate_zs", target="class", loss=zs[r][0], acc=zs[r][1], group_acc=zs[r][2], counts=zs[r][3]))
+        logs[r].append(dict(kind="validate_zs", target="spurious", loss=zss[r][0], acc=zss[r][1], group_acc=zss[r][2], counts=zss[r][3]))
+        # the best model as an ordinary module is only built for a caller who asked for the records (a host-side copy per replica)
+        logs[r].append(dict(kind="final", best_epoch=best_epoch[r], best_model=best_model_fn(r) if log is not None else None))
+        e = best_epoch[r] - 1
+        out.append(((train_accs[r][e], val_accs[r][e], test_accs[r][e]), (zs[r][2], zss[r][2])))
+    if log is not None:
+        log.extend(logs)
+    return out
+
+
+def _sweep_epoch_tail(streams, sweep, epoch, rec, val_table, test_table, bs_eval, target, val_idx_dev, n_val, ratio, best_acc, best_epoch,
+                      val_accs, test_accs):
+    """what every schedule does after an epoch's training: validate, strict `>` best-model selection per replica, test"""
+    R = sweep.R
+    vc, vl = _sweep_validate(streams, sweep, val_table, bs_eval, target, val_idx_dev, n_val)
+    better = [False] * R
+    for r in range(R):
+        vloss, vacc, vg = _eval_results(val_table, vc[r], float(vl[r]), n_val, ratio)
+        rec(r, kind="validate", epoch=epoch, split="val", loss=vloss, acc=vacc, group_acc=vg, counts=vc[r])
+        val_accs[r].append(vg)
+        if vg["worst_acc"] > best_acc[r]:
+            best_acc[r], best_epoch[r], better[r] = vg["worst_acc"], epoch, True
+    sweep.snapshot(better)
+    tc, tl = _sweep_validate(streams, sweep, test_table, bs_eval, "class", None, len(test_table))
+    for r in range(R):
+        tloss, tacc, tg = _eval_results(test_table, tc[r], float(tl[r]), len(test_table), ratio)
+        rec(r, kind="validate", epoch=epoch, split="test", loss=tloss, acc=tacc, group_acc=tg, counts=tc[r])
+        test_accs[r].append(tg)
+
+
+def _train_linear_sweep_group(replicas, train_table, val_table, test_table, log):
+    """_train_linear_probing for up to 16 replicas in lock-step: statement for statement the sequential schedule, every per-replica
+    host decision (initial weights, shuffle order, learning rate, best model) taken per replica"""
+    from . import optim as O
+    opts = [o for o, _ in replicas]
+    opt = opts[0]
+    R = len(replicas)
+    dev = train_table.device
+    D = train_table.embeddings.shape[1]
+    ratio = train_table.group_ratio.numpy()
+    logs = [[] for _ in range(R)]
+    rec = lambda r, **k: logs[r].append(k)
+    streams = ReplicaStreams([s for _, s in replicas])
+    mods = [streams.run(r, adapter.LinearClassifier, D, opt.n_cls) for r in range(R)]
+    for r in range(R):
+        rec(r, kind="init", state={k: v.clone() for k, v in mods[r].state_dict().items()})
+    sweep = adapter.SweepLinear.from_modules(mods, dev)
+    lr1 = [_Lr(o.learning_rate) for o in opts]
+    best_acc, best_epoch = [0] * R, [0] * R
+    train_accs, val_accs, test_accs = [[] for _ in range(R)], [[] for _ in range(R)], [[] for _ in range(R)]
+    bs_eval = max(opt.batch_size, 4096)
+    n_train = len(train_table)
+    for epoch in range(1, opt.epochs + 1):
+        for r in range(R):
+            O.adjust_learning_rate(opts[r], lr1[r], epoch)
+
+        def lrs(i, n, e=epoch):
+            for r in range(R):
+                O.warmup_learning_rate(opts[r], e, i, n, lr1[r])
+            return [l.lr for l in lr1]
+        c, ls, orders, _ = _sweep_train_pass(streams, sweep, train_table, lambda r: dataloader_shuffle_order(n_train), opt.batch_size,
+                                             opt.train_target, False, lrs, opt.momentum, opt.weight_decay)
+        for r in range(R):
+            res = _results(c[r], train_table.n_places)
+            gacc = {k: np.round(res[k], 4) for k in NEW_ORDER_FOR_PRINT[1:]}
+            rec(r, kind="train1", epoch=epoch, loss=float(ls[r]) / n_train, acc=int(c[r][:, 1].sum()) / int(c[r][:, 0].sum()), group_acc=gacc,
+                counts=c[r], order=orders[r])
+            train_accs[r].append(gacc)
+        _sweep_epoch_tail(streams, sweep, epoch, rec, val_table, test_table, bs_eval, opt.train_target, None, len(val_table), ratio, best_acc,
+                          best_epoch, val_accs, test_accs)
+    # a replica whose worst-group accuracy never rose above 0 has best_epoch 0 and no best model, like its sequential run
+    # validate_zs's linear_probing branch scores the raw embeddings against the prompts: no trained head in it, so one computation
+    # serves every replica; every replica's stream still advances by the two loader passes its own run would make
+    st, sts = {}, {}
+    zs = streams.run(0, validate_zs_linear_probing, test_table, opt.text_embedding_dir, opt.zs_temperature, bs_eval, ratio, target="class",
+                     stats=st)
+    zss = streams.run(0, validate_zs_linear_probing, test_table, opt.text_spurious_embedding_dir, opt.zs_temperature, bs_eval, ratio,
+                      target="spurious", stats=sts)
+    for _ in range(2):
+        for r in range(1, R):
+            streams.run(r, lambda: torch.empty((), dtype=torch.int64).random_())
+    return _sweep_finish(R, logs, log, best_epoch, lambda r: sweep.replica(r, best=True), train_accs, val_accs, test_accs,
+                         [zs + (st["counts"],)] * R, [zss + (sts["counts"],)] * R)
+
+
+def _train_adapter_reg_sweep_group(replicas, train_table, val_table, test_table, log):
+    """_train_adapter_reg for up to 16 replicas in lock-step on SweepAdapters: per epoch the train pass on the class prompts, then the
+    reg pass with the same momentum buffers -- the warm-up step index and count restart with each pass -- counted only when it runs
+    on the class prompts; one sync per epoch"""
+    from . import optim as O
+    opts = [o for o, _ in replicas]
+    opt = opts[0]
+    R = len(replicas)
+    dev = train_table.device
+    D = train_table.embeddings.shape[1]
+    reg_idx, val_idx = adapter.stratified_split_indices(val_table.group_array, 0.5)
+    val_idx_dev = torch.as_tensor(val_idx, dtype=torch.int64).to(dev)
+    ratio = train_table.group_ratio.numpy()
+    logs = [[] for _ in range(R)]
+    rec = lambda r, **k: logs[r].append(k)
+    streams = ReplicaStreams([s for _, s in replicas])
+
+    def new_clip():
+        return adapter.CustomCLIP(adapter.Adapter(D, opt.adapter_feat_dim), opt.text_embedding_dir, opt.text_spurious_embedding_dir,
+                                  opt.text_group_embedding_dir, temperature=opt.zs_temperature)
+    mods = [streams.run(r, new_clip) for r in range(R)]
+    for r in range(R):
+        rec(r, kind="init", state={k: v.clone() for k, v in mods[r].adapter.state_dict().items()})
+    sweep = adapter.SweepAdapters.from_modules(mods, dev)
+    lr1 = [_Lr(o.learning_rate) for o in opts]
+    best_acc, best_epoch = [0] * R, [0] * R
+    train_accs, val_accs, test_accs = [[] for _ in range(R)], [[] for _ in range(R)], [[] for _ in range(R)]
+    bs_eval = max(opt.batch_size_reg, 4096)
+    use_group = not opt.use_cls_prompt_in_reg
+    n_train = len(train_table)
+    reg_rows = torch.as_tensor(np.asarray(reg_idx), dtype=torch.int64)
+    for epoch in range(1, opt.epochs + 1):
+        for r in range(R):
+            O.adjust_learning_rate(opts[r], lr1[r], epoch)
+        if opt.balance_val:                                              # DataLoader(balanced_subset, shuffle=False, batch_size=adjusted)
+            balanced = [streams.run(r, adapter.balance_val_indices, val_table.group_array[reg_idx], val_table.n_groups, opt.batch_size_reg)
+                        for r in range(R)]
+            bs = balanced[0][1]
+
+            def order(r):
+                torch.empty((), dtype=torch.int64).random_()             # the un-shuffled loader's base-seed draw
+                return torch.as_tensor(np.asarray(reg_idx[balanced[r][0]]), dtype=torch.int64)
+        else:                                                            # the reg loader itself: shuffle=True
+            bs = opt.batch_size_reg
+
+            def order(r):
+                return reg_rows[dataloader_shuffle_order(len(reg_idx))]
+
+        def lrs(i, n, e=epoch):
+            for r in range(R):
+                O.warmup_learning_rate(opts[r], e, i, n, lr1[r])
+            return [l.lr for l in lr1]
+        _, _, o1, acc = _sweep_train_pass(streams, sweep, train_table, lambda r: dataloader_shuffle_order(n_train), opt.batch_size,
+                                          opt.train_target, False, lrs, opt.momentum, opt.weight_decay, sync=False)
+        c, ls, o2, _ = _sweep_train_pass(streams, sweep, val_table, order, bs, opt.train_target, use_group, lrs, opt.momentum,
+                                         opt.weight_decay, counted=not use_group, acc=acc)
+        n_rows = n_train + (0 if use_group else len(o2[0]))
+        for r in range(R):
+            res = _results(c[r], train_table.n_places)
+            gacc = {k: np.round(res[k], 4) for k in NEW_ORDER_FOR_PRINT[1:]}
+            rec(r, kind="train_reg", epoch=epoch, use_group=use_group, loss=float(ls[r]) / n_rows, acc=int(c[r][:, 1].sum()) / int(c[r][:, 0].sum()),
+                group_acc=gacc, counts=c[r], order=np.concatenate([o1[r], o2[r]]), n_train_rows=n_train)
+            train_accs[r].append(gacc)
+        _sweep_epoch_tail(streams, sweep, epoch, rec, val_table, test_table, bs_eval, opt.train_target, val_idx_dev, len(val_idx), ratio, best_acc,
+                          best_epoch, val_accs, test_accs)
+    if not all(sweep.has_best):
+        raise RuntimeError("train_sweep: a replica never had a worst-group accuracy above 0, so it has no best model")
+    zs, zss = [None] * R, [None] * R
+    for spurious, dst in ((False, zs), (True, zss)):
+        cc, ll = _sweep_validate(streams, sweep, test_table, bs_eval, "spurious" if spurious else "class", None, len(test_table),
+                                 spurious=spurious, best=True)
+        for r in range(R):
+            dst[r] = _eval_results(test_table, cc[r], float(ll[r]), len(test_table), ratio) + (cc[r],)
+    return _sweep_finish(R, logs, log, best_epoch, lambda r: sweep.replica(r, best=True), train_accs, val_accs, test_accs, zs, zss)
 
 
 def sweep_frame(results):

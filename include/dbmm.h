@@ -590,6 +590,34 @@ int dbmm_linear_ce_fwd(const float* x, const float* w, const float* b, const int
                        float* logits, float* loss_rows, float* loss_mean, int64_t B, int64_t D, int64_t C,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* Replica-batched linear-probe step (csrc/linear_sweep.hip): R <= 16 independent runs of one sweep group take one training step in
+ * the launches of ONE dbmm_linear_train_step (one memset of the R ticket counters + one kernel up to the option
+ * linear_step_one_launch_max_b, two kernels above it), the replica being a grid dimension.  Replica r's logits, loss_rows, loss_mean,
+ * w, b, m_w, m_b are the bits dbmm_linear_train_step gives for r alone on table[idx[r]].
+ *   table [n_rows][D], labels / groups [n_rows]: one shared embedding table; idx [idx_R][idx_B] (= [R][B], else DBMM_E_SHAPE): replica
+ *     r trains on rows idx[r][:], read in place (indices are clamped into the table; repeats are legal)
+ *   w / m_w [R][C][D], b / m_b [R][C]: stacked; lr [R] is a HOST array, read during the call (the rates travel as kernel arguments)
+ *   logits [R][B][C], loss_rows [R][B], loss_mean [R]: outputs.  counted != 0: counts int64 [R][G][2] += (n, correct) per group and
+ *     loss_sum double [R] += (double)loss_mean[r] * B, by the step's own launches.
+ * R outside 1..16, C outside 1..8, D % 4 != 0, D > 1024, G outside 1..64: DBMM_E_SHAPE.  table, w, m_w and the workspace 16-byte
+ * aligned; workspace = dbmm_workspace_bytes_linear_sweep_step(R, B, D, C) bytes (linear in R; 0: bad shape). */
+size_t dbmm_workspace_bytes_linear_sweep_step(int64_t R, int64_t B, int64_t D, int64_t C);
+int dbmm_linear_sweep_step(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B,
+                           const int64_t* labels, const int64_t* groups, float* w, float* b, float* m_w, float* m_b,
+                           const float* lr, float momentum, float weight_decay, int first_step, float* logits,
+                           float* loss_rows, float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted,
+                           int64_t R, int64_t B, int64_t D, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Replica-batched evaluation forward of the linear probe: logits [R][B][C] and per-row CE [R][B] (the bits of dbmm_linear_ce_fwd),
+ * group counters and the float64 loss sum (loss_sum[r] += sum_b (double)loss_rows[r][b], fixed order) of R replicas over the SAME B
+ * rows: idx [B] rows of the table, or idx == NULL: rows row0 .. row0 + B - 1 (outside the table: DBMM_E_SHAPE).  One memset + one
+ * kernel whatever R is.  w [R][C][D], b [R][C]. */
+size_t dbmm_workspace_bytes_linear_sweep_eval(int64_t R, int64_t B);
+int dbmm_linear_sweep_eval(const float* table, int64_t n_rows, const int64_t* idx, int64_t row0, const int64_t* labels,
+                           const int64_t* groups, const float* w, const float* b, float* logits, float* loss_rows,
+                           int64_t* counts, double* loss_sum, int64_t G, int64_t R, int64_t B, int64_t D, int64_t C,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* out[i][:] = table[idx[i]][:] -- batch assembly from a device-resident embedding table
  * (replaces the DataLoader + per-item DataFrame lookups of data/ *_embeddings*.py) */
 int dbmm_gather_rows(const float* table, const int64_t* idx, float* out, int64_t n_rows,

@@ -76,7 +76,7 @@ def run_driver(FM, cfg, paths, scale=1.0):
                                                                "/nonexistent/e.json", "--data_dir", "/nonexistent"]
     runs = []                                                                     # one record per seed
     cur = {}
-    names = ("train_one_epoch", "train_reg_seq_one_epoch", "validate", "validate_zs", "update_dict", "set_model", "set_model_multiple_adapter",
+    names = ("train_one_epoch", "train_reg_seq_one_epoch", "train_reg_one_epoch", "validate", "validate_zs", "update_dict", "set_model", "set_model_multiple_adapter",
              "warmup_learning_rate", "warmup_learning_rate_reg", "balance_val", "set_seed", "train_all_epochs")
     orig = {n: getattr(FM, n) for n in names}
 
@@ -85,10 +85,12 @@ def run_driver(FM, cfg, paths, scale=1.0):
             cur.clear(); cur.update(counts=np.zeros((4, 2), dtype=np.int64), start=len(log), lr=[])
             out = fn(*a, **k)
             loss, acc, gacc = out
-            optimizer = a[4] if kind in ("train1", "train2") else None
-            runs[-1]["epochs"].append(dict(kind=kind, use_group=bool(k.get("use_group", False)), target=k.get("target"), loss=float(loss),
+            optimizer = a[5] if kind == "train_reg" else a[4] if kind in ("train1", "train2") else None
+            rows = log[cur["start"]:]
+            runs[-1]["epochs"].append(dict(kind=kind, use_group=bool(k.get("use_group", k.get("group_prompt", False))), target=k.get("target"),
+                                           n_train=sum(1 for s, _ in rows if s == "train"), loss=float(loss),
                                            acc=float(acc), counts=cur["counts"].copy(), group_acc={kk: float(v) for kk, v in gacc.items()},
-                                           idx=[i for _, i in log[cur["start"]:]], lr=list(cur["lr"]),
+                                           idx=[i for _, i in rows], lr=list(cur["lr"]),
                                            lr_end=float(optimizer.param_groups[0]["lr"]) if optimizer is not None else float("nan")))
             return out
         return wrapped
@@ -106,7 +108,8 @@ def run_driver(FM, cfg, paths, scale=1.0):
     def model_maker(fn, which):
         def wrapped(*a, **k):
             out = fn(*a, **k)
-            ad = out[0].new_adapter if which == "stage2" else out[0].adapter
+            m = out[0]                                                            # fc.* of a LinearClassifier / the adapter's layers
+            ad = m.new_adapter if which == "stage2" else m if isinstance(m, FM.LinearClassifier) else m.adapter
             runs[-1]["inits"].append({kk: v.detach().clone().numpy() for kk, v in ad.state_dict().items()})
             return out
         return wrapped
@@ -136,6 +139,7 @@ def run_driver(FM, cfg, paths, scale=1.0):
     FM.parse_option = parse_option
     FM.train_one_epoch = phase("train1", orig["train_one_epoch"])
     FM.train_reg_seq_one_epoch = phase("train2", orig["train_reg_seq_one_epoch"])
+    FM.train_reg_one_epoch = phase("train_reg", orig["train_reg_one_epoch"])
     FM.validate = phase("validate", orig["validate"])
     FM.validate_zs = phase("validate_zs", orig["validate_zs"])
     FM.update_dict, FM.balance_val, FM.set_seed, FM.train_all_epochs = update_dict, balance, set_seed, train_all_epochs
@@ -200,8 +204,10 @@ def gen(cfg=SWEEP_WB, fname="sweep_wb.npz"):
             out[k + "counts_8ulp"], out[k + "loss_8ulp"] = pe8["counts"], np.float64(pe8["loss"])
             out[k + "group_acc"] = np.array([e["group_acc"].get(kk, np.nan) for kk in KEYS], dtype=np.float64)
             out[k + "lr"], out[k + "lr_end"] = np.asarray(e["lr"], dtype=np.float64), np.float64(e["lr_end"])
-            if e["kind"] in ("train1", "train2"):                                 # evaluation passes read their split in order
+            if e["kind"] in ("train1", "train2", "train_reg"):                    # evaluation passes read their split in order
                 out[k + "idx"] = np.asarray(e["idx"], dtype=np.int32)
+            if e["kind"] == "train_reg":                                          # the train loader's rows come first, then the reg loop's
+                out[k + "n_train"] = np.int64(e["n_train"])
             d = (np.abs(e["counts"] - pe["counts"]).max(), np.abs(e["counts"] - pe8["counts"]).max())
             print(f"[seed {run['seed']}] p{i:02d} {e['kind']:11s} n={e['counts'][:, 0].sum():5d} loss {e['loss']:.4f} worst "
                   f"{e['group_acc'].get('worst_acc', float('nan')):.4f} correct {e['counts'][:, 1].tolist()} |1 / 8 ulp count diff| {d}")
