@@ -75,12 +75,16 @@ def test_linear_sweep_workspace_is_linear_in_the_replicas(L):
 
 def test_train_sweep_routes_the_two_methods_to_their_lock_step_schedules(monkeypatch):
     """eligibility: linear_probing with R >= 2, n_cls <= 8, D % 4 == 0, D <= 1024; adapter_reg under the adapter path's conditions;
-    everything else replica by replica; more than 16 replicas in groups of 16"""
+    everything else replica by replica; more than 16 replicas in groups of 16.  Observed where train_sweep hands a group to the
+    schedule: which executor, which method, how many replicas"""
     import torch
     calls = []
-    monkeypatch.setattr(trainer, "_train_linear_sweep_group", lambda reps, *a: calls.append(("linear", len(reps))) or [None] * len(reps))
-    monkeypatch.setattr(trainer, "_train_adapter_reg_sweep_group", lambda reps, *a: calls.append(("adapter_reg", len(reps))) or [None] * len(reps))
-    monkeypatch.setattr(trainer, "_train_sweep_group", lambda reps, *a: calls.append(("adapter", len(reps))) or [None] * len(reps))
+
+    def schedule(ex, opts, *a, **k):
+        assert type(ex) is trainer._LockStep and ex.R == len(opts) == len(ex.streams.states)
+        calls.append((opts[0].tl_method, len(opts)))
+        return [None] * len(opts)
+    monkeypatch.setattr(trainer, "_run_schedule", schedule)
     monkeypatch.setattr(trainer, "train_all_epochs", lambda o, *a, **k: calls.append(("sequential", 1)))
     monkeypatch.setattr(trainer.ops, "get_option", lambda name: 1)
 
@@ -88,10 +92,11 @@ def test_train_sweep_routes_the_two_methods_to_their_lock_step_schedules(monkeyp
         calls.clear()
         opt = SimpleNamespace(tl_method=method, n_cls=2, adapter_feat_dim=128, learning_rate=0.1, **kw)
         table = SimpleNamespace(embeddings=torch.zeros(4, D))
-        trainer.train_sweep(opt, table, table, table, seeds)
+        out = trainer.train_sweep(opt, table, table, table, seeds)
+        assert len(out) == len(seeds)
         return list(calls)
-    assert run("linear_probing", 1024, range(3)) == [("linear", 3)]
-    assert run("linear_probing", 20, range(18)) == [("linear", 16), ("linear", 2)]
+    assert run("linear_probing", 1024, range(3)) == [("linear_probing", 3)]
+    assert run("linear_probing", 20, range(18)) == [("linear_probing", 16), ("linear_probing", 2)]
     assert run("linear_probing", 1028, range(2)) == [("sequential", 1)] * 2
     assert run("linear_probing", 1022, range(2)) == [("sequential", 1)] * 2
     assert run("linear_probing", 512, [7]) == [("sequential", 1)]
@@ -102,7 +107,7 @@ def test_train_sweep_routes_the_two_methods_to_their_lock_step_schedules(monkeyp
     assert calls == [("sequential", 1)] * 2
     assert run("adapter_reg", 512, range(17)) == [("adapter_reg", 16), ("adapter_reg", 1)]
     assert run("adapter_reg", 500, range(2)) == [("sequential", 1)] * 2
-    assert run("adapter_reg_seq", 512, range(2)) == [("adapter", 2)]
+    assert run("adapter_reg_seq", 512, range(2)) == [("adapter_reg_seq", 2)]
     with pytest.raises(ValueError):
         run("contrastive_adapter", 512, range(2))
 
