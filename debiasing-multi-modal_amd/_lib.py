@@ -43,6 +43,7 @@ KERNEL_SOURCES = (
     ("sweep_", ("adapter_sweep.hip", "adapter_bodies.inc", "common.h")),
     ("linear_sweep_", ("linear_sweep.hip", "linear_bodies.inc", "common.h")),
     ("linear_", ("linear_step.hip", "linear_bodies.inc", "common.h")),
+    ("pairdist_", ("pairdist.hip", "common.h")),
 )
 
 
@@ -190,6 +191,8 @@ _SIGS = {
     "dbmm_gather_rows": [_P, _P, _P, _L, _L, _L, _P],
     "dbmm_group_count": [_P, _P, _P, _P, _L, _L, _L, _P],
     "dbmm_group_loss_sum": [_P, _P, _P, _L, _L, _P],
+    "dbmm_workspace_bytes_pairdist": [_L, _L],
+    "dbmm_pairdist_group_sums": [_P, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
 }
 _RESTYPES = {
     "dbmm_error_string": ctypes.c_char_p,
@@ -207,6 +210,7 @@ _RESTYPES = {
     "dbmm_workspace_bytes_linear_ce_fwd": c_size_t,
     "dbmm_workspace_bytes_linear_sweep_step": c_size_t,
     "dbmm_workspace_bytes_linear_sweep_eval": c_size_t,
+    "dbmm_workspace_bytes_pairdist": c_size_t,
 }
 
 EXPORTS = tuple(_SIGS)

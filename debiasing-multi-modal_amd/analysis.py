@@ -1,0 +1,166 @@
+"""The numerical half of the reference's representation report (VisHandler.VisRepAll, demo/visualizer.py:182-222) on the device:
+group-wise embedding statistics (GetGroupWiseStatEbd :657-690), group-wise confidences (GetGroupWiseStatConf :692-708), the
+rows nearest to a prompt embedding (find_closest_sample :19-27) and the 3 x 6 table per split.  The plotting (UMAP, MDS,
+matplotlib) is not here.
+
+The reference's `Div.` row is scipy.cdist(X, X) summed: an N x N float64 matrix per split and per group, which its own notebook
+switches off (return_dist=False) at CelebA's size.  Here it is one pass of the fused Gram-and-distance kernel
+(ops.pairdist_group_sums): every pair is visited once and lands in its (group, group) bucket, nothing N x N is stored, and the
+between-group mean distances come with it.
+"""
+import numpy as np
+import torch
+
+from . import ops, trainer
+
+TABLE_INDEX = ["Acc.", "Div.", "Centr. Norm."]
+TABLE_COLUMNS = ["Avg.", "Worst", "group0", "group1", "group2", "group3"]
+
+
+def _rows_and_groups(embeddings, groups):
+    if isinstance(embeddings, trainer.EmbeddingTable):
+        x = embeddings.embeddings
+        groups = embeddings.targets_group if groups is None else groups
+    else:
+        x = embeddings
+    if groups is None:
+        raise ValueError("a device tensor of embeddings needs its `groups` array")
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+    g_np = groups.detach().cpu().numpy() if torch.is_tensor(groups) else np.asarray(groups)
+    if g_np.ndim != 1 or g_np.shape[0] != x.shape[0]:
+        raise ValueError(f"groups has shape {g_np.shape} for {x.shape[0]} rows")
+    return x, g_np
+
+
+SUM_ROWS = 512
+
+
+def _column_sums(rows):
+    """float64 [D] on the host: ops.colsum (fp32, fixed order) over blocks of SUM_ROWS rows, the blocks' sums added in float64 in
+    block order.  A block's fp32 sum is good to ~1e-6 of it, and nothing the size of the rows is allocated: a float64 reduction in
+    torch would first make a float64 copy of them."""
+    acc = torch.zeros(rows.shape[1], dtype=torch.float64, device=rows.device)
+    for i in range(0, rows.shape[0], SUM_ROWS):
+        acc += ops.colsum(rows[i:i + SUM_ROWS])
+    return acc.cpu().numpy()
+
+
+def group_stats(embeddings, groups=None, return_dist=True):
+    """GetGroupWiseStatEbd: {'mean_vector': {'full': v, g: v, ...}, 'mean_vector_norm': {...}, 'pairwise_distance': {...}} with the
+    groups in np.unique order and numpy values; 'pairwise_distance' is sum over ordered pairs / (n (n - 1)) of the Euclidean distance
+    (nan for a one-row group, the reference's 0 / 0) and stays empty with return_dist=False, which skips the kernel.  One more key
+    than the reference: 'between_distance', float64 [G, G], the mean distance between a row of group a and a row of group b (the
+    diagonal repeats 'pairwise_distance').
+
+    `embeddings`: an EmbeddingTable (its targets_group unless `groups` is given) or a device tensor [N, D] with `groups` [N].
+    The rows are sorted by group first (one gather), so that a group's mean is a slice's column sum and nearly every tile of the
+    distance kernel holds one bucket."""
+    x, g_np = _rows_and_groups(embeddings, groups)
+    uniq, dense, counts = np.unique(g_np, return_inverse=True, return_counts=True)
+    G, N = len(uniq), x.shape[0]
+    if return_dist and G > 8:
+        raise ops.DbmmUnsupported(f"group_stats: {G} groups; the distance kernel buckets at most 8")
+    order = np.argsort(dense, kind="stable")
+    xs = ops.gather_rows(x.float().contiguous(), torch.from_numpy(order).to(x.device))
+    bounds = np.concatenate([[0], np.cumsum(counts)])
+    sums = np.stack([_column_sums(xs[bounds[k]:bounds[k + 1]]) for k in range(G)])                       # [G, D] float64, fixed order
+    mean_full = sums.sum(0) / N
+    means = sums / counts.astype(np.float64)[:, None]
+    norms = np.linalg.norm(np.concatenate([mean_full[None], means]), axis=1)
+    stats = {"mean_vector": {"full": mean_full.astype(np.float32)}, "mean_vector_norm": {"full": np.float32(norms[0])},
+             "pairwise_distance": {}}
+    means_np = means.astype(np.float32)
+    for k, g in enumerate(uniq):
+        stats["mean_vector"][g] = means_np[k]
+        stats["mean_vector_norm"][g] = np.float32(norms[k + 1])
+    if not return_dist:
+        return stats
+    gs = torch.from_numpy(dense[order].astype(np.int64)).to(x.device)
+    S = ops.pairdist_group_sums(xs, gs, G, torch.from_numpy(stats["mean_vector"]["full"]).to(x.device)).cpu().numpy()
+    n = counts.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        stats["pairwise_distance"]["full"] = 2.0 * np.triu(S).sum() / np.float64(N * (N - 1.0))
+        within = 2.0 * np.diag(S) / (n * (n - 1.0))
+        between = S / np.outer(n, n)
+    for k, g in enumerate(uniq):
+        stats["pairwise_distance"][g] = within[k]
+    between[np.arange(G), np.arange(G)] = within
+    stats["between_distance"] = between
+    return stats
+
+
+def group_conf_stats(confidences, groups):
+    """GetGroupWiseStatConf: {'full': mean confidence, g: group g's mean, ...} in np.unique order, summed on the device in float64"""
+    g_np = groups.detach().cpu().numpy() if torch.is_tensor(groups) else np.asarray(groups)
+    conf = confidences if torch.is_tensor(confidences) else torch.as_tensor(np.asarray(confidences))
+    if not conf.is_cuda:
+        conf = conf.cuda()
+    conf = conf.flatten()
+    uniq, dense = np.unique(g_np, return_inverse=True)
+    gd = torch.from_numpy(dense.astype(np.int64)).to(conf.device)
+    onehot = gd.unsqueeze(0) == torch.arange(len(uniq), device=conf.device).unsqueeze(1)                 # [G, N]
+    sums = torch.where(onehot, conf.double().unsqueeze(0), 0.0).sum(1)
+    cnt = onehot.sum(1)
+    out = {"full": np.float32((sums.sum() / conf.numel()).item())}
+    for g, m in zip(uniq, (sums / cnt).cpu().numpy()):
+        out[g] = np.float32(m)
+    return out
+
+
+def closest_samples(embeddings, anchor, top_k=1):
+    """find_closest_sample: indices (numpy int64 [top_k], most similar first) of the rows whose normalised embedding has the
+    largest dot product with the normalised anchor.  The fused normalise-and-similarity kernel, then torch.topk."""
+    x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
+    a = torch.as_tensor(np.asarray(anchor) if not torch.is_tensor(anchor) else anchor, dtype=torch.float32).to(x.device).reshape(-1, 1)
+    tn = ops.text_colnorm(a.contiguous())                                                               # [1, D], unit norm
+    scores = ops.l2norm_sim_ce_fwd(x.float().contiguous(), tn, 1.0, want_loss=False)[0][:, 0]
+    return torch.topk(scores, min(int(top_k), scores.numel())).indices.cpu().numpy()
+
+
+def representation_table(stats, zs_group_acc):
+    """One split's table of VisRepAll (demo/visualizer.py:204-222): rows Acc. / Div. / Centr. Norm., columns Avg., Worst, group0 ..
+    group3, rounded to 3 places.  `stats`: group_stats' dict (with distances); `zs_group_acc`: the group-accuracy dict of validate /
+    validate_zs_linear_probing (its last entry, mean_acc, is dropped like the reference does)."""
+    import pandas as pd
+    values = [list(zs_group_acc.values())[:-1],
+              [list(stats["pairwise_distance"].values())[0]] + [0] + list(stats["pairwise_distance"].values())[1:],
+              [list(stats["mean_vector_norm"].values())[0]] + [0] + list(stats["mean_vector_norm"].values())[1:]]
+    df = pd.DataFrame(values, index=TABLE_INDEX, columns=TABLE_COLUMNS)
+    return df.round(3)
+
+
+@torch.no_grad()
+def _transformed(table, transform, batch_size):
+    was_training = getattr(transform, "training", False)
+    if hasattr(transform, "eval"):
+        transform.eval()
+    out = torch.empty_like(table.embeddings)
+    for i in range(0, len(table), batch_size):
+        out[i:i + batch_size] = transform(table.embeddings[i:i + batch_size])
+    if was_training:
+        transform.train()
+    return out
+
+
+def representation_report(opt, train_table, val_table, test_table, classifier=None, transform=None):
+    """The three tables of VisRepAll (train, val, test) and the group_stats dicts they were built from:
+    ([frame_train, frame_val, frame_test], {'train': stats, 'val': stats, 'test': stats}).
+
+    The `Acc.` row is the split's zero-shot group accuracies: validate() of `classifier` on the class prompts, or -- for
+    linear_probing and without a classifier -- validate_zs_linear_probing, the raw embeddings against opt.text_embedding_dir.
+    `transform` (a callable emb -> emb, e.g. classifier.adapter) is applied batch by batch in eval mode before the statistics: the
+    report after the trained adapter (the reference's note 1.1)."""
+    bs = max(int(getattr(opt, "batch_size", 0) or 0), 4096)
+    ratio = train_table.group_ratio.numpy()
+    zero_shot = classifier is None or getattr(opt, "tl_method", None) == "linear_probing"
+    frames, all_stats = [], {}
+    for split, table in (("train", train_table), ("val", val_table), ("test", test_table)):
+        if zero_shot:
+            acc = trainer.validate_zs_linear_probing(table, opt.text_embedding_dir, opt.zs_temperature, bs, ratio)[2]
+        else:
+            acc = trainer.validate(table, classifier, bs, ratio)[2]
+        emb = table.embeddings if transform is None else _transformed(table, transform, bs)
+        all_stats[split] = group_stats(emb, table.targets_group)
+        frames.append(representation_table(all_stats[split], acc))
+    return frames, all_stats

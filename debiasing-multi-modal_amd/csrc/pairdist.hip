@@ -1,0 +1,401 @@
+// Group-wise sums of pairwise Euclidean distances (the numbers behind the reference's representation report,
+// demo/visualizer.py:650-690: scipy.cdist(X, X) summed, for the whole split and once per group) WITHOUT the N x N matrix:
+//   S[a][b] = sum over unordered pairs i < j with {g_i, g_j} = {a, b} of ||x_i - x_j||_2,   float64 [G][G], symmetric.
+// Every pair is visited once: d^2 = |a|^2 + |b|^2 - 2 a.b over 256 x 256 tiles of the UPPER TRIANGLE of the Gram matrix, sqrt and
+// the bucket reduction in the epilogue, straight from the accumulator layout.
+//
+// Arithmetic.  The rows are centred first (x - centre: distances do not change, the cancellation in |a|^2 + |b|^2 - 2 a.b mostly
+// goes), scaled by an exact power of two so that the largest centred magnitude lies in [2^13, 2^14), and split into two fp16
+// planes hi = fp16(v), lo = fp16(v - hi) (22 bits).  The Gram product is hi.hi + hi.lo + lo.hi, three fp16 MFMA products with
+// fp32 accumulation (lo.lo is below 2^-22 of |a||b|); the row norms are taken from the same rounded values hi + lo, so a pair of
+// identical rows differs from zero only by the accumulation's rounding, and d^2 is clamped at 0.  The diagonal is excluded by
+// index, not by value.
+//
+// Structure.  pairdist_split_kernel writes the planes as ONE fp16 matrix P [N][2 Dp] (row = hi | lo, Dp = D rounded up to 128,
+// zero padded) plus {norm, group} per row.  The tile product is the deep-pipelined structure of gemm_f16_8ph_kernel (f16_ops.hip:
+// 256 x 256 x 64 tiles, LDS-DMA half-tiles staged five phases ahead, two wave rows one barrier apart, persistent workgroups, the
+// next tile's prologue in flight during the epilogue) run over a K of 3 Dp: K tile t reads A from plane columns (t < T ? t : t - T)
+// and B from (t < 2 T ? t : t - 2 T), T = Dp / 64, i.e. the segments hi.hi, hi.lo, lo.hi.  Both operands are row blocks of P.
+//
+// Determinism.  No floating-point atomics: a lane sums its 128 distances in float64, a wave folds them by butterfly, eight wave
+// slots are added in wave order, a workgroup keeps one float64 running sum per (row group, column group) over ITS tiles (the tile ->
+// workgroup map is static), and pairdist_fold_kernel adds the workgroups' 64 sums in workgroup order.  Rows sorted by group make
+// nearly every tile single-bucket (the fast path: no predicates); mixed, ragged and diagonal tiles take the predicated path.
+// Workspace: the planes (4 Dp bytes per row), 8 bytes per row, 512 bytes per workgroup -- O(N D), never O(N^2).
+#include <stdlib.h>
+#include "common.h"
+
+namespace {
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr unsigned OOR = 0x80000000u;
+constexpr long long EXT_LIM = 0x7FFFFFF0LL;
+constexpr int PH_HALF = 128 * 64 * 2;                              // bytes of a half-tile
+constexpr int MAX_WG = 256;                                        // persistent grid: one workgroup per CU
+constexpr int NO_GROUP = 15;                                       // rows past N / labels outside [0, G): in no bucket
+constexpr size_t HEAD_BYTES = 256;                                 // workspace head: the centred absmax (uint bits)
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
+    long long ext = total - shift;
+    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
+}
+__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_dst, unsigned voff, unsigned soff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
+#else
+    (void)r; (void)lds_dst; (void)voff; (void)soff;
+#endif
+}
+__device__ __forceinline__ int scale_exp(float amax) {      // s with amax * 2^s in [2^13, 2^14)
+    const unsigned b = __float_as_uint(amax) & 0x7fffffffu;
+    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
+    return s < -60 ? -60 : (s > 60 ? 60 : s);
+}
+__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
+__device__ __forceinline__ double wave_sum_f64(double v) {         // butterfly: every lane gets the same bits
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+struct RowInfo { float norm; int group; };                         // |hi + lo|^2 in scaled units, group label or NO_GROUP
+
+// max |x - centre| over the split (an integer max of the float bits: the order of the atomics does not matter)
+__global__ __launch_bounds__(256) void pairdist_absmax_kernel(const float* __restrict__ x, const float* __restrict__ c, long long n4, int D4,
+                                                              unsigned* __restrict__ amax_bits) {
+    __shared__ float red[4];
+    float m = 0.f;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const f32x4 v = ((const f32x4*)x)[i], cc = ((const f32x4*)c)[i % D4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m = fmaxf(m, fabsf(v[e] - cc[e]));
+    }
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        if (m == m && m < 3.0e38f) atomicMax(amax_bits, __float_as_uint(m));
+    }
+}
+
+// one wave per row: centre, scale, split; P[row] = hi[0 .. Dp) | lo[0 .. Dp), info[row] = {sum (hi + lo)^2, group}
+__global__ __launch_bounds__(256) void pairdist_split_kernel(const float* __restrict__ x, const float* __restrict__ c, const int64_t* __restrict__ g,
+                                                             const unsigned* __restrict__ amax_bits, u16* __restrict__ P, RowInfo* __restrict__ info,
+                                                             int N, int D, int Dp, int G) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= N) return;
+    const float sc = pow2f(scale_exp(__uint_as_float(*amax_bits)));
+    const float* xr = x + (size_t)row * D;
+    unsigned* ph = (unsigned*)(P + (size_t)row * 2 * Dp);
+    unsigned* pl = ph + Dp / 2;
+    float nrm = 0.f;
+    for (int k = 2 * lane; k < Dp; k += 128) {
+        unsigned hb = 0, lb = 0;
+        if (k < D) {                                               // D is even: a pair is inside or outside
+            const float v0 = (xr[k] - c[k]) * sc, v1 = (xr[k + 1] - c[k + 1]) * sc;
+            const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
+            const _Float16 l0 = (_Float16)(v0 - (float)h0), l1 = (_Float16)(v1 - (float)h1);
+            const float r0 = (float)h0 + (float)l0, r1 = (float)h1 + (float)l1;
+            nrm = fmaf(r0, r0, nrm); nrm = fmaf(r1, r1, nrm);
+            hb = __builtin_bit_cast(unsigned, (f16x2){h0, h1});
+            lb = __builtin_bit_cast(unsigned, (f16x2){l0, l1});
+        }
+        ph[k >> 1] = hb; pl[k >> 1] = lb;
+    }
+    nrm = wave_sum(nrm);
+    if (lane == 0) {
+        const int64_t gv = g[row];
+        info[row] = RowInfo{nrm, (gv >= 0 && gv < G) ? (int)gv : NO_GROUP};
+    }
+}
+
+struct PairDistP {
+    const u16* P; const RowInfo* info; double* part;               // part [MAX_WG][64]: a workgroup's sums per (row group * 8 + column group)
+    long long ldp, p_total;                                        // halves per row of P (2 Dp), bytes of P
+    int N, T, nb, n_tiles;                                         // T = Dp / 64 K tiles per plane, nb = row blocks of 256
+};
+
+__global__ __launch_bounds__(512, 1) void pairdist_tile_kernel(const PairDistP p) {
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[8 * PH_HALF];      // [buffer 2][Ah0, Bh0, Bh1, Ah1] = 128 KB
+    __shared__ float e_norm[512];                                  // epilogue: norms of the tile's 256 rows, then of its 256 columns
+    __shared__ unsigned char e_grp[512];
+    __shared__ unsigned e_mask[2];                                 // groups present among the rows / the columns
+    __shared__ double e_wsum[8][64];                               // per wave, per bucket
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 2, wc = wid & 3;
+    const int fr = lane & 31, fh = lane >> 5;
+    // this workgroup's tiles: the XCD's contiguous range (xcd_remap's split), walked with the stride of the XCD's workgroups
+    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot_in_xcd = blockIdx.x >> 3, wg_per_xcd = (nwg - xcd + 7) >> 3;
+    const int tq = p.n_tiles >> 3, trm = p.n_tiles & 7;
+    const int t_lo = xcd < trm ? xcd * (tq + 1) : trm * (tq + 1) + (xcd - trm) * tq, t_hi = t_lo + tq + (xcd < trm ? 1 : 0);
+    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.P, 0, 0, 0x00020000);
+    __amdgpu_buffer_rsrc_t rsA = rs0, rsW = rs0;
+    int m0 = 0, n0 = 0;
+    // stager: thread -> LDS chunk (tid + 512 i) of a half-tile = local row (tid >> 3) + 64 i, slot tid & 7; it fetches
+    // source chunk slot ^ swz(row).  Half-tile kind k = 0..3 (Ah0, Bh0, Bh1, Ah1) -> operand rows:
+    //   A half h: tile row (lr >> 6) * 128 + h * 64 + (lr & 63);   B half h: tile column (lr >> 5) * 64 + 2 * (lr & 31) + h
+    unsigned voff[4][2];
+    // tile number -> (row block bi <= column block bj) of the upper triangle, row-major: row bi starts at bi * nb - bi (bi - 1) / 2
+    auto set_tile = [&](int tile) {
+        const double w = 2.0 * p.nb + 1.0;
+        int bi = (int)((w - sqrt(w * w - 8.0 * tile)) * 0.5);
+        bi = bi < 0 ? 0 : (bi > p.nb - 1 ? p.nb - 1 : bi);
+        auto start = [&](int b) { return (long long)b * p.nb - (long long)b * (b - 1) / 2; };
+        while (bi > 0 && start(bi) > tile) --bi;
+        while (bi + 1 < p.nb && start(bi + 1) <= tile) ++bi;
+        const int bj = bi + (int)(tile - start(bi));
+        m0 = bi * 256; n0 = bj * 256;
+        rsA = desc(p.P, p.p_total, (long long)m0 * p.ldp * 2);
+        rsW = desc(p.P, p.p_total, (long long)n0 * p.ldp * 2);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int lr = (tid >> 3) + 64 * i, c = (tid & 7) ^ ((lr >> 1) & 7);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int ra = (lr >> 6) * 128 + h * 64 + (lr & 63), rw = (lr >> 5) * 64 + 2 * (lr & 31) + h;
+                voff[h ? 3 : 0][i] = m0 + ra < p.N ? (unsigned)ra * (unsigned)(p.ldp * 2) + c * 16u : OOR;
+                voff[h ? 2 : 1][i] = n0 + rw < p.N ? (unsigned)rw * (unsigned)(p.ldp * 2) + c * 16u : OOR;
+            }
+        }
+    };
+    const int nT = 3 * p.T;                                          // K tiles of the three products: hi.hi, hi.lo, lo.hi
+    // stage number q: kind q & 3 of K tile q >> 2 into buffer (q >> 2) & 1; tiles past the end go through the zero-extent
+    // descriptor so that every phase issues exactly two DMA instructions per wave (the vmcnt arithmetic relies on it)
+    auto stage = [&](int kind, int buf, int t) {
+        const bool isA = kind == 0 || kind == 3, valid = t < nT;
+        unsigned char* slot = lds + (buf * 4 + kind) * PH_HALF + wid * 1024;
+        const __amdgpu_buffer_rsrc_t rs = valid ? (isA ? rsA : rsW) : rs0;
+        const int kt = isA ? (t < p.T ? t : t - p.T) : (t < 2 * p.T ? t : t - 2 * p.T);     // the K tile inside P's row (hi | lo)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) glds16(rs, slot + i * 8192, voff[kind][i], (unsigned)kt * 128u);
+    };
+    // fragment addresses inside a half-tile (bytes): A rows wr * 64 + blk * 32 + fr, B rows wc * 32 + fr, chunk (2 ks + fh) ^ swz
+    int aoff[2][4], boff[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int r = wr * 64 + b * 32 + fr;
+            aoff[b][ks] = r * 128 + (((2 * ks + fh) ^ ((r >> 1) & 7)) << 4);
+        }
+        const int r = wc * 32 + fr;
+        boff[ks] = r * 128 + (((2 * ks + fh) ^ ((r >> 1) & 7)) << 4);
+    }
+    f32x16 acc[4][2];
+    u32x4 fa[2][4], fb0[4], fb1[4];
+
+    // one phase: j = phase within the loop trip (static), t2 = first K tile of the trip.  `first`: the tile's first trip; its
+    // prologue has staged both K tiles of the trip (stages 0 .. 7), so phases 0 - 2 stage nothing and phases 0 - 4 wait for nothing.
+    auto phase = [&](int j, int t2, bool first) {
+        const int ph = j & 3, buf = (j >> 2) & 1;
+        const unsigned char* base = lds + buf * 4 * PH_HALF;
+        if (ph == 0) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) fb0[ks] = *(const u32x4*)(base + 1 * PH_HALF + boff[ks]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) fa[b][ks] = *(const u32x4*)(base + 0 * PH_HALF + aoff[b][ks]);
+        } else if (ph == 1) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) fb1[ks] = *(const u32x4*)(base + 2 * PH_HALF + boff[ks]);
+        } else if (ph == 2) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) fa[b][ks] = *(const u32x4*)(base + 3 * PH_HALF + aoff[b][ks]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (!(first && j < 3)) {
+            const int q = j + 5;                                      // stage number relative to the trip's first tile
+            stage(q & 3, (q >> 2) & 1, t2 + (q >> 2));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (!(first && j < 5)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+        const int ai = (ph >= 2) ? 2 : 0, bj = (ph == 1 || ph == 2) ? 1 : 0;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                acc[ai + b][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[b][ks]),
+                                                                         __builtin_bit_cast(f16x8, bj ? fb1[ks] : fb0[ks]), acc[ai + b][bj], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+    };
+
+    const int n_items = t_lo + slot_in_xcd < t_hi ? (t_hi - t_lo - slot_in_xcd + wg_per_xcd - 1) / wg_per_xcd : 0;
+    auto prologue = [&]() {                                           // stages 0 .. 7 = a tile's first two K tiles, both buffers
+#pragma unroll
+        for (int q = 0; q < 8; ++q) stage(q & 3, (q >> 2) & 1, q >> 2);
+    };
+    const int wm0 = wr * 128, wn0 = wc * 64;
+    double total = 0.0;                                               // thread b < 64: this workgroup's sum of bucket b
+    if (tid < 2) e_mask[tid] = 0u;
+    if (n_items > 0) { set_tile(t_lo + slot_in_xcd); prologue(); }
+    for (int k = 0; k < n_items; ++k) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the prologue's 16 DMA instructions have landed
+        __builtin_amdgcn_s_barrier();
+        if (wr == 1) __builtin_amdgcn_s_barrier();                    // the second wave row runs one barrier behind
+#pragma unroll
+        for (int j = 0; j < 8; ++j) phase(j, 0, true);
+        for (int t2 = 2; t2 < nT; t2 += 2) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) phase(j, t2, false);
+        }
+        if (wr == 0) __builtin_amdgcn_s_barrier();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the look-ahead DMA past the last K tile
+        __builtin_amdgcn_s_barrier();                                 // every wave is done with the ring
+        const int em0 = m0, en0 = n0;
+        if (k + 1 < n_items) { set_tile(t_lo + slot_in_xcd + (k + 1) * wg_per_xcd); prologue(); }   // in flight during the epilogue
+
+        // ---- epilogue: distances and bucket sums straight from the accumulators -------------------------------------------
+        // lane (fr, fh) holds columns wn0 + 2 fr + j (blocks j = 0 / 1: the B halves are the even / odd columns) of rows
+        // wm0 + 32 i + (r & 3) + 8 (r >> 2) + 4 fh.
+        {
+            const int src = (tid < 256 ? em0 : en0 - 256) + tid;      // threads 0 .. 255: the tile's rows, 256 .. 511: its columns
+            RowInfo ri{0.f, NO_GROUP};
+            if (src < p.N) ri = p.info[src];
+            e_norm[tid] = ri.norm;
+            e_grp[tid] = (unsigned char)ri.group;
+            if (ri.group != NO_GROUP) atomicOr(&e_mask[tid >> 8], 1u << ri.group);   // integer, order-free
+        }
+        __syncthreads();
+        const unsigned mA = e_mask[0], mB = e_mask[1];
+        const bool diag = em0 == en0;
+        const bool fast = !diag && em0 + 256 <= p.N && en0 + 256 <= p.N && __builtin_popcount(mA) == 1 && __builtin_popcount(mB) == 1;
+        const int c0 = wn0 + 2 * fr;
+        const float cn0 = e_norm[256 + c0], cn1 = e_norm[256 + c0 + 1];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float rn = e_norm[wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh];
+                acc[i][0][r] = __builtin_sqrtf(fmaxf(fmaf(-2.f, acc[i][0][r], rn + cn0), 0.f));
+                acc[i][1][r] = __builtin_sqrtf(fmaxf(fmaf(-2.f, acc[i][1][r], rn + cn1), 0.f));
+            }
+        if (fast) {
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s += (double)acc[i][0][r] + (double)acc[i][1][r];
+            s = wave_sum_f64(s);
+            if (lane == 0) e_wsum[wid][(__builtin_ctz(mA) << 3) + __builtin_ctz(mB)] = s;
+        } else {
+            const int gb0 = e_grp[256 + c0], gb1 = e_grp[256 + c0 + 1];
+            for (unsigned ma = mA; ma; ma &= ma - 1) {
+                const int ga = __builtin_ctz(ma);
+                double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int lr = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                        const bool in = e_grp[lr] == ga;
+                        v0 += (in && (!diag || lr < c0)) ? (double)acc[i][0][r] : 0.0;
+                        v1 += (in && (!diag || lr < c0 + 1)) ? (double)acc[i][1][r] : 0.0;
+                    }
+                for (unsigned mb = mB; mb; mb &= mb - 1) {
+                    const int gb = __builtin_ctz(mb);
+                    const double s = wave_sum_f64((gb0 == gb ? v0 : 0.0) + (gb1 == gb ? v1 : 0.0));
+                    if (lane == 0) e_wsum[wid][(ga << 3) + gb] = s;
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < 64 && ((mA >> (tid >> 3)) & 1u) && ((mB >> (tid & 7)) & 1u)) {
+            double s = 0.0;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) s += e_wsum[w][tid];
+            total += s;
+        }
+        __syncthreads();
+        if (tid < 2) e_mask[tid] = 0u;                                // for the next tile: its atomics come after that tile's ring barriers
+    }
+    if (tid < 64) p.part[(size_t)blockIdx.x * 64 + tid] = total;
+}
+
+// workgroup sums -> S [G][G]: bucket (a, b) of the kernel is "row in group a, column in group b"; unordered pairs fold (a, b) and (b, a)
+__global__ __launch_bounds__(64) void pairdist_fold_kernel(const double* __restrict__ part, int n_wg, const unsigned* __restrict__ amax_bits, int G,
+                                                           double* __restrict__ S) {
+    __shared__ double tot[64];
+    const int b = threadIdx.x;
+    double s = 0.0;
+    for (int w = 0; w < n_wg; ++w) s += part[(size_t)w * 64 + b];
+    tot[b] = s;
+    __syncthreads();
+    const int ga = b >> 3, gb = b & 7;
+    if (ga < G && gb < G) {
+        const int e = -scale_exp(__uint_as_float(*amax_bits));       // distances were taken in units of 2^-s
+        const double v = ga == gb ? tot[b] : tot[(ga << 3) + gb] + tot[(gb << 3) + ga];
+        S[ga * G + gb] = ldexp(v, e);
+    }
+}
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline long long padded_dim(long long D) { return (D + 127) / 128 * 128; }
+
+}  // namespace
+
+// see include/dbmm.h
+extern "C" size_t dbmm_workspace_bytes_pairdist(int64_t N, int64_t D) {
+    if (N <= 0 || D <= 0) return 0;
+    const size_t Dp = (size_t)padded_dim(D);
+    return HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256) + align_up((size_t)N * 2 * Dp * 2, 256) + (size_t)MAX_WG * 64 * sizeof(double);
+}
+
+// see include/dbmm.h
+extern "C" int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N, int64_t D,
+                                        int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
+    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > 8) return DBMM_E_SHAPE;
+    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
+    if (!x || !groups || !center || !sums || !workspace) return DBMM_E_ARG;
+    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
+    if (workspace_bytes < dbmm_workspace_bytes_pairdist(N, D)) return DBMM_E_WORKSPACE;
+    const long long Dp = padded_dim(D);
+    char* ws = (char*)workspace;
+    unsigned* amax = (unsigned*)ws;
+    RowInfo* info = (RowInfo*)(ws + HEAD_BYTES);
+    u16* P = (u16*)(ws + HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256));
+    double* part = (double*)((char*)P + align_up((size_t)N * 2 * Dp * 2, 256));
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(amax, 0, HEAD_BYTES, s);
+    if (e != hipSuccess) return (int)e;
+    const long long n4 = N * D / 4;
+    const int g1 = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+    hipLaunchKernelGGL(pairdist_absmax_kernel, dim3(g1), dim3(256), 0, s, x, center, n4, (int)(D / 4), amax);
+    DBMM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(pairdist_split_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
+                       (int)G);
+    DBMM_CHECK_LAUNCH();
+    PairDistP p{};
+    p.P = P; p.info = info; p.part = part;
+    p.ldp = 2 * Dp; p.p_total = (long long)N * 2 * Dp * 2;
+    p.N = (int)N; p.T = (int)(Dp / 64); p.nb = (int)((N + 255) / 256);
+    const long long nt = (long long)p.nb * (p.nb + 1) / 2;
+    p.n_tiles = (int)nt;
+    const int grid = nt < MAX_WG ? (int)nt : MAX_WG;
+    hipLaunchKernelGGL(pairdist_tile_kernel, dim3(grid), dim3(512), 0, s, p);
+    DBMM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(pairdist_fold_kernel, dim3(1), dim3(64), 0, s, part, grid, amax, (int)G, sums);
+    DBMM_CHECK_LAUNCH();
+    return DBMM_OK;
+}

@@ -1080,6 +1080,40 @@ def gather_rows(table, idx):
     return out
 
 
+def pairdist_group_sums(x, groups, n_groups, center):
+    """S float64 [G, G], symmetric: S[a, b] = sum over unordered pairs i < j with {groups[i], groups[j]} = {a, b} of
+    ||x[i] - x[j]||_2, on the fused Gram-and-distance kernel (dbmm_pairdist_group_sums): no N x N matrix, float64 sums in a fixed
+    order.  x fp32 [N, D] (D % 64 == 0, D <= 4096), groups int64 [N] in [0, n_groups) (n_groups <= 8), center fp32 [D]: a vector
+    near the rows' mean (the split's mean vector), subtracted before the products are formed.  The whole split's sum is
+    S.triu().sum(); group a's own is S[a, a]."""
+    require_cuda(x, groups, center)
+    _f32c(x)
+    _f32c(center)
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise _lib.DbmmError(f"pairdist_group_sums: x must be [N, D] with N >= 1, got {tuple(x.shape)}")
+    N, D = x.shape
+    if groups.dtype != torch.int64 or not groups.is_contiguous() or groups.dim() != 1:
+        raise _lib.DbmmError("pairdist_group_sums: groups must be a contiguous int64 [N] tensor")
+    _sized("pairdist_group_sums: groups", groups, N)
+    _sized("pairdist_group_sums: center", center, D)
+    if groups.device != x.device or center.device != x.device:
+        raise _lib.DbmmError(f"pairdist_group_sums: groups is on {groups.device}, center on {center.device}, x on {x.device}")
+    if not 1 <= n_groups <= 8:
+        raise _lib.DbmmError(f"pairdist_group_sums: n_groups = {n_groups} outside 1..8")
+    if D % 64 or D > 4096:
+        raise DbmmUnsupported(f"pairdist_group_sums: D = {D}; the kernel serves D % 64 == 0, D <= 4096")
+    L = _lib.lib()
+    nbytes = L.dbmm_workspace_bytes_pairdist(N, D)
+    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # the planes: sized by the call, not cached
+    out = _empty((n_groups, n_groups), device=x.device, dtype=torch.float64)
+    rc = L.dbmm_pairdist_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), out.data_ptr(), N, D, n_groups, ws.data_ptr(),
+                                    ws.numel() * 4, stream())
+    if rc == _lib.E_UNSUPPORTED:
+        raise DbmmUnsupported(f"pairdist_group_sums: no kernel for N = {N}, D = {D}")
+    check(rc, "pairdist_group_sums")
+    return out
+
+
 # ---- fp16 mode of the transformer towers (csrc/f16_ops.hip) -------------------------------------------------------
 
 def _f16c(t):

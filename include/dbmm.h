@@ -632,6 +632,20 @@ int dbmm_group_count(const float* logits, const int64_t* y, const int64_t* g, in
 int dbmm_group_loss_sum(const float* loss_rows, const int64_t* g, float* sums, int64_t B,
                         int64_t G, void* stream);
 
+/* Group-wise sums of pairwise Euclidean distances without the N x N matrix (the numbers of GetGroupWiseStatEbd's
+ * compute_averaged_pairwise_distance, demo/visualizer.py:650-690, for the whole split and every group in ONE pass):
+ *   sums double [G][G], symmetric: sums[a][b] = sum over unordered pairs i < j with {groups[i], groups[j]} = {a, b} of
+ *   ||x[i] - x[j]||_2.  The whole split's sum is the sum of the upper triangle (diagonal included); group a's own is sums[a][a].
+ * x fp32 [N][D] (contiguous), groups int64 [N] in [0, G) (a row with a label outside belongs to no bucket), center fp32 [D]: any
+ * vector near the rows' mean -- it is subtracted before the products are formed (distances do not change, the cancellation does).
+ * fp32-accurate products (hi + lo fp16 planes under a power-of-two scale, fp32 accumulation), float64 sums in a fixed order: two
+ * calls on the same input give the same bits.  Four launches and one memset on `stream`.
+ * D % 64 != 0 or D > 4096: DBMM_E_UNSUPPORTED; G outside 1..8, N outside 1..2^23: DBMM_E_SHAPE; x, center and the workspace
+ * 16-byte aligned.  The workspace holds the planes (about N * D * 4 bytes) and 512 bytes per workgroup, never N x N. */
+size_t dbmm_workspace_bytes_pairdist(int64_t N, int64_t D);
+int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N,
+                             int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
