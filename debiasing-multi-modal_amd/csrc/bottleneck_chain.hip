@@ -11,7 +11,7 @@
 // walks them in 64-channel slabs, and every finished slab is at once the next 64-deep K chunk of conv1': the
 // wide tensor is written once and never read back for conv1.
 //
-// Arithmetic = the fp16-pair path of igemm_f32.hip (fp32 value = fp16 hi + lo with an exact power-of-two scale,
+// Arithmetic = the fp16-pair split of common.h (fp32 value = fp16 hi + lo with an exact power-of-two scale,
 // weights exact in one fp16 plane, fp32 accumulate).  conv3 takes its scale from the producer's device scalar
 // (a_absmax); the slab's scale is WAVE-LOCAL: every wave owns 32 pixel rows through both GEMMs (4x1 wave layout),
 // so it can use the running maximum of its own finished slabs and rescale its conv1' accumulators (exactly, by a
@@ -36,14 +36,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
-
 struct ChainP {
     const float* a; const float* a_absmax;                 // y2 [M][K] in standard pixel order
     const u16* w3; int w3_exp; const float* sc3; const float* b3;      // [N][K] fp16 plane of W3 * 2^w3_exp
@@ -61,31 +53,6 @@ struct ChainP {
     const u16* w2; int w2_exp; const float* sc2; const float* b2;      // [K][(cin/32, kh, kw, 32)] fp16 plane of W2 * 2^w2_exp
     int H, W;
 };
-
-__device__ __forceinline__ int scale_exp(float amax) {      // s with amax * 2^s in [2^13, 2^14)
-    const unsigned b = __float_as_uint(amax) & 0x7fffffffu;
-    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
-    return s < -60 ? -60 : (s > 60 ? 60 : s);
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-
-// (hi, lo) fp16 pairs of x0 * sc and x1 * sc, packed {x0 | x1 << 16}
-__device__ __forceinline__ void split2h_pair(float x0, float x1, float sc, unsigned& hi, unsigned& lo) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(sc));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(sc));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(sc), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(sc), "v"(hi));
-#else
-    (void)x0; (void)x1; (void)sc; hi = lo = 0;
-#endif
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
 
 // LDS rows of RH halves (2 * RH bytes): XOR of the 16-B chunk index with row bits keeps the 16 lanes of a ds_read_b128
 // group on distinct bank quads -- 64-B rows: 4 rows per 256-B bank sweep; 128-B rows: 2; 256-B rows: every row starts a sweep

@@ -48,14 +48,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
-
 struct Chain8P {
     const float* a; const float* a_absmax;                              // y2 [M][256]
     const u16* w3; int w3_exp; const float* sc3; const float* b3;       // [N][256] fp16 plane of W3 * 2^w3_exp
@@ -65,35 +57,6 @@ struct Chain8P {
     int M, N;
 };
 
-__device__ __forceinline__ int scale_exp(float amax) {      // s with amax * 2^s in [2^13, 2^14)
-    const unsigned b = __float_as_uint(amax) & 0x7fffffffu;
-    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
-    return s < -60 ? -60 : (s > 60 ? 60 : s);
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-
-__device__ __forceinline__ void split2h_pair(float x0, float x1, float sc, unsigned& hi, unsigned& lo) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(sc));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(sc));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(sc), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(sc), "v"(hi));
-#else
-    (void)x0; (void)x1; (void)sc; hi = lo = 0;
-#endif
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_dst, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#else
-    (void)r; (void)lds_dst; (void)voff; (void)soff;
-#endif
-}
 // one ds_max_u32 per lane on ONE LDS word (the hardware serialises the 64 lanes; atomicMax() would be expanded by the compiler into a
 // 64-trip scan loop over the lanes first)
 __device__ __forceinline__ void lds_max_u32(unsigned* word, unsigned v) {

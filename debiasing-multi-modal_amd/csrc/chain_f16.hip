@@ -24,14 +24,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
-
 struct ChainHP {
     const u16* a; const u16* w3; const float* sc3; const float* b3; const u16* res; u16* x;
     const u16* w1; const float* sc1; const float* b1; u16* y1;
@@ -49,15 +41,6 @@ __device__ __forceinline__ int row_pixel(const ChainHP& p, int m) {
     return (n * p.Ho + 2 * hp + (q >> 1)) * p.Wo + 2 * (rem - hp * wp2) + (q & 1);
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const f16x2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 // LDS rows of RB bytes: XOR of the 16-B chunk index with row bits keeps the lanes of a ds_read_b128 group on distinct bank quads
 template <int RB>
 __device__ __forceinline__ int swz(int row) { return RB == 128 ? ((row >> 1) & 7) : (row & 15); }

@@ -1,4 +1,11 @@
-// Shared helpers for the gfx950 kernels of libdbmm_hip.so.
+// Shared helpers for the gfx950 kernels of libdbmm_hip.so, each defined ONCE here:
+//   - the vector typedefs of the MFMA fragments and 8 / 16-byte accesses (f16x8, u32x4, ...);
+//   - DBMM_N_CU and dbmm_cut_slices: persistent-grid sizing;
+//   - wave_sum / wave_max, xcd_remap: wave reductions and the tile -> workgroup map;
+//   - desc / glds16 with OOR and EXT_LIM: rebased buffer descriptors and LDS-DMA loads;
+//   - scale_exp / pow2f / split2h_pair / frag / pack2: the fp16 (hi, lo) split under an exact power-of-two scale, the
+//     library's precision contract.  Every parity kernel splits with THESE functions.
+// plus the internal C entries that one kernel file calls in another.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +14,14 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16;
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int DBMM_N_CU = 256;                   // compute units of the MI355X: a persistent grid is one workgroup (or a multiple) per CU
 
 #define DBMM_CHECK_LAUNCH()                      \
     do {                                         \
@@ -39,13 +54,13 @@ int dbmm_gemm_dual_pair_8ph(const float* a, int64_t lda, const float* a_absmax, 
                             int64_t K2, const float* ratio, const float* bias, float* c, int64_t ldc, float* c_absmax, int64_t M, int64_t N, int act,
                             void* stream);
 
-// K cut of a short last round of the 256-tile persistent kernels: `rem` tiles left for 256 workgroups, `trips` loop trips per tile -> slices
+// K cut of a short last round of the 256-tile persistent kernels: `rem` tiles left for DBMM_N_CU workgroups, `trips` loop trips per tile -> slices
 // per tile (0: no cut).  One slice per workgroup at most: a slice costs ~0.3 of a layer-3 tile on top of its share of the loop (prologue,
 // 256 KB of partial sums) and the summing launch reads rem x S x 256 KB, so a second slice per workgroup (rem > 128) never paid
 // (HISTORY.md, round 4); with rem = 64 and S = 4 the cut is already neutral.
 static inline int dbmm_cut_slices(int rem, int trips) {
-    if (rem <= 0 || rem > 128) return 0;
-    int S = 256 / rem;
+    if (rem <= 0 || rem > DBMM_N_CU / 2) return 0;
+    int S = DBMM_N_CU / rem;
     S = S < trips ? S : trips;
     S = S < 16 ? S : 16;
     return S >= 2 ? S : 0;
@@ -82,3 +97,54 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + idx;
 }
+
+// Buffer addressing.  OOR: a voffset that is out of range for every descriptor (>= any accepted extent, and OOR + (K offset)
+// cannot wrap): the hardware drops the store / returns 0 for the load, so ragged edges need no branch.
+constexpr unsigned OOR = 0x80000000u;
+constexpr long long EXT_LIM = 0x7FFFFFF0LL;
+
+// Buffer descriptor of a tensor of `total` bytes rebased to `shift` bytes (wave-uniform) past its start: extent = what is left
+// of the tensor, capped below 2 GiB.  Offsets are then relative to the tile's first row / image, a few MB at most, while the
+// tensor itself may be any size.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
+    long long ext = total - shift;
+    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
+}
+// LDS-DMA: 16 B per lane from a buffer straight into LDS at (wave-uniform dst) + 16 * lane.
+// (The builtin only exists in the device pass, hence the guard; the host pass never calls it.)
+__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_dst, unsigned voff, unsigned soff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
+#else
+    (void)r; (void)lds_dst; (void)voff; (void)soff;
+#endif
+}
+
+// The fp16-pair split.  Contract: s with amax * 2^s in [2^13, 2^14), clamped to +-60; hi = fp16(x * sc), lo = fp16(x * sc - hi).
+// fp16 tops out at 65504 and hi + lo keep 22 bits; the fp32 accumulator is rescaled by 2^-(s + w_exp) in the epilogue --
+// powers of two, so the scaling itself is exact.
+__device__ __forceinline__ int scale_exp(float amax) {
+    const unsigned b = __float_as_uint(amax) & 0x7fffffffu;
+    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
+    return s < -60 ? -60 : (s > 60 ? 60 : s);
+}
+__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
+// (hi, lo) fp16 pairs of x0 * sc and x1 * sc, packed {x0 | x1 << 16}, on v_fma_mix{lo,hi}_f16
+__device__ __forceinline__ void split2h_pair(float x0, float x1, float sc, unsigned& hi, unsigned& lo) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(sc));
+    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(sc));
+    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(sc), "v"(hi));
+    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(sc), "v"(hi));
+#else
+    (void)x0; (void)x1; (void)sc; hi = lo = 0;
+#endif
+}
+// fp16-mode twin of the packing: {fp16(a) | fp16(b) << 16}
+__device__ __forceinline__ unsigned pack2(float a, float b) {
+    const f16x2 v = {(_Float16)a, (_Float16)b};
+    return __builtin_bit_cast(unsigned, v);
+}
+// four packed fp16 pairs as one MFMA operand
+__device__ __forceinline__ f16x8 frag(const unsigned (&v)[4]) { return __builtin_bit_cast(f16x8, (u32x4){v[0], v[1], v[2], v[3]}); }

@@ -27,14 +27,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
-
 struct ResStreamP {
     const float* a; const float* a_absmax;
     const u16* w; int w_exp; const float* sc; const float* b;
@@ -52,29 +44,6 @@ __device__ __forceinline__ int row_pixel(const ResStreamP& p, int m) {
     return (n * p.Ho + 2 * hp + (q >> 1)) * p.Wo + 2 * (rem - hp * wp2) + (q & 1);
 }
 
-__device__ __forceinline__ int scale_exp(float amax) {      // s with amax * 2^s in [2^13, 2^14)
-    const unsigned b = __float_as_uint(amax) & 0x7fffffffu;
-    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
-    return s < -60 ? -60 : (s > 60 ? 60 : s);
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-
-__device__ __forceinline__ void split2h_pair(float x0, float x1, float sc, unsigned& hi, unsigned& lo) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(sc));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(sc));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(sc), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(sc), "v"(hi));
-#else
-    (void)x0; (void)x1; (void)sc; hi = lo = 0;
-#endif
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
 // LDS rows of RH halves: XOR of the 16-B chunk index with row bits keeps the 16 lanes of a ds_read_b128 group on distinct bank quads
 template <int RH>
 __device__ __forceinline__ int swz(int row) { return RH == 64 ? ((row >> 1) & 7) : (row & 15); }
@@ -257,7 +226,7 @@ int dbmm_conv1x1_res_stream(const float* a, const float* a_absmax, const void* w
     p.y_absmax = y_absmax; p.M = (int)M; p.N = (int)N; p.n_tiles = (int)((M + BM - 1) / BM);
     p.yp = y_pooled; p.Ho = (int)Ho; p.Wo = (int)Wo;
     const long long units = (long long)p.n_tiles * (N / BNS);
-    const int grid = (int)(units < 512 ? units : 512);              // two workgroups per CU
+    const int grid = (int)(units < 2 * DBMM_N_CU ? units : 2 * DBMM_N_CU);      // two workgroups per CU
     hipStream_t s = (hipStream_t)stream;
     if (y_pooled) hipLaunchKernelGGL((conv1x1_res_stream_kernel<256, 1>), dim3(grid), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((conv1x1_res_stream_kernel<256, 0>), dim3(grid), dim3(256), 0, s, p);

@@ -21,28 +21,11 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
-
 struct ResStreamHP {
     const u16* a; const u16* w; const float* sc; const float* b; const u16* res; u16* y; u16* yp;
     int M, N, n_tiles, Ho, Wo;
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const f16x2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 // pixel (standard order) of tile row m: identity, or 2x2-window-major (m = 4 * pooled pixel + dy * 2 + dx)
 template <int POOL>
 __device__ __forceinline__ int row_pixel(const ResStreamHP& p, int m) {
@@ -196,7 +179,7 @@ int dbmm_conv1x1_res_stream_f16(const void* x, const void* w, const float* scale
     p.a = (const u16*)x; p.w = (const u16*)w; p.sc = scale; p.b = bias; p.res = (const u16*)residual; p.y = (u16*)y; p.yp = (u16*)y_pooled;
     p.M = (int)M; p.N = (int)Cout; p.n_tiles = (int)((M + BM - 1) / BM); p.Ho = (int)Ho; p.Wo = (int)Wo;
     const long long units = (long long)p.n_tiles * (Cout / BNS);
-    const int grid = (int)(units < 512 ? units : 512);              // two workgroups per CU
+    const int grid = (int)(units < 2 * DBMM_N_CU ? units : 2 * DBMM_N_CU);      // two workgroups per CU
     hipStream_t s = (hipStream_t)stream;
     if (Cin == 128) hipLaunchKernelGGL((conv1x1_res_stream_f16_kernel<128, 1>), dim3(grid), dim3(256), 0, s, p);
     else if (y_pooled) hipLaunchKernelGGL((conv1x1_res_stream_f16_kernel<256, 1>), dim3(grid), dim3(256), 0, s, p);

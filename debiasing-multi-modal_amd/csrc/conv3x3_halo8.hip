@@ -29,12 +29,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
 constexpr int AR = 272, A_PLANE = AR * 64, A_BUF = 2 * A_PLANE;   // rows of a plane (64 B each); bytes of a plane / of a buffer (hi, lo)
 constexpr int W_HALF = 128 * 64, W_BUF = 2 * W_HALF;
 constexpr int OFF_W = 0, OFF_A = 2 * W_BUF;                       // W first: every fragment read then reaches its buffer / plane / block through the
@@ -54,34 +48,6 @@ struct Halo8P {
     float* ws;
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_dst, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#else
-    (void)r; (void)lds_dst; (void)voff; (void)soff;
-#endif
-}
-__device__ __forceinline__ int scale_exp(float amax) {      // s with amax * 2^s in [2^13, 2^14)
-    const unsigned b = __float_as_uint(amax) & 0x7fffffffu;
-    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
-    return s < -60 ? -60 : (s > 60 ? 60 : s);
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-__device__ __forceinline__ void split2h_pair(float x0, float x1, float sc, unsigned& hi, unsigned& lo) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(sc));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(sc));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(sc), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(sc), "v"(hi));
-#else
-    (void)x0; (void)x1; (void)sc; hi = lo = 0;
-#endif
-}
 // standard-order pixel of the top-left corner of pooled pixel mp (rows run window-major: m = 4 * mp + 2 dy + dx)
 __device__ __forceinline__ int pool_base_pixel(const Halo8P& p, int mp) {
     const int wp2 = p.W >> 1, hwp = (p.H >> 1) * wp2;
@@ -713,7 +679,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo8n_kernel(const Halo8P p) 
 }  // namespace
 
 // see common.h.  DBMM_E_UNSUPPORTED: the caller falls back to igemm_halo_kernel.
-// Tile quantisation: the persistent grid works in rounds of 256 tiles (layer 3 at B = 1024: 784 tiles = 3.06 rounds = the time of 4).
+// Tile quantisation: the persistent grid works in rounds of DBMM_N_CU tiles (layer 3 at B = 1024: 784 tiles = 3.06 rounds = the time of 4).
 // With a workspace and split != 0 the tiles of a short last round are cut along K into S slices (dbmm_cut_slices, common.h) dealt over the
 // workgroups, and a small second launch sums the slices and runs the epilogue: the last round then costs ~1 / S of a round plus the slices'
 // fixed costs and 2 x tiles x S x 256 KB of traffic.
@@ -740,7 +706,7 @@ int dbmm_conv3x3_halo8(const float* x, const float* x_absmax, const void* w_plan
         p.tiles_n = (int)(Cout / 128);
         p.n_tiles = (int)((M + 255) / 256) * p.tiles_n;
         p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-        const int gridn = p.n_tiles < 256 ? p.n_tiles : 256;
+        const int gridn = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;
 #define DBMM_H8N(P, A) hipLaunchKernelGGL((conv3x3_halo8n_kernel<P, A>), dim3(gridn), dim3(512), 0, s, p)
         if (pool) { if (act == DBMM_ACT_RELU) DBMM_H8N(1, 1); else DBMM_H8N(1, 0); }
         else { if (act == DBMM_ACT_RELU) DBMM_H8N(0, 1); else DBMM_H8N(0, 0); }
@@ -751,14 +717,14 @@ int dbmm_conv3x3_halo8(const float* x, const float* x_absmax, const void* w_plan
     p.tiles_n = (int)(Cout / 256);
     p.n_tiles = (int)((M + 255) / 256) * p.tiles_n;
     p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-    const int rem = p.n_tiles % 256, trips = (int)(3 * (Cin / 32) / 2);
-    if (split && workspace && dbmm_aligned16(workspace) && p.n_tiles > 256 && rem != 0) {
+    const int rem = p.n_tiles % DBMM_N_CU, trips = (int)(3 * (Cin / 32) / 2);
+    if (split && workspace && dbmm_aligned16(workspace) && p.n_tiles > DBMM_N_CU && rem != 0) {
         const int S = dbmm_cut_slices(rem, trips);
         if (S >= 2 && (size_t)rem * S * (128 * 512 * sizeof(float)) <= workspace_bytes) {
             p.n_full = p.n_tiles - rem; p.n_cut = rem; p.n_slices = S; p.ws = (float*)workspace;
         }
     }
-    const int grid = p.n_tiles < 256 ? p.n_tiles : 256;               // persistent: one workgroup per CU
+    const int grid = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;             // persistent: one workgroup per CU
 #define DBMM_H8(P, A) hipLaunchKernelGGL((conv3x3_halo8_kernel<P, A>), dim3(grid), dim3(512), 0, s, p)
     if (pool) { if (act == DBMM_ACT_RELU) DBMM_H8(1, 1); else DBMM_H8(1, 0); }
     else { if (act == DBMM_ACT_RELU) DBMM_H8(0, 1); else DBMM_H8(0, 0); }

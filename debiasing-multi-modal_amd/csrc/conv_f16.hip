@@ -34,31 +34,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_dst, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#else
-    (void)r; (void)lds_dst; (void)voff; (void)soff;
-#endif
-}
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const f16x2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-
 struct ConvHP {
     const u16* x; const u16* w; const float* scale; const float* bias; u16* y;
     long long x_total, w_total, y_total;        // bytes
@@ -1116,7 +1091,7 @@ extern "C" int dbmm_conv3x3_bn_relu_f16(const void* x, const void* w, const floa
         q.x = (const u16*)x; q.w = (const u16*)w; q.scale = scale; q.bias = bias; q.y = (u16*)y; q.B = (int)B; q.H = (int)H; q.W = (int)W;
         q.tiles_w = (int)(W / C_TC); q.tiles_h = (int)(H / C_TR); q.n_tiles = (int)(B * q.tiles_h * q.tiles_w);
         const int per_cu = Cout == 32 ? 4 : 2;
-        const int grid = q.n_tiles < 256 * per_cu ? q.n_tiles : 256 * per_cu;
+        const int grid = q.n_tiles < DBMM_N_CU * per_cu ? q.n_tiles : DBMM_N_CU * per_cu;
         if (Cout == 32) {
             if (pool) hipLaunchKernelGGL((conv3x3_c32_f16_kernel<32, 1>), dim3(grid), dim3(256), 0, s, q);
             else hipLaunchKernelGGL((conv3x3_c32_f16_kernel<32, 0>), dim3(grid), dim3(256), 0, s, q);
@@ -1131,7 +1106,7 @@ extern "C" int dbmm_conv3x3_bn_relu_f16(const void* x, const void* w, const floa
     if (dbmm_opt(OPT_F16_CONV_8PH) && (Cout % 256) == 0 && M >= 16384) {
         p.tiles_n = (int)(Cout / 256);
         p.n_tiles = (int)((M + 255) / 256) * p.tiles_n;
-        const int grid = p.n_tiles < 256 ? p.n_tiles : 256;
+        const int grid = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;
         if (pool) hipLaunchKernelGGL((conv3x3_f16_8ph_kernel<1>), dim3(grid), dim3(512), 0, s, p);
         else hipLaunchKernelGGL((conv3x3_f16_8ph_kernel<0>), dim3(grid), dim3(512), 0, s, p);
         DBMM_CHECK_LAUNCH();

@@ -11,7 +11,7 @@
 //     its 6 x 30-pixel input patch is fetched ONCE and all nine taps are formed from it by shifted LDS reads
 //     (1.6 input reads per output pixel instead of 9 through L1);
 //   * the next tile's patch is in flight (registers) while the current tile computes and stores.
-// Arithmetic = the fp16-pair path of igemm_f32.hip: x = (hi + lo) * 2^-s with s from the producer's device maximum,
+// Arithmetic = the fp16-pair split of common.h: x = (hi + lo) * 2^-s with s from the producer's device maximum,
 // weights exact in one fp16 plane, two MFMA products, fp32 accumulation, exact power-of-two rescale.
 //
 // Output goes straight from the MFMA accumulator layout: one register = two 128-B row segments per wave instruction
@@ -22,13 +22,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
 constexpr int TR = 4, TC = 28;                        // output tile: rows x columns (112 pixels)
 constexpr int PR = TR + 2, PC = TC + 2, PPX = PR * PC; // input patch: 6 x 30 = 180 pixels
 constexpr int CIN = 32, KTOT = 9 * CIN;               // 288
@@ -41,29 +34,6 @@ struct PatchP {
     int B, H, W, tiles_w, tiles_h, n_tiles;
 };
 
-__device__ __forceinline__ int scale_exp(float amax) {
-    const unsigned b = __float_as_uint(amax) & 0x7fffffffu;
-    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
-    return s < -60 ? -60 : (s > 60 ? 60 : s);
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-
-__device__ __forceinline__ void split2h_pair(float x0, float x1, float sc, unsigned& hi, unsigned& lo) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(sc));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(sc));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(sc), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(sc), "v"(hi));
-#else
-    (void)x0; (void)x1; (void)sc; hi = lo = 0;
-#endif
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
 // patch rows of 32 halves (64 B): four rows per 256-B bank sweep
 __device__ __forceinline__ int pswz(int row) { return (row >> 2) & 3; }
 
@@ -236,7 +206,7 @@ extern "C" int dbmm_conv3x3_c32_bn_relu_x2(const float* x, const float* x_absmax
     p.y = y; p.y_absmax = y_absmax; p.B = (int)B; p.H = (int)H; p.W = (int)W;
     p.tiles_w = (int)(W / TC); p.tiles_h = (int)(H / TR); p.n_tiles = (int)(B * p.tiles_h * p.tiles_w);
     const int per_cu = Cout == 32 ? 3 : 2;                        // 42 / 61 KB of LDS per workgroup
-    const int grid = p.n_tiles < 256 * per_cu ? p.n_tiles : 256 * per_cu;
+    const int grid = p.n_tiles < DBMM_N_CU * per_cu ? p.n_tiles : DBMM_N_CU * per_cu;
     hipStream_t s = (hipStream_t)stream;
     if (Cout == 32) {
         if (pool) hipLaunchKernelGGL((conv3x3_c32_kernel<32, 1>), dim3(grid), dim3(256), 0, s, p);

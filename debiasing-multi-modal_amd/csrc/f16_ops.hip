@@ -16,28 +16,9 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
 // 128-B LDS rows (64 halves): XOR of the 16-B chunk index, two rows per 256-B bank sweep
 __device__ __forceinline__ int swz64(int row) { return (row >> 1) & 7; }
 
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const f16x2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 __device__ __forceinline__ float fast_exp2(float x) {       // v_exp_f32: 1 ulp, denormal results flush to zero
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_exp2f(x);
@@ -285,14 +266,6 @@ constexpr int PH_HALF = 128 * 64 * 2;                              // bytes of a
 #ifndef GF16_ABL            // timing ablations (results wrong): 1 no C stores, 2 no epilogue arithmetic either, 8 no main loop
 #define GF16_ABL 0
 #endif
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_dst, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#else
-    (void)r; (void)lds_dst; (void)voff; (void)soff;
-#endif
-}
 
 template <int ACT, int RES, int TWO = 0>                             // epilogue specialised: a run-time `act` costs 22 VALU per output pair
 __global__ __launch_bounds__(512, 1) void gemm_f16_8ph_kernel(const GemmHP p) {
@@ -634,7 +607,6 @@ constexpr int A_OROW = 72;                                       // O staging pi
 __device__ __forceinline__ u32x4 vt_frag(const unsigned char* p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
     const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p + 8 * 128));
     const u32x2 ua = __builtin_bit_cast(u32x2, a), ub = __builtin_bit_cast(u32x2, b);
@@ -1055,7 +1027,7 @@ extern "C" int dbmm_conv1x1_dual_bn_act_f16(const void* y2, const void* w3, cons
     p.tiles_n = (int)(Cout / 256);
     p.n_tiles = (int)((M + 255) / 256) * p.tiles_n;
     p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-    const int grid = p.n_tiles < 256 ? p.n_tiles : 256;
+    const int grid = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;
     if (act == DBMM_ACT_RELU) hipLaunchKernelGGL((gemm_f16_8ph_kernel<1, 0, 1>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((gemm_f16_8ph_kernel<0, 0, 1>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p);
     DBMM_CHECK_LAUNCH();
@@ -1094,9 +1066,9 @@ int gemm_f16_impl(const void* a, int64_t lda, const void* w, int64_t ldw, const 
             // With a workspace the tiles of the short last round (at most 128) are instead cut along K into S = min(256 / tiles, trips)
             // slices, one workgroup each, and gemm_f16_8ph_fixup_kernel sums them and runs the epilogue (as gemm_pair_8ph.hip).
             p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-            if (part == 0 && dbmm_opt(OPT_TAIL_SPLIT) && p.n_tiles > 256 && (p.n_tiles % 256) != 0) {
-                const int rem = p.n_tiles % 256, trips = (int)(K / 128);
-                int S = rem <= 128 ? 256 / rem : 1;
+            if (part == 0 && dbmm_opt(OPT_TAIL_SPLIT) && p.n_tiles > DBMM_N_CU && (p.n_tiles % DBMM_N_CU) != 0) {
+                const int rem = p.n_tiles % DBMM_N_CU, trips = (int)(K / 128);
+                int S = rem <= DBMM_N_CU / 2 ? DBMM_N_CU / rem : 1;
                 S = S < trips ? S : trips;
                 const int mode = dbmm_opt(OPT_TAIL_SPLIT);            // 1: by rule, 2: the K cut wherever it applies, 3: the row split only
                 // same box, tools/bench_tail_f16.py (profiles/r04_ab_tail_f16.log): the cut pays on long K only -- ViT-B/32's c_proj (K 3072, 300 /
@@ -1107,11 +1079,11 @@ int gemm_f16_impl(const void* a, int64_t lda, const void* w, int64_t ldw, const 
                     (size_t)rem * S * (128 * 512 * sizeof(float)) <= workspace_bytes) {
                     p.n_full = p.n_tiles - rem; p.n_cut = rem; p.n_slices = S; p.ws = (float*)workspace;
                 } else {
-                const int64_t mt = (M + 255) / 256, full_rounds = p.n_tiles / 256, mt_full = full_rounds * 256 / p.tiles_n;
+                const int64_t mt = (M + 255) / 256, full_rounds = p.n_tiles / DBMM_N_CU, mt_full = full_rounds * DBMM_N_CU / p.tiles_n;
                 const int64_t m_split = mt_full * 256, tail_rows = M - m_split;
                 const int64_t tail_tiles = ((tail_rows + 127) / 128) * ((N + 127) / 128);
                 // (the row split: +1-2 % on the 300-tile projections of ViT-B/32 at 512 images, a loss from 600 tiles on)
-                if ((mode == 3 || (mode == 1 && p.n_tiles <= 512)) && mt_full >= 1 && mt_full < mt && tail_tiles <= 512 && (p.n_tiles % 256) <= 128) {
+                if ((mode == 3 || (mode == 1 && p.n_tiles <= 512)) && mt_full >= 1 && mt_full < mt && tail_tiles <= 512 && (p.n_tiles % DBMM_N_CU) <= DBMM_N_CU / 2) {
                     int rc = gemm_f16_impl(a, lda, w, ldw, out_scale, bias, residual, ldr, res_first, c, ldc, m_split, N, K, act, stream, 1, nullptr, 0);
                     if (rc != DBMM_OK) return rc;
                     return gemm_f16_impl((const u16*)a + m_split * lda, lda, w, ldw, out_scale, bias,
@@ -1120,7 +1092,7 @@ int gemm_f16_impl(const void* a, int64_t lda, const void* w, int64_t ldw, const 
                 }
                 }
             }
-            const int grid = p.n_tiles < 256 ? p.n_tiles : 256;   // persistent: one workgroup per CU
+            const int grid = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;   // persistent: one workgroup per CU
             hipStream_t s8 = (hipStream_t)stream;
 #define DBMM_8PH(A, R) hipLaunchKernelGGL((gemm_f16_8ph_kernel<A, R>), dim3(grid), dim3(512), 0, s8, p)
             if (residual) { if (act == 0) DBMM_8PH(0, 1); else if (act == 1) DBMM_8PH(1, 1); else DBMM_8PH(2, 1); }

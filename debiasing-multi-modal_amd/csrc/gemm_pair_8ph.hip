@@ -1,7 +1,7 @@
 // Parity-mode GEMM of the transformer towers on the deep-pipelined structure of gemm_f16_8ph_kernel (f16_ops.hip):
 //   c = act(alpha * ((a @ w^T) * out_scale + bias) + residual),  a fp32 [M][K],  w exact in ONE fp16 plane (w * 2^w_exp),
 // at fp32 accuracy: a = (hi + lo) * 2^-s, two fp16 MFMA products per fp32 product, fp32 accumulation (the fp16-pair
-// arithmetic of igemm_f32.hip; clip/model.py:171-240 are the GEMMs it serves in the parity mode).
+// split of common.h; clip/model.py:171-240 are the GEMMs it serves in the parity mode).
 //
 // What differs from the fp16 kernel: the activations are fp32 in HBM, so LDS-DMA brings them in as fp32 and the split into
 // (hi, lo) happens when a wave READS its fragments -- 16 VALU per 32 x 16 fragment, placed in the "load" half of a phase,
@@ -22,11 +22,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned OOR = 0x80000000u;
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
 constexpr int A_HALF = 128 * 32 * 4, W_HALF = 128 * 32 * 2;        // bytes of the half-tiles
 constexpr int BUF = 2 * A_HALF + 2 * W_HALF;                       // one buffer: Ah0, Bh0, Bh1, Ah1
 constexpr int OFF_AH0 = 0, OFF_BH0 = A_HALF, OFF_BH1 = A_HALF + W_HALF, OFF_AH1 = A_HALF + 2 * W_HALF;
@@ -48,36 +43,6 @@ struct PairP {
     int n_full, n_cut, n_slices;
     float* ws;
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t desc(const void* base, long long total, long long shift) {
-    long long ext = total - shift;
-    ext = ext < 0 ? 0 : (ext > EXT_LIM ? EXT_LIM : ext);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + shift), 0, (int)ext, 0x00020000);
-}
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_dst, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#else
-    (void)r; (void)lds_dst; (void)voff; (void)soff;
-#endif
-}
-__device__ __forceinline__ int scale_exp(float amax) {      // s with amax * 2^s in [2^13, 2^14)
-    const unsigned b = __float_as_uint(amax) & 0x7fffffffu;
-    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
-    return s < -60 ? -60 : (s > 60 ? 60 : s);
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-__device__ __forceinline__ void split2h_pair(float x0, float x1, float sc, unsigned& hi, unsigned& lo) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(sc));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(sc));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(sc), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(sc), "v"(hi));
-#else
-    (void)x0; (void)x1; (void)sc; hi = lo = 0;
-#endif
-}
-__device__ __forceinline__ f16x8 frag(const unsigned (&v)[4]) { return __builtin_bit_cast(f16x8, (u32x4){v[0], v[1], v[2], v[3]}); }
 
 template <int ACT, int RES, int TWO = 0>
 __global__ __launch_bounds__(512, 1) void gemm_pair_8ph_kernel(const PairP p) {
@@ -469,21 +434,21 @@ __global__ __launch_bounds__(512) void gemm_pair_8ph_fixup_kernel(const PairP p)
     }
 }
 
-// Tile quantisation: the persistent grid works in rounds of 256 tiles.  With a workspace the tiles of a short last round are cut along K into
+// Tile quantisation: the persistent grid works in rounds of DBMM_N_CU tiles.  With a workspace the tiles of a short last round are cut along K into
 // S slices (dbmm_cut_slices, common.h) dealt over the workgroups, and a small second launch sums the slices and runs the epilogue (as
 // conv3x3_halo8.hip does).
 int pair_8ph_launch(PairP& p, int act, bool two, void* workspace, size_t workspace_bytes, void* stream) {
     p.tiles_n = p.N / 256;
     p.n_tiles = ((p.M + 255) / 256) * p.tiles_n;
     p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-    const int rem = p.n_tiles % 256, trips = p.K / 64;
-    if (!two && workspace && dbmm_aligned16(workspace) && p.n_tiles > 256 && rem != 0) {
+    const int rem = p.n_tiles % DBMM_N_CU, trips = p.K / 64;
+    if (!two && workspace && dbmm_aligned16(workspace) && p.n_tiles > DBMM_N_CU && rem != 0) {
         const int S = dbmm_cut_slices(rem, trips);
         if (S >= 2 && (size_t)rem * S * (128 * 512 * sizeof(float)) <= workspace_bytes) {
             p.n_full = p.n_tiles - rem; p.n_cut = rem; p.n_slices = S; p.ws = (float*)workspace;
         }
     }
-    const int grid = p.n_tiles < 256 ? p.n_tiles : 256;               // persistent: one workgroup per CU
+    const int grid = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;             // persistent: one workgroup per CU
     hipStream_t s = (hipStream_t)stream;
 #define DBMM_P8(A, R, T) hipLaunchKernelGGL((gemm_pair_8ph_kernel<A, R, T>), dim3(grid), dim3(512), 0, s, p)
     if (two) { if (act == 0) DBMM_P8(0, 0, 1); else if (act == 1) DBMM_P8(1, 0, 1); else return DBMM_E_UNSUPPORTED; }

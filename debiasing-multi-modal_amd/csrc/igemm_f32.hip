@@ -91,15 +91,8 @@ struct IgemmP {
 
 inline int epi_direct_env() { return dbmm_opt(OPT_IGEMM_EPI_DIRECT); }
 
-// fp16-pair path: A is scaled by 2^s so that max|A| * 2^s lies in [2^13, 2^14) (fp16 tops out at
-// 65504; the fp32 accumulator is rescaled by 2^-(s + w_exp) in the epilogue -- powers of two,
-// so the scaling itself is exact).
-__device__ __forceinline__ int a_scale_exp(const float* a_absmax) {
-    const unsigned b = __float_as_uint(*a_absmax) & 0x7fffffffu;
-    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
-    return s < -60 ? -60 : (s > 60 ? 60 : s);
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
+// fp16-pair path: A is scaled by 2^s, s = scale_exp (common.h) of the producer's device scalar
+__device__ __forceinline__ int a_scale_exp(const float* a_absmax) { return scale_exp(*a_absmax); }
 // pool2 row order: row m = 4 * (pooled pixel, standard order) + (dy * 2 + dx).  Returns the
 // standard-order pixel index of the window's top-left corner (q = 0); q adds (q >> 1) * Wo + (q & 1).
 __device__ __forceinline__ int pool2_base_pixel(const IgemmP& p, int mp) {
@@ -111,10 +104,6 @@ __device__ __forceinline__ int pool2_base_pixel(const IgemmP& p, int mp) {
 __device__ __forceinline__ float igemm_acc_scale(const IgemmP& p) {
     return p.a_absmax ? pow2f(-a_scale_exp(p.a_absmax) - p.w_exp) : 1.f;
 }
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOR = 0x80000000u;   // >= any accepted extent, and OOR + (K offset) cannot wrap
-constexpr long long EXT_LIM = 0x7FFFFFF0LL;
 
 // Buffer descriptor of an A operand rebased to `shift` bytes (16-B aligned, wave-uniform) past its start: extent =
 // what is left of the tensor, capped below 2 GiB.  Offsets are then relative to the tile's first row / image, a few
@@ -538,9 +527,6 @@ constexpr bool EPI_DIRECT = false;        // fp32-input kernels: small register 
 // 16-B chunk index XOR (row >> 3) & 1 -> conflict-free ds_read_b128 fragment reads.
 // ---------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void split3(float x, u16& hi, u16& mid, u16& lo) {
     const __bf16 h = (__bf16)x;
@@ -560,18 +546,6 @@ __device__ __forceinline__ void split2h(float xs, u16& hi, u16& lo) {
     const _Float16 h = (_Float16)xs;
     const _Float16 l = (_Float16)(xs - (float)h);
     hi = __builtin_bit_cast(u16, h); lo = __builtin_bit_cast(u16, l);
-}
-
-// (hi, lo) fp16 pairs of x0 * sc and x1 * sc, packed {x0 | x1 << 16}, on v_fma_mix{lo,hi}_f16
-__device__ __forceinline__ void split2h_pair(float x0, float x1, float sc, unsigned& hi, unsigned& lo) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(sc));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(sc));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(sc), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(sc), "v"(hi));
-#else
-    (void)x0; (void)x1; (void)sc; hi = lo = 0;
-#endif
 }
 
 // instruction-order fences of the split kernels' K loop (see kloop): X3_SCHED 0 = none (compiler's order),
@@ -1345,8 +1319,6 @@ bool fast_ok(const IgemmP& p) {
     return p.a_bytes != 0 && p.w_bytes != 0;
 }
 
-constexpr int NUM_CUS = 256;
-
 // template arguments of this thread's most recent igemm launch (profiling aid: lets bench.py
 // name the exact instantiation rocprofv3 reports); not used by any compute path
 thread_local int g_last_cfg[11] = {0};
@@ -1360,7 +1332,7 @@ inline int sk_mode_env() { return dbmm_opt(OPT_IGEMM_STREAMK); }
 // three (layer3/4 conv1: partial sums, extra pipeline fills, a fix-up launch).  It is kept for
 // grids that cannot fill every resident slot once (small batches); DBMM_IGEMM_STREAMK=2 forces it.
 inline bool sk_skip(int n_tiles, int resident_per_cu) {
-    return sk_mode_env() != 2 && n_tiles >= NUM_CUS * resident_per_cu;
+    return sk_mode_env() != 2 && n_tiles >= DBMM_N_CU * resident_per_cu;
 }
 
 constexpr int X2_MINB(int BN, int NW) { return (BN == 128 && NW == 2) ? 2 : 3; }
@@ -1375,11 +1347,11 @@ int launch_cfg(IgemmP& p, hipStream_t s, int nbatch, void* ws, size_t ws_bytes) 
     // loop is long enough to be worth cutting (DBMM_IGEMM_STREAMK=0 disables, =2 forces)
     const int sk_mode = sk_mode_env();
     const int nk = (p.K + BK - 1) / BK;
-    const int grid_sk = NUM_CUS * MINB;
+    const int grid_sk = DBMM_N_CU * MINB;
     const size_t need = (size_t)grid_sk * 2 * BM * BN * sizeof(float);
     if (sk_mode && nbatch == 1 && ws && ws_bytes >= need && dbmm_aligned16(ws) && nk >= 8) {
-        const double per_cu = (double)p.n_tiles / NUM_CUS;
-        const double eff = per_cu / (double)((p.n_tiles + NUM_CUS - 1) / NUM_CUS);
+        const double per_cu = (double)p.n_tiles / DBMM_N_CU;
+        const double eff = per_cu / (double)((p.n_tiles + DBMM_N_CU - 1) / DBMM_N_CU);
         if (sk_mode == 2 || (eff < 0.93 && (long long)p.n_tiles * nk >= 4LL * grid_sk)) {
             p.sk_blocks = grid_sk; p.sk_ws = (float*)ws;
         }
@@ -1403,7 +1375,7 @@ int launch_cfg(IgemmP& p, hipStream_t s, int nbatch, void* ws, size_t ws_bytes) 
             const int MB = p.nw == 1 ? MB1 : MB2;
             const int nkx = p.K / (bk32 ? 32 : 16);
             if (p.sk_blocks) {
-                p.sk_blocks = NUM_CUS * MB;
+                p.sk_blocks = DBMM_N_CU * MB;
                 if ((long long)p.n_tiles * nkx < 4LL * p.sk_blocks || nkx < 8 || sk_skip(p.n_tiles, MB)) p.sk_blocks = 0;
             }
             const dim3 g3(p.sk_blocks ? p.sk_blocks : p.n_tiles, 1);
@@ -1441,7 +1413,7 @@ int launch_cfg(IgemmP& p, hipStream_t s, int nbatch, void* ws, size_t ws_bytes) 
         if (x3_allow && p.w3 && nbatch == 1 && fast_ok<AMODE, WMODE, BK>(p) && slab_ok16) {
             constexpr int MB = BN == 128 ? 2 : 3;   // register budget for the two prefetch sets (no spills)
             if (p.sk_blocks) {   // the resident grid is sized for this kernel's occupancy
-                p.sk_blocks = NUM_CUS * MB;
+                p.sk_blocks = DBMM_N_CU * MB;
                 if ((long long)p.n_tiles * (p.K / 16) < 4LL * p.sk_blocks) p.sk_blocks = 0;
             }
             const dim3 g3(p.sk_blocks ? p.sk_blocks : p.n_tiles, 1);
@@ -1501,11 +1473,11 @@ int launch_halo(IgemmP& p, hipStream_t s, void* ws, size_t ws_bytes, int* rc) {
     const bool whole_units = (p.K % 192) == 0;           // stream-K cuts at unit boundaries
     p.sk_blocks = 0; p.sk_ws = nullptr; p.sk_nk = 0;
     const int sk_mode = sk_mode_env();
-    const int grid_sk = NUM_CUS * MB;
+    const int grid_sk = DBMM_N_CU * MB;
     const size_t need = (size_t)grid_sk * 2 * BM * BN * sizeof(float);
     if (!POOL && sk_mode && whole_units && ws && ws_bytes >= need && dbmm_aligned16(ws) && nu >= 4) {
-        const double per_slot = (double)p.n_tiles / NUM_CUS;
-        const double eff = per_slot / (double)((p.n_tiles + NUM_CUS - 1) / NUM_CUS);
+        const double per_slot = (double)p.n_tiles / DBMM_N_CU;
+        const double eff = per_slot / (double)((p.n_tiles + DBMM_N_CU - 1) / DBMM_N_CU);
         if (sk_mode == 2 || (eff < 0.93 && (long long)p.n_tiles * nu >= 4LL * grid_sk && !sk_skip(p.n_tiles, MB))) {
             p.sk_blocks = grid_sk; p.sk_ws = (float*)ws; p.sk_nk = nu;
         }
@@ -1757,9 +1729,9 @@ int conv_impl(const float* x, const float* w, const float* bias, const float* re
             const long long tn8 = Cout / 256, mt8 = (M + 255) / 256, t8 = mt8 * tn8;
             // Tile quantisation (option tail_split): the tiles of a short last round (at most 128) are cut along K over the idle CUs inside
             // dbmm_gemm_pair_8ph_ws -- layer 3's conv1 (784 tiles = 3.06 rounds) then costs 3 rounds + 16 x 16 slices instead of 4 rounds.
-            const long long rem8 = t8 % NUM_CUS;
-            const bool cut = dbmm_opt(OPT_TAIL_SPLIT) && ws && t8 > NUM_CUS && rem8 != 0 && rem8 <= NUM_CUS / 2;
-            const bool pays = m8 == 2 || (m8 == 1 && Cin >= 512 && Cout <= 512 && (Cout == 512 || t8 >= 8 * NUM_CUS || cut));
+            const long long rem8 = t8 % DBMM_N_CU;
+            const bool cut = dbmm_opt(OPT_TAIL_SPLIT) && ws && t8 > DBMM_N_CU && rem8 != 0 && rem8 <= DBMM_N_CU / 2;
+            const bool pays = m8 == 2 || (m8 == 1 && Cin >= 512 && Cout <= 512 && (Cout == 512 || t8 >= 8 * DBMM_N_CU || cut));
             if (pays && p.wh && p.nw == 1 && p.a_absmax && !p.pool2 && (Cout % 256) == 0 && (Cin % 64) == 0 && M >= 16384 && p.wh_bytes &&
                 dbmm_aligned16(y) && (!residual || dbmm_aligned16(residual)) && 256 * (Cin > Cout ? Cin : Cout) * 4 < 0x7FFFFFF0LL) {
                 const int rc = dbmm_gemm_pair_8ph_ws(x, Cin, sx.a_absmax, p.wh, p.w_exp, K, sx.oscale, bias, residual, Cout, y, Cout, sx.absmax_out,
@@ -1828,7 +1800,7 @@ extern "C" void dbmm_debug_last_igemm(int* out11) {
 
 extern "C" size_t dbmm_workspace_bytes_igemm(void) {
     // stream-K partial accumulators: (256 CUs x 6 resident workgroups) x 2 slots x 128x128 fp32
-    return (size_t)NUM_CUS * 6 * 2 * 128 * 128 * sizeof(float);
+    return (size_t)DBMM_N_CU * 6 * 2 * 128 * 128 * sizeof(float);
 }
 
 extern "C" int dbmm_gemm_bias_act(const float* a, int64_t lda, int trans_a, const float* w, int64_t ldw,
@@ -1999,11 +1971,11 @@ extern "C" int dbmm_gemm_dual_bn_act_x2(const float* a, int64_t lda, const float
     if (p.n_tiles < 192) return DBMM_E_UNSUPPORTED;
     const int nk = (int)(K / 32 + K2 / 32);
     const int sk_mode = sk_mode_env();
-    const int grid_sk = NUM_CUS * MB;
+    const int grid_sk = DBMM_N_CU * MB;
     const size_t need = (size_t)grid_sk * 2 * BM * BN * sizeof(float);
     if (sk_mode && workspace && workspace_bytes >= need && dbmm_aligned16(workspace) && nk >= 8) {
-        const double per_cu = (double)p.n_tiles / NUM_CUS;
-        const double eff = per_cu / (double)((p.n_tiles + NUM_CUS - 1) / NUM_CUS);
+        const double per_cu = (double)p.n_tiles / DBMM_N_CU;
+        const double eff = per_cu / (double)((p.n_tiles + DBMM_N_CU - 1) / DBMM_N_CU);
         if (sk_mode == 2 || (eff < 0.93 && (long long)p.n_tiles * nk >= 4LL * grid_sk && !sk_skip(p.n_tiles, MB))) {
             p.sk_blocks = grid_sk; p.sk_ws = (float*)workspace; p.sk_nk = nk;
         }

@@ -102,26 +102,7 @@ __global__ __launch_bounds__(256) void stem_s2_kernel(const float* __restrict__ 
 // no LDS at all.  The accumulator layout (column = channel) stores two whole 128-B pixel rows per
 // wave instruction.  Bound: HBM (0.15 MB in + 1.6 MB out per image at 224 px).
 // ---------------------------------------------------------------------------------------
-typedef _Float16 stem_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int stem_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ stem_f16x8 stem_frag(const unsigned (&v)[4]) { return __builtin_bit_cast(stem_f16x8, (stem_u32x4){v[0], v[1], v[2], v[3]}); }
-
-__device__ __forceinline__ int stem_scale_exp(float amax) {          // 2^s * amax in [2^13, 2^14): fp16 hi + lo keep 22 bits
-    const unsigned b = __float_as_uint(amax) & 0x7fffffffu;
-    int s = b ? 13 - ((int)(b >> 23) - 127) : 0;
-    return s < -60 ? -60 : (s > 60 ? 60 : s);
-}
-__device__ __forceinline__ float stem_pow2(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-__device__ __forceinline__ void stem_split_pair(float x0, float x1, float sc, unsigned& hi, unsigned& lo) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(x0), "v"(sc));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(x1), "v"(sc));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(sc), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(sc), "v"(hi));
-#else
-    (void)x0; (void)x1; (void)sc; hi = lo = 0;
-#endif
-}
+// (the split, scale rule and fragment cast: scale_exp / pow2f / split2h_pair / frag of common.h)
 
 #ifndef STEM_PREFETCH
 #define STEM_PREFETCH 1
@@ -133,7 +114,6 @@ __global__ __launch_bounds__(256, STEM_MINB(NB)) void stem_s2_mfma_kernel(const 
                                                            float* __restrict__ y_absmax, int B, int H, int W, int Ho, int Wo,
                                                            int n_blocks) {
     constexpr int Cout = NB * 32;
-    constexpr unsigned OOR = 0x80000000u;
     // (the wave index through readfirstlane: the block number and with it the buffer descriptors are then PROVABLY
     //  wave-uniform; derived from threadIdx alone the compiler wrapped each of the 48 buffer operations of a block in a
     //  waterfall loop -- 208 v_readfirstlane in the listing)
@@ -166,14 +146,14 @@ __global__ __launch_bounds__(256, STEM_MINB(NB)) void stem_s2_mfma_kernel(const 
                 wv[j][t] = (fh ? v1 : v0) ? w[k * Cout + j * 32 + fr] : 0.f;
                 wmax = fmaxf(wmax, fabsf(wv[j][t]));
             }
-        e_w = stem_scale_exp(wave_max(wmax));
-        const float sc = stem_pow2(e_w);
+        e_w = scale_exp(wave_max(wmax));
+        const float sc = pow2f(e_w);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) stem_split_pair(wv[j][ks * 8 + 2 * q], wv[j][ks * 8 + 2 * q + 1], sc, wh[j][ks][q], wlo[j][ks][q]);
+                for (int q = 0; q < 4; ++q) split2h_pair(wv[j][ks * 8 + 2 * q], wv[j][ks * 8 + 2 * q + 1], sc, wh[j][ks][q], wlo[j][ks][q]);
             bv[j] = bias ? bias[j * 32 + fr] : 0.f;
         }
     }
@@ -220,16 +200,16 @@ __global__ __launch_bounds__(256, STEM_MINB(NB)) void stem_s2_mfma_kernel(const 
         float amax = 0.f;
 #pragma unroll
         for (int t = 0; t < 16; ++t) amax = fmaxf(amax, fabsf(xv[t]));
-        const int e_a = stem_scale_exp(wave_max(amax));
-        const float sc = stem_pow2(e_a);
+        const int e_a = scale_exp(wave_max(amax));
+        const float sc = pow2f(e_a);
         unsigned ah[2][4], al[2][4];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) stem_split_pair(xv[ks * 8 + 2 * q], xv[ks * 8 + 2 * q + 1], sc, ah[ks][q], al[ks][q]);
+            for (int q = 0; q < 4; ++q) split2h_pair(xv[ks * 8 + 2 * q], xv[ks * 8 + 2 * q + 1], sc, ah[ks][q], al[ks][q]);
         const long long mb = (long long)blk * 32;
         if (STEM_PREFETCH && blk + n_waves < n_blocks) gather(blk + n_waves);   // next block's taps in flight during the MFMAs and stores
-        const float osc = stem_pow2(-e_a - e_w);
+        const float osc = pow2f(-e_a - e_w);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             f32x16 acc;
@@ -237,12 +217,12 @@ __global__ __launch_bounds__(256, STEM_MINB(NB)) void stem_s2_mfma_kernel(const 
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(stem_frag(al[ks]), stem_frag(wh[j][ks]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(stem_frag(ah[ks]), stem_frag(wlo[j][ks]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag(al[ks]), frag(wh[j][ks]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag(ah[ks]), frag(wlo[j][ks]), acc, 0, 0, 0);
             }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(stem_frag(ah[ks]), stem_frag(wh[j][ks]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag(ah[ks]), frag(wh[j][ks]), acc, 0, 0, 0);
             // accumulator register r = pixel row (r & 3) + 8 (r >> 2) + 4 fh, column = channel j * 32 + fr
             const long long rows_left = M - mb;
             const long long bytes = (rows_left < 32 ? rows_left : 32) * Cout * 4;
@@ -385,7 +365,6 @@ __global__ __launch_bounds__(256) void attnpool_tokens_kernel(const void* __rest
     for (int j = 0; j < HW; ++j) {
         f32x4 v;
         if constexpr (XH) {
-            typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
             const f16x4 h = ((const f16x4*)x)[((long long)b * HW + j) * C4 + c];
             v = (f32x4){(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
         } else {

@@ -201,7 +201,6 @@ __global__ __launch_bounds__(64) void mha_core_kernel(const float* __restrict__ 
 // K rows are stored with the 16-B chunk index XOR (row & 15): the 16 lanes of a ds_read_b128
 // group read the same chunk of 16 different rows.
 // ---------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // NW = 1: one wave per workgroup, its own K / V tiles (short sequences: one query tile per head).
 // NW = 4: four query tiles of the same (head, image) share each K / V block in LDS; the next block's

@@ -1,0 +1,50 @@
+"""The fp16-pair split and the buffer helpers are defined once, in csrc/common.h (Precision).
+
+A kernel file that pastes its own copy of one of them, or a prefixed twin, fails here (source scan, no compute)."""
+import glob
+import os
+import re
+
+import pytest
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "debiasing-multi-modal_amd", "csrc")
+FUNCTIONS = ("desc", "glds16", "scale_exp", "pow2f", "split2h_pair", "pack2", "frag")
+CONSTANTS = ("OOR", "EXT_LIM")
+
+
+def _sources():
+    out = {}
+    for path in sorted(glob.glob(os.path.join(CSRC, "*"))):
+        if path.endswith((".hip", ".h", ".inc")):
+            txt = open(path).read()
+            out[os.path.basename(path)] = re.sub(r"//[^\n]*", "", txt)        # comments may speak of the names
+    return out
+
+
+SOURCES = _sources()
+
+
+def _where(pattern):
+    return sorted((name, len(re.findall(pattern, txt))) for name, txt in SOURCES.items() if re.search(pattern, txt))
+
+
+def test_sources_found():
+    assert "common.h" in SOURCES and len(SOURCES) >= 20
+
+
+@pytest.mark.parametrize("name", FUNCTIONS)
+def test_device_helper_defined_once_in_common_h(name):
+    # a __device__ function definition of exactly this name: declarator, parameter list, opening brace
+    assert _where(r"__device__\s[^;(){}]*?\b%s\s*\([^;{}]*\)\s*\{" % name) == [("common.h", 1)]
+
+
+@pytest.mark.parametrize("name", CONSTANTS)
+def test_constant_defined_once_in_common_h(name):
+    assert _where(r"\bconstexpr\s[^;=(){}]*?\b%s\s*=" % name) == [("common.h", 1)]
+
+
+@pytest.mark.parametrize("name", FUNCTIONS + CONSTANTS + ("pow2", "split_pair", "f16x8", "u32x4"))
+def test_no_stem_prefixed_twin(name):
+    assert _where(r"\bstem_%s\b" % name) == []
