@@ -172,6 +172,11 @@ _SIGS = {
     "dbmm_sgd_momentum": [_L, _P, _P, _P, _P, _F, _F, _F, _I, _P],
     "dbmm_workspace_bytes_adapter_train_step": [_L, _L, _L, _I],
     "dbmm_adapter_train_step": [_P] * 26 + [_F, _P, _F, _F, _F, _F, _I, _P, _P, _P, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_group_dro_weights": [_P, _P, _P, _P, _P, _P, _L, _L, _F, _P],
+    "dbmm_l2norm_sim_ce_bwd_weighted": [_P, _P, _F, _I, _P, _P, _P, _P, _P, _L, _F, _P, _L, _L, _L, _P],
+    "dbmm_adapter_train_step_gdro": [_P] * 26 + [_F, _P, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _F, _L, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_adapter_sweep_step_gdro": [_P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _F, _P, _F, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _I, _P, _F, _L, _L,
+                                     _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_adapter_sweep_step": [_L, _L, _L, _L, _I],
     "dbmm_adapter_sweep_step": [_P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _F, _P, _F, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _I, _L, _L, _L, _L, _L,
                                 _P, _Z, _P],

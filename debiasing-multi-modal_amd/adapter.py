@@ -177,6 +177,57 @@ class _SimCEFn(torch.autograd.Function):
         return dz * gloss, None, None, None, None, None
 
 
+class GroupDRO:
+    """State of online group DRO (Sagawa et al. 2020, Algorithm 1): the adversarial group distribution `q` (float32 [n_groups] on the
+    device, or [replicas, n_groups] for a sweep), initialised to 1 / n_groups, and its step size.  A robust step -- `loss(...,
+    robust=(state, groups))`, `train_step(..., robust=(state, groups))`, `SweepAdapters.step(..., robust=state)` -- updates `q` in
+    place from the batch's group losses and minimises sum_g q_g L_g.  Holds one tensor and two numbers: deepcopy and pickle work."""
+
+    def __init__(self, n_groups, step_size=0.01, device="cuda", replicas=None):
+        if not 1 <= int(n_groups) <= ops.GDRO_MAX_GROUPS:
+            raise ValueError(f"GroupDRO: n_groups must be in 1 .. {ops.GDRO_MAX_GROUPS}, got {n_groups}")
+        self.n_groups, self.step_size = int(n_groups), float(step_size)
+        shape = (self.n_groups,) if replicas is None else (int(replicas), self.n_groups)
+        self.q = torch.full(shape, 1.0 / self.n_groups, dtype=torch.float32, device=device)
+
+    def reset(self):
+        """q = 1 / n_groups again (a new stage of the schedule)"""
+        self.q.fill_(1.0 / self.n_groups)
+
+
+class _SimCERobustFn(torch.autograd.Function):
+    """Fused logits + group-DRO loss; returns (robust loss, logits, per-row CE).  Three launches: forward rows, group reduction + q
+    update (in place, in the forward), weighted backward rows."""
+
+    @staticmethod
+    def forward(ctx, z, z_old, tn, temperature, ebd_weight, labels, groups, q, eta):
+        logits, loss_rows, _, _, inv_norm = ops.l2norm_sim_ce_fwd(z, tn, temperature, labels=labels, z_old=z_old, ebd_weight=ebd_weight,
+                                                                  want_mean=False)
+        robust, stats = ops.group_dro_weights(loss_rows, groups, q, eta)
+        ctx.save_for_backward(z, inv_norm, tn, logits, labels, groups, stats)
+        ctx.cfg = (temperature, ebd_weight, z_old is not None)
+        ctx.mark_non_differentiable(logits, loss_rows)
+        return robust, logits, loss_rows
+
+    @staticmethod
+    def backward(ctx, gloss, _gl, _gr):
+        z, inv_norm, tn, logits, labels, groups, stats = ctx.saved_tensors
+        T, w, blended = ctx.cfg
+        dz = ops.l2norm_sim_ce_bwd_weighted(z, inv_norm, tn, T, logits, labels, groups, stats[0], blended=blended, ebd_weight=w)
+        return dz * gloss, None, None, None, None, None, None, None, None
+
+
+def _robust_operands(robust, n_rows):
+    """(groups, q, eta) of a `robust=(state, groups)` argument"""
+    state, groups = robust
+    if not isinstance(state, GroupDRO) or state.q.dim() != 1:
+        raise TypeError("robust=(GroupDRO state of one run, group ids of the batch) expected")
+    groups = groups.contiguous()
+    if groups.numel() != n_rows:
+        raise RuntimeError(f"robust: {groups.numel()} group ids for a batch of {n_rows} rows")
+    return groups, state.q, state.step_size
+
+
 def _step_key(new_ad, old_ad, optimizer):
     """every device address the fused step's argument block holds (15 of the trainable adapter incl. its six momentum buffers, 9 of the
     frozen one), or None while a momentum buffer does not exist yet"""
@@ -302,23 +353,29 @@ class CustomCLIP(nn.Module):
         tn = self._text("spurious", features.device)
         return _SimFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5))
 
-    def loss(self, features, labels, use_group=False, spurious=False):
+    def loss(self, features, labels, use_group=False, spurious=False, robust=None):
         """fused step body: returns (mean CE, logits, per-row CE); `spurious`: against the spurious-attribute prompts
-        (forward_spurious + criterion, final_main.py:764-766)."""
+        (forward_spurious + criterion, final_main.py:764-766).  `robust` = (GroupDRO state, group ids of the batch): the loss is the
+        group-DRO robust loss and the state's q is updated in place."""
         z, z_old = self._features(features)
         tn = self._text("spurious" if spurious else "group" if use_group else "class", features.device)
+        if robust is not None:
+            groups, q, eta = _robust_operands(robust, features.shape[0])
+            return _SimCERobustFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5), labels, groups, q, eta)
         return _SimCEFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5), labels)
 
     def _step_adapters(self):
         """(trainable adapter, frozen old adapter or None)"""
         return self.adapter, None
 
-    def train_step(self, features, labels, optimizer, use_group=False):
+    def train_step(self, features, labels, optimizer, use_group=False, robust=None):
         """The whole step body of final_main.py:455-466 / :610-623 -- forward, mean CE, backward and
         the SGD-momentum update -- as ONE C call (~20 launches back to back, no autograd graph, no
         host round trip).  Uses the optimiser's lr / momentum / weight_decay and its
         `momentum_buffer` state, so it can be mixed freely with `loss.backward(); optimizer.step()`.
-        Requires train mode.  Returns (mean CE, logits, per-row CE), all on the device."""
+        Requires train mode.  Returns (mean CE, logits, per-row CE), all on the device.  `robust` = (GroupDRO state, group ids of
+        the batch): the group-DRO step (two launches more) -- the state's q is updated in place, the returned loss is the robust
+        loss."""
         if not self.training:
             raise RuntimeError("train_step needs classifier.train()")
         new_ad, old_ad = self._step_adapters()
@@ -358,7 +415,7 @@ class CustomCLIP(nn.Module):
             return ops.adapter_train_step(
                 features.detach().contiguous(), labels.contiguous(), plan["args"], plan["H"], plan["with_old"],
                 getattr(self, "ebd_weight", 0.5), tn, self.temperature, group["lr"], group.get("momentum", 0.0),
-                group.get("weight_decay", 0.0), first)
+                group.get("weight_decay", 0.0), first, robust=None if robust is None else _robust_operands(robust, features.shape[0]))
 
 
 class MultipleAdapter(CustomCLIP):
@@ -550,11 +607,15 @@ class SweepAdapters:
             self._args[key] = a
         return a
 
-    def step(self, table, idx, labels, groups, which, lrs, momentum, weight_decay, counts, loss_sum, counted=True):
+    def step(self, table, idx, labels, groups, which, lrs, momentum, weight_decay, counts, loss_sum, counted=True, robust=None):
         """one training step of every replica on rows idx[r] of `table` against the `which` prompts.  Returns (mean CE [R], logits
-        [R, B, C], per-row CE [R, B])"""
+        [R, B, C], per-row CE [R, B]).  `robust`: a GroupDRO state with q [R, G] over the groups of `groups` -- the group-DRO step of
+        every replica; q is updated in place and the robust losses take the means' place"""
+        if robust is not None and (not isinstance(robust, GroupDRO) or robust.q.dim() != 2):
+            raise TypeError("SweepAdapters.step: robust must be a GroupDRO state built with replicas=R")
         out = ops.adapter_sweep_step(table, idx, labels, groups, self._call_args(), self.ebd_weight, self.text(which), self.temperature, lrs,
-                                     momentum, weight_decay, self.first_step, counts, loss_sum, counted)
+                                     momentum, weight_decay, self.first_step, counts, loss_sum, counted,
+                                     robust=None if robust is None else (robust.q, robust.step_size))
         self.first_step = False
         return out
 

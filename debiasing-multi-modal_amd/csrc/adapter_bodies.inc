@@ -522,6 +522,77 @@ __device__ __forceinline__ void ce_bwd_row(const float* __restrict__ z, float in
     }
 }
 
+// ---- online group DRO (Sagawa et al. 2020): the group reduction and the update of q, one workgroup of 256 threads -------------
+// Row b belongs to group groups[row], row = b, or idx[b] clamped into a table of n_tab rows when `idx` is given; a group id
+// outside [0, G) belongs to no bucket (-1).
+constexpr int GDRO_MAXG = 8;
+
+__device__ __forceinline__ int gdro_group(const long long* __restrict__ groups, const long long* __restrict__ idx, long long n_tab, int b, int G) {
+    const long long g = groups[idx ? table_row(idx, b, n_tab) : (long long)b];
+    return (g >= 0 && g < G) ? (int)g : -1;
+}
+
+// n_g, L_g = mean of loss_rows over group g (0 for an absent group), m = max L_g over the groups present,
+// q'_g = q_g exp(eta (L_g - m)), q = q' / sum q', weight of a row of group g = q_g / n_g (0 for an absent group), robust loss =
+// sum_g q_g L_g.  Sums in float64 in a fixed order: thread t adds rows t, t + 256, ... in row order, then an LDS tree over the
+// 256 threads; the G-element arithmetic is thread 0's, in float64.  stats [3][G]: the row weights | L_g | n_g.  q_in may be q_out
+// (every q_in is read before any q_out is written, by the same thread).
+__device__ __forceinline__ void gdro_weights_body(const float* __restrict__ loss_rows, const long long* __restrict__ groups,
+                                                  const long long* __restrict__ idx, long long n_tab, const float* q_in, float* q_out,
+                                                  float* __restrict__ stats, float* __restrict__ robust_loss, int B, int G, float eta) {
+    __shared__ double sred[GDRO_MAXG][256];
+    __shared__ int nred[GDRO_MAXG][256];
+    const int t = threadIdx.x;
+    double s[GDRO_MAXG];
+    int n[GDRO_MAXG];
+#pragma unroll
+    for (int k = 0; k < GDRO_MAXG; ++k) { s[k] = 0.0; n[k] = 0; }
+    for (int b = t; b < B; b += 256) {
+        const int g = gdro_group(groups, idx, n_tab, b, G);
+        const double l = (double)loss_rows[b];
+#pragma unroll
+        for (int k = 0; k < GDRO_MAXG; ++k)
+            if (k == g) { s[k] += l; n[k] += 1; }
+    }
+#pragma unroll
+    for (int k = 0; k < GDRO_MAXG; ++k) { sred[k][t] = s[k]; nred[k][t] = n[k]; }
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+#pragma unroll
+            for (int k = 0; k < GDRO_MAXG; ++k) { sred[k][t] += sred[k][t + o]; nred[k][t] += nred[k][t + o]; }
+        }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    double L[GDRO_MAXG], qn[GDRO_MAXG];
+    double m = 0.0, sum = 0.0, rl = 0.0;
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < GDRO_MAXG; ++k) {
+        const int nk = k < G ? nred[k][0] : 0;
+        n[k] = nk;
+        L[k] = nk ? sred[k][0] / (double)nk : 0.0;
+        if (nk && (!any || L[k] > m)) { m = L[k]; any = true; }
+    }
+#pragma unroll
+    for (int k = 0; k < GDRO_MAXG; ++k) {
+        qn[k] = k < G ? (double)q_in[k] * exp((double)eta * (L[k] - m)) : 0.0;
+        sum += qn[k];
+    }
+#pragma unroll
+    for (int k = 0; k < GDRO_MAXG; ++k)
+        if (k < G) {
+            const float qf = (float)(qn[k] / sum);
+            q_out[k] = qf;
+            stats[k] = n[k] ? qf / (float)n[k] : 0.f;
+            stats[G + k] = (float)L[k];
+            stats[2 * G + k] = (float)n[k];
+            rl += (double)qf * L[k];
+        }
+    *robust_loss = (float)rl;
+}
+
 // ---- multi-tensor SGD with momentum: one tensor's update (n elements; ns > 1: g holds ns partial gradients n apart, summed here
 // in order, grad_reduce_body's order) -------------------------------------------------------------------------------------
 __device__ __forceinline__ void sgd_body(const dim3 bi, const dim3 gd, float* p, const float* g, float* m, const long long n, const int ns, float lr,

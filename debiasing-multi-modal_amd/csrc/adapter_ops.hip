@@ -205,6 +205,27 @@ __global__ __launch_bounds__(256) void l2norm_sim_ce_bwd_kernel(
     ce_bwd_row<CMAX>(z, inv_norm[row], w_new, tn, lgv, labels, dlogits, invT, gscale, dz, row, lane, D4, C, row);
 }
 
+// group DRO: the row's weight is its group's entry of the weight vector (gdro_weights_body), 0 for a group id outside [0, G)
+template <int CMAX>
+__global__ __launch_bounds__(256) void l2norm_sim_ce_bwd_w_kernel(
+    const float* __restrict__ z, const float* __restrict__ inv_norm, float w_new, const float* __restrict__ tn,
+    const float* __restrict__ logits, const long long* __restrict__ labels, const long long* __restrict__ groups,
+    const float* __restrict__ weights, int G, float invT, float* __restrict__ dz, int B, int D4, int C) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B) return;
+    float lgv[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) lgv[c] = (c < C) ? logits[(long long)row * C + c] : -INFINITY;
+    const int g = gdro_group(groups, nullptr, 0, row, G);
+    ce_bwd_row<CMAX>(z, inv_norm[row], w_new, tn, lgv, labels, nullptr, invT, g >= 0 ? weights[g] : 0.f, dz, row, lane, D4, C, row);
+}
+
+__global__ __launch_bounds__(256) void gdro_weights_kernel(const float* __restrict__ loss_rows, const long long* __restrict__ groups,
+                                                           const float* q_in, float* q_out, float* __restrict__ stats,
+                                                           float* __restrict__ robust_loss, int B, int G, float eta) {
+    gdro_weights_body(loss_rows, groups, nullptr, 0, q_in, q_out, stats, robust_loss, B, G, eta);
+}
+
 // the one-call step: forward and backward of a row in ONE launch (both are row-local; the logits stay in registers).  Same
 // statements as the two kernels above, so the results are the same bits.
 template <int CMAX>
@@ -465,6 +486,35 @@ extern "C" int dbmm_l2norm_sim_ce_bwd(const float* z, const float* inv_norm, flo
     return DBMM_OK;
 }
 
+extern "C" int dbmm_group_dro_weights(const float* loss_rows, const int64_t* groups, const float* q_in, float* q_out, float* weights,
+                                      float* robust_loss, int64_t B, int64_t G, float eta, void* stream) {
+    if (!loss_rows || !groups || !q_in || !q_out || !weights || !robust_loss) return DBMM_E_ARG;
+    if (G < 1 || G > GDRO_MAXG || B < 2 || B > INT32_MAX) return DBMM_E_SHAPE;
+    hipLaunchKernelGGL(gdro_weights_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_rows, (const long long*)groups, q_in, q_out, weights,
+                       robust_loss, (int)B, (int)G, eta);
+    DBMM_CHECK_LAUNCH();
+    return DBMM_OK;
+}
+
+extern "C" int dbmm_l2norm_sim_ce_bwd_weighted(const float* z, const float* inv_norm, float ebd_weight, int blended, const float* tn,
+                                               const float* logits, const int64_t* labels, const int64_t* groups, const float* weights,
+                                               int64_t G, float temperature, float* dz, int64_t B, int64_t D, int64_t C, void* stream) {
+    if (!z || !inv_norm || !tn || !dz || !logits || !labels || !groups || !weights) return DBMM_E_ARG;
+    if (G < 1 || G > GDRO_MAXG || B < 2 || D <= 0 || (D & 3) || C <= 0 || C > 8 || B > INT32_MAX) return DBMM_E_SHAPE;
+    if (!dbmm_aligned16(z) || !dbmm_aligned16(tn) || !dbmm_aligned16(dz)) return DBMM_E_ALIGN;
+    const float w_new = blended ? (1.f - ebd_weight) : 1.f;
+    const dim3 grid((unsigned)((B + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+    if (C <= 4)
+        hipLaunchKernelGGL(l2norm_sim_ce_bwd_w_kernel<4>, grid, dim3(256), 0, s, z, inv_norm, w_new, tn, logits, (const long long*)labels,
+                           (const long long*)groups, weights, (int)G, 1.f / temperature, dz, (int)B, (int)(D / 4), (int)C);
+    else
+        hipLaunchKernelGGL(l2norm_sim_ce_bwd_w_kernel<8>, grid, dim3(256), 0, s, z, inv_norm, w_new, tn, logits, (const long long*)labels,
+                           (const long long*)groups, weights, (int)G, 1.f / temperature, dz, (int)B, (int)(D / 4), (int)C);
+    DBMM_CHECK_LAUNCH();
+    return DBMM_OK;
+}
+
 // forward + backward of the cosine-logits / CE head in one launch (the one-call step): logits, per-row losses, dz
 static int ce_fwdbwd(const float* z, const float* z_old, float ebd_weight, const float* tn, const int64_t* labels, float temperature,
                      float* logits, float* loss_rows, float* dz, int64_t B, int64_t D, int64_t C, void* stream) {
@@ -556,16 +606,17 @@ extern "C" size_t dbmm_workspace_bytes_adapter_train_step(int64_t B, int64_t D, 
     return train_step_floats(B, D, H, with_old) * sizeof(float);
 }
 
-extern "C" int dbmm_adapter_train_step(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
-                                       float* beta, float* rmean, float* rvar, int64_t* nbt, float* w2, float* b2,
-                                       float* m_w1, float* m_b1, float* m_gamma, float* m_beta, float* m_w2,
-                                       float* m_b2, const float* o_w1, const float* o_b1, const float* o_gamma,
-                                       const float* o_beta, float* o_rmean, float* o_rvar, int64_t* o_nbt,
-                                       const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
-                                       float temperature, float lr, float momentum, float weight_decay,
-                                       int first_step, float* logits, float* loss_rows, float* loss_mean, int64_t B,
-                                       int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
-                                       void* stream) {
+// `groups` given: the group-DRO step (q [G] updated in place, loss_mean = the robust loss); else the ERM step
+static int train_step_impl(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
+                           float* beta, float* rmean, float* rvar, int64_t* nbt, float* w2, float* b2,
+                           float* m_w1, float* m_b1, float* m_gamma, float* m_beta, float* m_w2,
+                           float* m_b2, const float* o_w1, const float* o_b1, const float* o_gamma,
+                           const float* o_beta, float* o_rmean, float* o_rvar, int64_t* o_nbt,
+                           const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
+                           float temperature, float lr, float momentum, float weight_decay,
+                           int first_step, float* logits, float* loss_rows, float* loss_mean, const int64_t* groups, float* q, float eta,
+                           int64_t G, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
+                           void* stream) {
     if (!x || !labels || !w1 || !b1 || !gamma || !beta || !rmean || !rvar || !w2 || !b2 || !m_w1 || !m_b1 ||
         !m_gamma || !m_beta || !m_w2 || !m_b2 || !tn || !logits || !loss_rows || !loss_mean || !workspace)
         return DBMM_E_ARG;
@@ -609,7 +660,17 @@ extern "C" int dbmm_adapter_train_step(const float* x, const int64_t* labels, fl
     // mean of the losses rides in a spare block of the next launch, the sums of the batch-split dW1 / db1 partials in the SGD
     // launch -- the same statements as the stand-alone launches the autograd path uses, hence the same bits
     const bool fast = dbmm_adapter_fast_shape(B, D, H) && dbmm_opt(OPT_ADAPTER_STEP_FUSED) && dbmm_aligned16(x);
-    if (fast) {
+    if (groups) {
+        // group DRO: a row's weight needs the whole batch's losses, so the head is three launches -- forward rows, the group
+        // reduction + q update (one workgroup), weighted backward rows; the robust loss is written by the second, so the backward's
+        // spare loss-mean block is not launched.  The [3][G] statistics live at the start of the backward scratch (unused until then).
+        rc = dbmm_l2norm_sim_ce_fwd(z, oz, ebd_weight, tn, labels, temperature, logits, loss_rows, nullptr, nullptr, inv_norm, B, D, C, stream);
+        if (rc) return rc;
+        rc = dbmm_group_dro_weights(loss_rows, groups, q, q, bws, loss_mean, B, G, eta, stream);
+        if (rc) return rc;
+        rc = dbmm_l2norm_sim_ce_bwd_weighted(z, inv_norm, ebd_weight, with_old, tn, logits, labels, groups, bws, G, temperature, dz, B, D, C, stream);
+        if (rc) return rc;
+    } else if (fast) {
         if ((D & 3) || C <= 0 || C > 8) return DBMM_E_SHAPE;
         rc = ce_fwdbwd(z, oz, ebd_weight, tn, labels, temperature, logits, loss_rows, dz, B, D, C, stream);
         if (rc) return rc;
@@ -628,7 +689,7 @@ extern "C" int dbmm_adapter_train_step(const float* x, const int64_t* labels, fl
         const float *dw1part = nullptr, *db1part = nullptr;
         int nsplit = 1;
         rc = dbmm_adapter_bwd_fast(x, dz, h, mean, invstd, r, gamma, beta, w2, dw1, db1, dgamma, dbeta, dw2, db2, dh, dh + B * H, B, D,
-                                   (hipStream_t)stream, &dw1part, &db1part, &nsplit, loss_rows, loss_mean);
+                                   (hipStream_t)stream, &dw1part, &db1part, &nsplit, groups ? nullptr : loss_rows, groups ? nullptr : loss_mean);
         if (rc) return rc;
         gs[0] = dw1part; gs[1] = db1part;
         const int nsp[6] = {nsplit, nsplit, 1, 1, 1, 1};
@@ -638,6 +699,39 @@ extern "C" int dbmm_adapter_train_step(const float* x, const int64_t* labels, fl
                           dbmm_workspace_bytes_adapter_bwd(B, D, H), stream);
     if (rc) return rc;
     return dbmm_sgd_momentum(6, ps, gs, ms, ns, lr, momentum, weight_decay, first_step, stream);
+}
+
+extern "C" int dbmm_adapter_train_step(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
+                                       float* beta, float* rmean, float* rvar, int64_t* nbt, float* w2, float* b2,
+                                       float* m_w1, float* m_b1, float* m_gamma, float* m_beta, float* m_w2,
+                                       float* m_b2, const float* o_w1, const float* o_b1, const float* o_gamma,
+                                       const float* o_beta, float* o_rmean, float* o_rvar, int64_t* o_nbt,
+                                       const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
+                                       float temperature, float lr, float momentum, float weight_decay,
+                                       int first_step, float* logits, float* loss_rows, float* loss_mean, int64_t B,
+                                       int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    return train_step_impl(x, labels, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2, o_w1, o_b1, o_gamma,
+                           o_beta, o_rmean, o_rvar, o_nbt, o_w2, o_b2, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, logits,
+                           loss_rows, loss_mean, nullptr, nullptr, 0.f, 0, B, D, H, C, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dbmm_adapter_train_step_gdro(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
+                                            float* beta, float* rmean, float* rvar, int64_t* nbt, float* w2, float* b2,
+                                            float* m_w1, float* m_b1, float* m_gamma, float* m_beta, float* m_w2,
+                                            float* m_b2, const float* o_w1, const float* o_b1, const float* o_gamma,
+                                            const float* o_beta, float* o_rmean, float* o_rvar, int64_t* o_nbt,
+                                            const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
+                                            float temperature, float lr, float momentum, float weight_decay,
+                                            int first_step, float* logits, float* loss_rows, float* robust_loss,
+                                            const int64_t* groups, float* q, float eta, int64_t G, int64_t B,
+                                            int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+    if (!groups || !q) return DBMM_E_ARG;
+    if (G < 1 || G > GDRO_MAXG) return DBMM_E_SHAPE;
+    return train_step_impl(x, labels, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2, o_w1, o_b1, o_gamma,
+                           o_beta, o_rmean, o_rvar, o_nbt, o_w2, o_b2, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, logits,
+                           loss_rows, robust_loss, groups, q, eta, G, B, D, H, C, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dbmm_version(void) { return 101; }

@@ -11,7 +11,8 @@
 //     loss mean adds `(double)loss_mean * B` to the replica's float64 epoch loss sum (one thread, one add per step);
 //   * the per-replica learning rates reach the SGD launch by value.
 // Launches of a step: fc1 partials, BN statistics, fc2 [the same three for a frozen old adapter], CE forward + backward, bwd2,
-// BN backward, bwd1, SGD = 8 (11), whatever R is.  Evaluation: fc1 partials, reduce, fc2 [x 2], CE forward, loss sum = 5 (8).
+// BN backward, bwd1, SGD = 8 (11), whatever R is; the group-DRO step (dbmm_adapter_sweep_step_gdro) has CE forward, group weights +
+// q update, weighted CE backward in place of the one CE launch = 10 (13).  Evaluation: fc1 partials, reduce, fc2 [x 2], CE forward, loss sum = 5 (8).
 // No float atomics, no order that depends on timing.
 #include "common.h"
 
@@ -119,6 +120,68 @@ __global__ __launch_bounds__(256) void sweep_ce_fwdbwd_kernel(float* __restrict_
     }
 }
 
+// group-DRO train step, first of the head's three launches: forward of row b of replica r (l2norm_sim_ce_fwd_kernel's call, 1 / ||z||
+// kept for the backward) + the group counters
+template <int CMAX>
+__global__ __launch_bounds__(256) void sweep_ce_fwd_train_kernel(float* __restrict__ ws, long long ws_stride, long long zoff, long long ozoff,
+                                                                 long long invoff, float w_old, const float* __restrict__ tn,
+                                                                 const long long* __restrict__ labels, const long long* __restrict__ groups,
+                                                                 const long long* __restrict__ idx, long long n_tab, float invT,
+                                                                 float* __restrict__ logits, float* __restrict__ loss_rows,
+                                                                 unsigned long long* __restrict__ counts, int G, int B, int D4, int C) {
+    __shared__ unsigned int sc[64][2];
+    const int r = blockIdx.y;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (counts) {
+        if (threadIdx.x < 64) { sc[threadIdx.x][0] = 0; sc[threadIdx.x][1] = 0; }
+        __syncthreads();
+    }
+    if (row < B) {
+        float* w = ws + r * ws_stride;
+        const long long lrow = table_row(idx + (long long)r * B, row, n_tab);
+        float lg[CMAX], inv;
+        ce_fwd_row<CMAX>(w + zoff, ozoff >= 0 ? w + ozoff : nullptr, w_old, tn, labels, invT, logits + (long long)r * B * C, loss_rows + (long long)r * B,
+                         nullptr, w + invoff, row, lane, D4, C, lg, inv, lrow);
+        if (counts && lane == 0) count_row<CMAX>(lg, C, labels[lrow], groups[lrow], G, sc);
+    }
+    if (counts) {
+        __syncthreads();
+        flush_counts(sc, counts + (long long)r * G * 2, G);
+    }
+}
+
+// second: replica r's group reduction and q update (gdro_weights_kernel's call); loss_mean[r] = the robust loss, and the thread
+// that wrote it adds it, as a double times the batch rows, to the epoch's loss sum
+__global__ __launch_bounds__(256) void sweep_gdro_weights_kernel(float* __restrict__ ws, long long ws_stride, long long gwoff,
+                                                                 const float* __restrict__ loss_rows, const long long* __restrict__ groups,
+                                                                 const long long* __restrict__ idx, long long n_tab, float* q,
+                                                                 float* __restrict__ loss_mean, double* __restrict__ loss_sum, int B, int G, float eta) {
+    const int r = blockIdx.x;
+    gdro_weights_body(loss_rows + (long long)r * B, groups, idx + (long long)r * B, n_tab, q + r * G, q + r * G, ws + r * ws_stride + gwoff, loss_mean + r,
+                      B, G, eta);
+    if (loss_sum && threadIdx.x == 0) loss_sum[r] += (double)loss_mean[r] * (double)B;
+}
+
+// third: weighted backward of row b of replica r (l2norm_sim_ce_bwd_w_kernel's call)
+template <int CMAX>
+__global__ __launch_bounds__(256) void sweep_ce_bwd_w_kernel(float* __restrict__ ws, long long ws_stride, long long zoff, long long invoff, long long gwoff,
+                                                             long long dzoff, float w_new, const float* __restrict__ tn,
+                                                             const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                             const long long* __restrict__ groups, const long long* __restrict__ idx, long long n_tab,
+                                                             int G, float invT, int B, int D4, int C) {
+    const int r = blockIdx.y;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B) return;
+    float* w = ws + r * ws_stride;
+    const long long* idr = idx + (long long)r * B;
+    float lgv[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) lgv[c] = (c < C) ? logits[((long long)r * B + row) * C + c] : -INFINITY;
+    const int g = gdro_group(groups, idr, n_tab, row, G);
+    ce_bwd_row<CMAX>(w + zoff, (w + invoff)[row], w_new, tn, lgv, labels, nullptr, invT, g >= 0 ? (w + gwoff)[g] : 0.f, w + dzoff, row, lane, D4, C,
+                     table_row(idr, row, n_tab));
+}
+
 // eval: l2norm_sim_ce_fwd_kernel's call for row b of replica r + the group counters; every replica scores the same rows
 template <int CMAX>
 __global__ __launch_bounds__(256) void sweep_ce_fwd_kernel(float* __restrict__ ws, long long ws_stride, long long zoff, long long ozoff, float w_old,
@@ -165,7 +228,7 @@ __global__ __launch_bounds__(256) void sweep_bwd2_kernel(float* __restrict__ ws,
     const int r = blockIdx.y;
     float* w = ws + r * ws_stride;
     bwd2_body(dim3(blockIdx.x, 0, 0), dim3(gridDim.x, 1, 1), w + dzoff, w + roff, w2 + (long long)r * D * 128, w + dw2p, w + db2p, w + drp, B, D, NS, RB,
-              loss_rows + (long long)r * B, loss_mean + r);
+              loss_rows + (long long)r * B, loss_mean ? loss_mean + r : nullptr);
     // losses.update(loss.item(), bsz) on the device: the thread that wrote the mean adds it, as a double times the batch rows
     if (loss_sum && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) loss_sum[r] += (double)loss_mean[r] * (double)B;
 }
@@ -278,11 +341,13 @@ extern "C" size_t dbmm_workspace_bytes_adapter_sweep_eval(int64_t R, int64_t B, 
     return (size_t)R * (size_t)eval_layout(B, D, with_old).total * sizeof(float);
 }
 
-extern "C" int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B, const int64_t* labels,
-                                       const int64_t* groups, void* const* params, float* const* bufs, void* const* old, float ebd_weight,
-                                       const float* tn, float temperature, const float* lr, float momentum, float weight_decay, int first_step,
-                                       float* logits, float* loss_rows, float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted,
-                                       int64_t R, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes, void* stream) {
+// `q` given: the group-DRO step of every replica (q [R][G] updated in place, loss_mean = the robust losses); else the ERM step
+static int sweep_step_impl(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B, const int64_t* labels,
+                           const int64_t* groups, void* const* params, float* const* bufs, void* const* old, float ebd_weight,
+                           const float* tn, float temperature, const float* lr, float momentum, float weight_decay, int first_step,
+                           float* logits, float* loss_rows, float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted,
+                           float* q, float eta, int64_t R, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
+                           void* stream) {
     if (!table || !idx || !labels || !groups || !tn || !lr || !logits || !loss_rows || !loss_mean || !counts || !loss_sum || !workspace || !bufs)
         return DBMM_E_ARG;
     if (!stack_ok(params) || (old && !stack_ok(old))) return DBMM_E_ARG;
@@ -321,7 +386,33 @@ extern "C" int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const
                            iB, iD);
         DBMM_CHECK_LAUNCH();
     }
-    {
+    if (q) {
+        // group DRO: forward rows, group reduction + q update (one workgroup per replica), weighted backward rows.  1 / ||z|| and the
+        // [3][G] statistics live in the dh region, which nothing uses before the BatchNorm backward
+        const float w_new = with_old ? (1.f - ebd_weight) : 1.f, invT = 1.f / temperature;
+        unsigned long long* cnt = counted ? (unsigned long long*)counts : nullptr;
+        const dim3 grid((unsigned)((B + 3) / 4), iR);
+        const long long invoff = L.dh, gwoff = L.dh + (long long)up4(B);
+        const long long* lab = (const long long*)labels;
+        const long long* grp = (const long long*)groups;
+        if (C <= 4)
+            hipLaunchKernelGGL(sweep_ce_fwd_train_kernel<4>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, invoff, ebd_weight, tn, lab, grp, idxl,
+                               (long long)n_rows, invT, logits, loss_rows, cnt, (int)G, iB, (int)(D / 4), (int)C);
+        else
+            hipLaunchKernelGGL(sweep_ce_fwd_train_kernel<8>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, invoff, ebd_weight, tn, lab, grp, idxl,
+                               (long long)n_rows, invT, logits, loss_rows, cnt, (int)G, iB, (int)(D / 4), (int)C);
+        DBMM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(sweep_gdro_weights_kernel, dim3(iR), dim3(256), 0, s, ws, wst, gwoff, (const float*)loss_rows, grp, idxl, (long long)n_rows, q,
+                           loss_mean, counted ? loss_sum : nullptr, iB, (int)G, eta);
+        DBMM_CHECK_LAUNCH();
+        if (C <= 4)
+            hipLaunchKernelGGL(sweep_ce_bwd_w_kernel<4>, grid, dim3(256), 0, s, ws, wst, L.z, invoff, gwoff, L.dz, w_new, tn, (const float*)logits, lab, grp,
+                               idxl, (long long)n_rows, (int)G, invT, iB, (int)(D / 4), (int)C);
+        else
+            hipLaunchKernelGGL(sweep_ce_bwd_w_kernel<8>, grid, dim3(256), 0, s, ws, wst, L.z, invoff, gwoff, L.dz, w_new, tn, (const float*)logits, lab, grp,
+                               idxl, (long long)n_rows, (int)G, invT, iB, (int)(D / 4), (int)C);
+        DBMM_CHECK_LAUNCH();
+    } else {
         const float w_new = with_old ? (1.f - ebd_weight) : 1.f, gs = 1.f / (float)B;
         unsigned long long* cnt = counted ? (unsigned long long*)counts : nullptr;
         const dim3 grid((unsigned)((B + 3) / 4), iR);
@@ -341,8 +432,9 @@ extern "C" int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const
     const long long drp = L.scratch, dw2p = drp + B * D, db2p = dw2p + (long long)NS * D * 128, dw1p = db2p + (long long)NS * D,
                     db1p = dw1p + (long long)NS * 128 * D;
     const int nbT = (int)((B + TB - 1) / TB);
-    hipLaunchKernelGGL(sweep_bwd2_kernel, dim3((unsigned)(D / 32 * NS + nbT * KS + 1), iR), dim3(256), 0, s, ws, wst, L.dz, L.r, (const float*)P.w2, dw2p,
-                       db2p, drp, iB, iD, NS, RB, (const float*)loss_rows, loss_mean, counted ? loss_sum : nullptr);
+    // (group DRO: the robust loss is already written and counted, so the spare loss-mean block is not launched)
+    hipLaunchKernelGGL(sweep_bwd2_kernel, dim3((unsigned)(D / 32 * NS + nbT * KS + (q ? 0 : 1)), iR), dim3(256), 0, s, ws, wst, L.dz, L.r, (const float*)P.w2,
+                       dw2p, db2p, drp, iB, iD, NS, RB, (const float*)loss_rows, q ? nullptr : loss_mean, (counted && !q) ? loss_sum : nullptr);
     DBMM_CHECK_LAUNCH();
     const long long nw4 = D * 128 / 4, nb4 = D / 4;
     hipLaunchKernelGGL(sweep_bn_bwd_kernel, dim3((unsigned)(32 + (nw4 + nb4 + 255) / 256), iR), dim3(256), 0, s, ws, wst, drp, KS, L.h, L.mean, L.invstd,
@@ -366,6 +458,29 @@ extern "C" int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const
     hipLaunchKernelGGL(sweep_sgd_kernel, dim3((unsigned)bx, 6, iR), dim3(256), 0, s, a, (const float*)ws, wst, momentum, weight_decay, first_step);
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
+}
+
+extern "C" int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B, const int64_t* labels,
+                                       const int64_t* groups, void* const* params, float* const* bufs, void* const* old, float ebd_weight,
+                                       const float* tn, float temperature, const float* lr, float momentum, float weight_decay, int first_step,
+                                       float* logits, float* loss_rows, float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted,
+                                       int64_t R, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes, void* stream) {
+    return sweep_step_impl(table, n_rows, idx, idx_R, idx_B, labels, groups, params, bufs, old, ebd_weight, tn, temperature, lr, momentum, weight_decay,
+                           first_step, logits, loss_rows, loss_mean, counts, loss_sum, G, counted, nullptr, 0.f, R, B, D, H, C, workspace, workspace_bytes,
+                           stream);
+}
+
+extern "C" int dbmm_adapter_sweep_step_gdro(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B, const int64_t* labels,
+                                            const int64_t* groups, void* const* params, float* const* bufs, void* const* old, float ebd_weight,
+                                            const float* tn, float temperature, const float* lr, float momentum, float weight_decay, int first_step,
+                                            float* logits, float* loss_rows, float* robust_loss, int64_t* counts, double* loss_sum, int64_t G,
+                                            int counted, float* q, float eta, int64_t R, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    if (!q) return DBMM_E_ARG;
+    if (G < 1 || G > GDRO_MAXG) return DBMM_E_SHAPE;
+    return sweep_step_impl(table, n_rows, idx, idx_R, idx_B, labels, groups, params, bufs, old, ebd_weight, tn, temperature, lr, momentum, weight_decay,
+                           first_step, logits, loss_rows, robust_loss, counts, loss_sum, G, counted, q, eta, R, B, D, H, C, workspace, workspace_bytes,
+                           stream);
 }
 
 extern "C" int dbmm_adapter_sweep_eval(const float* table, int64_t n_rows, const int64_t* idx, int64_t row0, const int64_t* labels,

@@ -640,7 +640,7 @@ def colsum(x):
     return out
 
 
-def l2norm_sim_ce_fwd(z, tn, temperature, labels=None, z_old=None, ebd_weight=0.5, want_loss=True, want_pred=False):
+def l2norm_sim_ce_fwd(z, tn, temperature, labels=None, z_old=None, ebd_weight=0.5, want_loss=True, want_pred=False, want_mean=True):
     require_cuda(z, tn)
     _f32c(z)
     B, D = z.shape
@@ -651,7 +651,7 @@ def l2norm_sim_ce_fwd(z, tn, temperature, labels=None, z_old=None, ebd_weight=0.
     loss_rows = loss_mean = pred = None
     if labels is not None and want_loss:
         loss_rows = _empty((B,), device=dev, dtype=torch.float32)
-        loss_mean = _empty((), device=dev, dtype=torch.float32)
+        loss_mean = _empty((), device=dev, dtype=torch.float32) if want_mean else None      # (the mean is a launch of its own)
     if want_pred:
         pred = _empty((B,), device=dev, dtype=torch.int64)
     check(_lib.lib().dbmm_l2norm_sim_ce_fwd(ptr(z), ptr(z_old), float(ebd_weight), ptr(tn), ptr(labels),
@@ -668,6 +668,60 @@ def l2norm_sim_ce_bwd(z, inv_norm, tn, temperature, logits=None, labels=None, dl
     check(_lib.lib().dbmm_l2norm_sim_ce_bwd(ptr(z), ptr(inv_norm), float(ebd_weight), int(blended), ptr(tn), ptr(logits),
                                             ptr(labels), ptr(dlogits), float(temperature), float(grad_scale), ptr(dz),
                                             B, D, C, stream()), "l2norm_sim_ce_bwd")
+    return dz
+
+
+GDRO_MAX_GROUPS = 8
+
+
+def _gdro_operands(groups, q, B, R=None):
+    """the group ids of a batch and the group-DRO state q ([G], or [R, G] for R replicas) as the library will index them"""
+    require_cuda(groups, q)
+    if groups.dtype != torch.int64 or not groups.is_contiguous():
+        raise _lib.DbmmError("group DRO: groups must be a contiguous int64 tensor")
+    if B is not None:
+        _sized("group DRO groups", groups, B)
+    _f32c(q)
+    if q.dim() != (1 if R is None else 2) or (R is not None and q.shape[0] != R) or not 1 <= q.shape[-1] <= GDRO_MAX_GROUPS:
+        want = "[G]" if R is None else f"[{R}, G]"
+        raise _lib.DbmmError(f"group DRO: q must be a float32 {want} tensor with 1 <= G <= {GDRO_MAX_GROUPS}, got {tuple(q.shape)}")
+    return q.shape[-1]
+
+
+def group_dro_weights(loss_rows, groups, q, eta, q_out=None):
+    """one online group-DRO update on a batch's per-row CE (dbmm_group_dro_weights): `q` [G] is updated in place, or left alone and
+    the new state written to `q_out`.  Returns (robust loss (0-dim), stats [3, G]: row weights q_g / n_g | group means L_g | n_g)."""
+    require_cuda(loss_rows)
+    _f32c(loss_rows)
+    B = loss_rows.shape[0]
+    G = _gdro_operands(groups, q, B)
+    if q_out is None:
+        q_out = q
+    else:
+        require_cuda(q_out)
+        _f32c(q_out)
+        _sized("group DRO q_out", q_out, G)
+    stats = _empty((3, G), device=loss_rows.device, dtype=torch.float32)
+    robust = _empty((), device=loss_rows.device, dtype=torch.float32)
+    check(_lib.lib().dbmm_group_dro_weights(ptr(loss_rows), ptr(groups), ptr(q), ptr(q_out), ptr(stats), ptr(robust), B, G, float(eta),
+                                            stream()), "group_dro_weights")
+    return robust, stats
+
+
+def l2norm_sim_ce_bwd_weighted(z, inv_norm, tn, temperature, logits, labels, groups, weights, blended=False, ebd_weight=0.5):
+    """dz of sum_b weights[groups[b]] CE_b (dbmm_l2norm_sim_ce_bwd_weighted); `weights` [G] = row 0 of group_dro_weights' stats"""
+    require_cuda(z, inv_norm, tn, logits, labels, groups, weights)
+    _f32c(z); _f32c(weights)
+    B, D = z.shape
+    C = tn.shape[0]
+    _sized("l2norm_sim_ce_bwd_weighted inv_norm", inv_norm, B)
+    _sized("l2norm_sim_ce_bwd_weighted logits", logits, B * C)
+    _sized("l2norm_sim_ce_bwd_weighted labels", labels, B)
+    G = _gdro_operands(groups, weights, B)
+    dz = _empty(tuple(z.shape), device=z.device, dtype=z.dtype)
+    check(_lib.lib().dbmm_l2norm_sim_ce_bwd_weighted(ptr(z), ptr(inv_norm), float(ebd_weight), int(blended), ptr(tn), ptr(logits), ptr(labels),
+                                                     ptr(groups), ptr(weights), G, float(temperature), ptr(dz), B, D, C, stream()),
+          "l2norm_sim_ce_bwd_weighted")
     return dz
 
 
@@ -735,14 +789,15 @@ def group_loss_sum(loss_rows, g, sums):
 _step_ws = {}
 
 
-def adapter_step_launches(B, D, H, with_old=False):
+def adapter_step_launches(B, D, H, with_old=False, robust=False):
     """kernel launches of one dbmm_adapter_train_step call on the purpose-built kernels (csrc/adapter_step.hip): forward 3
     (K-split fc1, BatchNorm statistics, BatchNorm + ReLU + fc2; 3 more for a frozen old adapter), cosine logits + CE forward
     and backward in one, backward 3 (dW2 / dr + the loss mean, BatchNorm backward + dW2 sums, dW1), SGD (+ dW1 sums); None for
-    shapes that take the general GEMM kernel (H != 128 or D % 128 != 0)"""
+    shapes that take the general GEMM kernel (H != 128 or D % 128 != 0).  `robust` (dbmm_adapter_train_step_gdro): 2 more -- the
+    head is forward rows, group reduction + q update, weighted backward rows, and the loss needs no launch of the backward"""
     if H != 128 or D % 128 or not get_option("adapter_step_fused"):
         return None
-    return 8 + (3 if with_old else 0)
+    return 8 + (3 if with_old else 0) + (2 if robust else 0)
 
 
 def adapter_step_args(new, bufs, old):
@@ -753,8 +808,10 @@ def adapter_step_args(new, bufs, old):
     return tuple(ptr(t) for t in list(new) + list(bufs)) + (tuple(ptr(t) for t in old) if old is not None else (None,) * 9)
 
 
-def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step):
-    """one fused training-step body (dbmm_adapter_train_step); `args` from adapter_step_args()."""
+def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, robust=None):
+    """one fused training-step body (dbmm_adapter_train_step); `args` from adapter_step_args().  `robust` = (groups int64 [B], q
+    float32 [G], eta): the group-DRO step (dbmm_adapter_train_step_gdro) -- q is updated in place, the returned loss is the robust
+    loss."""
     if not (x.is_cuda and labels.is_cuda and tn.is_cuda):
         require_cuda(x, labels, tn)
     _f32c(x)
@@ -771,6 +828,16 @@ def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature
         _step_ws[key] = ws
     logits = _empty((B, C), device=dev, dtype=torch.float32)
     loss = _empty((B + 1,), device=dev, dtype=torch.float32)        # per-row losses, then their mean: one allocation
+    if robust is not None:
+        groups, q, eta = robust
+        G = _gdro_operands(groups, q, B)
+        rc = _lib.lib().dbmm_adapter_train_step_gdro(
+            x.data_ptr(), labels.data_ptr(), *args, float(ebd_weight), tn.data_ptr(), float(temperature), float(lr), float(momentum),
+            float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * B, groups.data_ptr(), q.data_ptr(),
+            float(eta), G, B, D, H, C, ws.data_ptr(), ws.numel() * 4, stream())
+        if rc:
+            check(rc, "adapter_train_step_gdro")
+        return loss[B], logits, loss[:B]
     rc = _lib.lib().dbmm_adapter_train_step(
         x.data_ptr(), labels.data_ptr(), *args, float(ebd_weight), tn.data_ptr(), float(temperature), float(lr), float(momentum),
         float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * B, B, D, H, C, ws.data_ptr(),
@@ -852,10 +919,12 @@ def _sweep_metrics(counts, loss_sum, R):
 
 
 def adapter_sweep_step(table, idx, labels, groups, args, ebd_weight, tn, temperature, lrs, momentum, weight_decay, first_step, counts, loss_sum,
-                       counted=True):
+                       counted=True, robust=None):
     """one training step of R replicas in the launches of one (dbmm_adapter_sweep_step): replica r trains on rows idx[r] of `table`
     ([N, D] fp32; labels / groups int64 [N]); `args` from adapter_sweep_args(); `lrs` R host floats; counts int64 [R, G, 2] and
-    loss_sum float64 [R] are accumulated in place when `counted`.  Returns (mean CE [R], logits [R, B, C], per-row CE [R, B])."""
+    loss_sum float64 [R] are accumulated in place when `counted`.  Returns (mean CE [R], logits [R, B, C], per-row CE [R, B]).
+    `robust` = (q float32 [R, G], eta): the group-DRO step of every replica (dbmm_adapter_sweep_step_gdro) over the groups of
+    `groups` (G = counts.shape[1] <= 8) -- q is updated in place, the robust losses take the means' place."""
     R, D, H = args["R"], args["D"], args["H"]
     if args["Bf"] is None:
         raise _lib.DbmmError("adapter sweep step: adapter_sweep_args() was built without momentum buffers")
@@ -877,6 +946,18 @@ def adapter_sweep_step(table, idx, labels, groups, args, ebd_weight, tn, tempera
     loss = _empty((R, B + 1), device=dev, dtype=torch.float32)          # [:, :B] would not be contiguous: rows first, then the R means
     loss = loss.view(-1)
     LR = (ctypes.c_float * R)(*[float(v) for v in lrs])
+    if robust is not None:
+        q, eta = robust
+        if _gdro_operands(groups, q, None, R) != G:
+            raise _lib.DbmmError(f"adapter sweep step: q {tuple(q.shape)} for counters of {G} groups")
+        rc = L.dbmm_adapter_sweep_step_gdro(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(),
+                                            args["P"], args["Bf"], args["O"], float(ebd_weight), tn.data_ptr(), float(temperature), LR,
+                                            float(momentum), float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(),
+                                            loss.data_ptr() + 4 * R * B, counts.data_ptr(), loss_sum.data_ptr(), G, int(counted), q.data_ptr(),
+                                            float(eta), R, B, D, H, C, ws.data_ptr(), ws.numel() * 4, stream())
+        if rc:
+            check(rc, "adapter_sweep_step_gdro")
+        return loss[R * B:], logits, loss[:R * B].view(R, B)
     rc = L.dbmm_adapter_sweep_step(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(),
                                    args["P"], args["Bf"], args["O"], float(ebd_weight), tn.data_ptr(), float(temperature), LR, float(momentum),
                                    float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * R * B,

@@ -117,15 +117,16 @@ def _pass_rows(p, r=0):
     return len(p.table) if p.rows is None else len(p.rows[r])
 
 
-def _train_passes(classifier, optimizer, target, passes, lr_hook):
+def _train_passes(classifier, optimizer, target, passes, lr_hook, robust=None, q_log=None):
     """The loader passes of one epoch of one run, on one pair of device accumulators with ONE host sync at the end.
     `lr_hook(step, n_steps)` runs before every step and restarts with each pass.  Returns (counters [G, 2] numpy, loss sum, the
-    epoch's row order)."""
+    epoch's row order).  `robust` (an adapter.GroupDRO state): every step is a group-DRO step over the table's group ids -- also on
+    the group-prompt passes --, the loss summed is the robust loss; `q_log` (a list) receives q after each pass."""
     classifier.train()
     dev = passes[0].table.device
     counts = torch.zeros((passes[0].table.n_groups, 2), dtype=torch.int64, device=dev)
     loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
-    order = []
+    order, qs = [], []
     for p in passes:
         batches = _epoch_batches(_pass_rows(p), p.batch_size, p.shuffle, None if p.rows is None else p.rows[0])
         for step, idx in enumerate(batches):
@@ -135,23 +136,32 @@ def _train_passes(classifier, optimizer, target, passes, lr_hook):
                 labels = groups
             if lr_hook is not None:
                 lr_hook(step, len(batches))
-            loss, logits, _ = classifier.train_step(emb, labels, optimizer, p.use_group)
+            if robust is not None:
+                loss, logits, _ = classifier.train_step(emb, labels, optimizer, p.use_group, robust=(robust, groups))
+            else:
+                loss, logits, _ = classifier.train_step(emb, labels, optimizer, p.use_group)
             if p.counted:
                 loss_sum += loss.double() * idx.numel()                  # losses.update(loss.item(), bsz)
                 adapter.group_counts(logits, labels, groups, p.table.n_groups, counts)
         order += batches
-    return counts.cpu().numpy(), loss_sum.item(), torch.cat(order).numpy()
+        if robust is not None:
+            qs.append(robust.q.clone())
+    c = counts.cpu().numpy()
+    if q_log is not None:
+        q_log.extend(q.cpu().numpy() for q in qs)
+    return c, loss_sum.item(), torch.cat(order).numpy()
 
 
 def train_epoch(table, classifier, optimizer, batch_size, target="class", use_group=False, indices=None,
-                shuffle=True, lr_hook=None, stats=None):
+                shuffle=True, lr_hook=None, stats=None, robust=None):
     """One epoch of train_one_epoch / train_reg_seq_one_epoch.  `indices` restricts the epoch to a
     subset (reg split, balanced indices); `lr_hook(step, n_steps)` runs before every step (the
     warm-up helpers).  Returns (loss average, accuracy, group accuracy dict) like the reference,
     computed from device-side accumulators with ONE host sync at the end.  `stats` (a dict) receives
-    the integer (n, correct) counters [G, 2] and the row order of the epoch."""
+    the integer (n, correct) counters [G, 2] and the row order of the epoch.  `robust`: an adapter.GroupDRO state -- the epoch
+    takes group-DRO steps and the loss average is that of the robust loss."""
     p = _Pass(table, None if indices is None else [indices], shuffle, batch_size, use_group, True)
-    c, loss_sum, order = _train_passes(classifier, optimizer, target, [p], lr_hook)
+    c, loss_sum, order = _train_passes(classifier, optimizer, target, [p], lr_hook, robust)
     if stats is not None:
         stats.update(counts=c, order=order)
     return _scores(table, c, loss_sum, _pass_rows(p))
@@ -244,7 +254,11 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
       the reg half: re-balanced per epoch by --balance_val from the global numpy RNG (also in stage 1, :920-921) and read by an
           un-shuffled loader with the adjusted batch size, else the reg loader itself (shuffled, batch_size_reg);
       every epoch: validate on the other half of the val split, keep the best worst-group model (strict `>`, :1001-1008), validate
-          on the test split (:1013-1016); finally the zero-shot class / spurious scores of the best model (:1037-1045).
+          on the test split (:1013-1016); finally the zero-shot class / spurious scores of the best model (:1037-1045);
+      opt.robust (a build-side addition; read with getattr, default off; step size opt.robust_step_size, default 0.01): every training
+          step of the adapter methods is a group-DRO step (Sagawa et al. 2020; adapter.GroupDRO) over the table's
+          group ids -- also on the group-prompt passes; q is per run, starts at 1 / G, starts over at the switch with the momentum, is
+          not part of the best model; a pass counts the robust loss; the train records carry q after each pass; linear_probing raises.
 
     Random streams are consumed like the reference does (global torch RNG: parameter initialisation and DataLoader orders; global
     numpy RNG: balance_val) through ex.streams.run(r, ...), so the same seeds give the same initial weights and batches.  Returns per
@@ -255,6 +269,9 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
     if method not in _METHODS:
         raise ValueError(f"the training schedule covers linear_probing and the adapter methods, not tl_method={method!r}")
     linear, seq, has_reg = method == "linear_probing", method.startswith("adapter_reg_seq"), method.startswith("adapter_reg")
+    robust = bool(getattr(opt, "robust", False))
+    if robust and linear:
+        raise ops.DbmmUnsupported("group DRO (opt.robust) covers the adapter methods; the linear probe's fused step has no weighted form")
     streams = ex.streams
     dev = train_table.device
     D = input_dim or train_table.embeddings.shape[1]
@@ -281,6 +298,8 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
     models = [streams.run(r, new_model) for r in range(R)]
     each(lambda r: record_init(r, models[r] if linear else models[r].adapter))
     lr1 = ex.start(models, dev)                                           # per run an optimiser, or what optim.py's helpers need of one
+    if robust:                                                            # per run a group distribution q = 1 / G; every training step is a group-DRO step
+        ex.start_robust(train_table.n_groups, getattr(opt, "robust_step_size", 0.01), dev)
     lr2 = None
     best_acc, best_epoch = [0] * R, [0] * R
     train_accs, val_accs, test_accs = [[] for _ in range(R)], [[] for _ in range(R)], [[] for _ in range(R)]
@@ -303,6 +322,8 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
                 fresh = [streams.run(r, adapter.Adapter, D, opt.adapter_feat_dim) for r in range(R)]
                 each(lambda r: record_init(r, fresh[r]))
             lr2 = ex.switch(fresh)
+            if robust:                                                    # a fresh optimiser: q starts over with the momentum
+                ex.dro.reset()
         if stage2:
             each(lambda r: O.adjust_learning_rate_reg(opts[r], lr2[r], epoch))
         lrs, warmup, warm_epoch = (lr2, O.warmup_learning_rate_reg, epoch - efl) if stage2 else (lr1, O.warmup_learning_rate, epoch)
@@ -323,6 +344,8 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
         n_rows = sum(_pass_rows(p) for p in passes if p.counted)
         for r in range(R):
             loss, acc, gacc = _scores(train_table, c[r], ls[r], n_rows)
+            if robust:                                                    # q after each pass of the epoch
+                extra = dict(extra, q=ex.q_log[r])
             rec(r, kind=kind, epoch=epoch, loss=loss, acc=acc, group_acc=gacc, counts=c[r], order=orders[r], **extra)
             train_accs[r].append(gacc)
         vc, vl = ex.evaluate(val_table, bs_eval, opt.train_target, val_idx)
@@ -381,10 +404,14 @@ class _SingleRun:
     def __init__(self, opt):
         self.opt = opt
         self.model = self.best = self.device = None
+        self.dro, self.q_log = None, None                                # group DRO: the run's state (not part of the best model)
 
     def start(self, models, device):
         self.model, self.device = models[0].to(device), device
         return [O.set_optimizer(self.opt, self.model)]
+
+    def start_robust(self, n_groups, step_size, device):
+        self.dro = adapter.GroupDRO(n_groups, step_size, device)
 
     def restore(self):
         self.model = deepcopy(self.best)
@@ -396,7 +423,9 @@ class _SingleRun:
         return [O.set_optimizer_reg(self.opt, self.model)]
 
     def train(self, passes, optimizers, hook):
-        c, loss_sum, order = _train_passes(self.model, optimizers[0], self.opt.train_target, passes, hook)
+        qs = []
+        c, loss_sum, order = _train_passes(self.model, optimizers[0], self.opt.train_target, passes, hook, self.dro, qs)
+        self.q_log = [qs]
         return [c], [loss_sum], [order]
 
     def evaluate(self, table, batch_size, target, indices, spurious=False, best=False):
@@ -475,12 +504,13 @@ class _Lr:
 
 
 def _sweep_train_pass(streams, sweep, table, orders_fn, batch_size, target, use_group, lr_fn, momentum, weight_decay, counted=True, acc=None,
-                      sync=True):
+                      sync=True, robust=None):
     """one loader pass of every replica: `orders_fn(r)` draws replica r's row order (under its own streams), all orders go to the
     device in ONE upload, then n_steps batched steps; lr_fn(step, n_steps) -> the R learning rates.  `sweep`: SweepAdapters (scored on
     the group prompts when `use_group`, else the class prompts) or SweepLinear.  `counted`: the pass adds to the loss sums and group
     counters; `acc` = (counts, loss sums) device tensors of an epoch made of several passes (fresh ones if None).  Returns (counts
-    [R, G, 2] numpy, loss sums [R] numpy, orders, acc) after the pass's one host sync; the two arrays are None without `sync`."""
+    [R, G, 2] numpy, loss sums [R] numpy, orders, acc) after the pass's one host sync; the two arrays are None without `sync`.
+    `robust`: an adapter.GroupDRO state with q [R, G] -- every step is a group-DRO step over the table's group ids."""
     R, dev = sweep.R, table.device
     linear = isinstance(sweep, adapter.SweepLinear)
     orders = [streams.run(r, orders_fn, r) for r in range(R)]
@@ -502,9 +532,10 @@ def _sweep_train_pass(streams, sweep, table, orders_fn, batch_size, target, use_
     counts, loss_sum = acc
     labels = table.targets_group if use_group else table.labels(target)
     prompts = () if linear else ("group" if use_group else "class",)
+    extra = {} if robust is None else {"robust": robust}
     for i, b in enumerate(steps):
         sweep.step(table.embeddings, b, labels, table.targets_group, *prompts, lr_fn(i, len(steps)), momentum, weight_decay, counts, loss_sum,
-                   counted=counted)
+                   counted=counted, **extra)
     orders = [o.numpy() for o in orders]
     if not sync:
         return None, None, orders, acc
@@ -542,11 +573,15 @@ class _LockStep:
         self.streams = ReplicaStreams(seeds)
         self.sweep = None
         self._dev_rows = None
+        self.dro, self.q_log = None, None                                # group DRO: q [R, G] (not part of the best models)
 
     def start(self, models, device):
         linear = isinstance(models[0], adapter.LinearClassifier)
         self.sweep = (adapter.SweepLinear if linear else adapter.SweepAdapters).from_modules(models, device)
         return [_Lr(o.learning_rate) for o in self.opts]
+
+    def start_robust(self, n_groups, step_size, device):
+        self.dro = adapter.GroupDRO(n_groups, step_size, device, replicas=self.R)
 
     def restore(self):
         self.sweep.restore([True] * self.R)
@@ -564,12 +599,17 @@ class _LockStep:
         def lr_fn(i, n):
             hook(i, n)
             return [l.lr for l in lrs]
-        acc, orders = None, []
+        acc, orders, qs = None, [], []
         for k, p in enumerate(passes):                                   # the passes of an epoch share the accumulators: one host sync
             order_fn = lambda r, p=p: _epoch_order(_pass_rows(p, r), p.shuffle, None if p.rows is None else p.rows[r])
             c, ls, o, acc = _sweep_train_pass(self.streams, self.sweep, p.table, order_fn, p.batch_size, opt.train_target, p.use_group, lr_fn,
-                                              opt.momentum, opt.weight_decay, counted=p.counted, acc=acc, sync=k == len(passes) - 1)
+                                              opt.momentum, opt.weight_decay, counted=p.counted, acc=acc, sync=k == len(passes) - 1, robust=self.dro)
             orders.append(o)
+            if self.dro is not None:
+                qs.append(self.dro.q.clone())
+        if self.dro is not None:
+            qs = [q.cpu().numpy() for q in qs]
+            self.q_log = [[q[r] for q in qs] for r in range(self.R)]
         return c, [float(x) for x in ls], [np.concatenate(o) for o in zip(*orders)]
 
     def evaluate(self, table, batch_size, target, indices, spurious=False, best=False):
@@ -684,6 +724,8 @@ def sweep_result_name(opt):
             name += "_cont"
     if getattr(opt, "resample_ce", False):
         name += "_rs"
+    if getattr(opt, "robust", False):
+        name += "_gdro"
     return name
 
 

@@ -541,6 +541,40 @@ int dbmm_adapter_train_step(const float* x, const int64_t* labels, float* w1, fl
                             int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* Online group DRO (Sagawa et al. 2020, "Distributionally Robust Neural Networks for Group Shifts", Algorithm 1) on the per-row
+ * CE of a batch.  loss_rows fp32 [B], groups int64 [B], q_in / q_out fp32 [G] (may be the same array), eta the step size:
+ *   n_g = rows of group g, L_g = mean loss of group g (float64 sums in a fixed order; 0 when n_g = 0), m = max L_g over the groups
+ *   present, q'_g = q_g exp(eta (L_g - m)) (absent groups: L_g = 0), q_out = q' / sum q', robust_loss [1] = sum_g q_out_g L_g.
+ * weights fp32 [3][G]: row 0 the row weights q_out_g / n_g (0 for an absent group), row 1 L_g, row 2 n_g.  A group id outside
+ * [0, G) belongs to no bucket.  One launch of one workgroup; identical inputs give identical bits.
+ * NULL pointer: DBMM_E_ARG; G outside 1..8 or B < 2: DBMM_E_SHAPE. */
+int dbmm_group_dro_weights(const float* loss_rows, const int64_t* groups, const float* q_in, float* q_out, float* weights,
+                           float* robust_loss, int64_t B, int64_t G, float eta, void* stream);
+
+/* dbmm_l2norm_sim_ce_bwd's fused training path with a weight per row: loss = sum_b weights[groups[b]] CE_b (row 0 of
+ * dbmm_group_dro_weights' output; weight 0 for a group id outside [0, G)). */
+int dbmm_l2norm_sim_ce_bwd_weighted(const float* z, const float* inv_norm, float ebd_weight, int blended, const float* tn,
+                                    const float* logits, const int64_t* labels, const int64_t* groups,
+                                    const float* weights, int64_t G, float temperature, float* dz, int64_t B, int64_t D,
+                                    int64_t C, void* stream);
+
+/* dbmm_adapter_train_step under group DRO: the step minimises sum_g q_g L_g instead of the batch mean.  groups int64 [B],
+ * q fp32 [G] (device state, updated in place by the step), eta the step size of q; robust_loss [1] takes loss_mean's place.
+ * Same workspace.  Two launches more than dbmm_adapter_train_step (10 / 13 on the fast shape): the head is forward rows, the
+ * group reduction + q update, weighted backward rows. */
+int dbmm_adapter_train_step_gdro(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
+                                 float* beta, float* running_mean, float* running_var, int64_t* nbt,
+                                 float* w2, float* b2, float* m_w1, float* m_b1, float* m_gamma,
+                                 float* m_beta, float* m_w2, float* m_b2, const float* o_w1,
+                                 const float* o_b1, const float* o_gamma, const float* o_beta,
+                                 float* o_running_mean, float* o_running_var, int64_t* o_nbt,
+                                 const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
+                                 float temperature, float lr, float momentum, float weight_decay,
+                                 int first_step, float* logits, float* loss_rows, float* robust_loss,
+                                 const int64_t* groups, float* q, float eta, int64_t G,
+                                 int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 /* Replica-batched adapter step (csrc/adapter_sweep.hip): R <= 16 independent runs of one sweep group take one training step in
  * the launches of ONE dbmm_adapter_train_step (8, or 11 with a frozen old adapter), the replica being a grid dimension.  Fast shape
  * only (H == 128, D % 128 == 0; else DBMM_E_UNSUPPORTED); replica r's results are the bits dbmm_adapter_train_step gives for r alone.
@@ -559,6 +593,17 @@ int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const int64_t* i
                             float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted, int64_t R,
                             int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
                             void* stream);
+
+/* dbmm_adapter_sweep_step under group DRO: replica r takes the step dbmm_adapter_train_step_gdro takes for r alone (same bits).
+ * The groups of the robust loss are `groups` (G <= 8 here), q fp32 [R][G] is updated in place, robust_loss [R] takes loss_mean's
+ * place and is what loss_sum accumulates (times B).  Same workspace; two launches more than dbmm_adapter_sweep_step. */
+int dbmm_adapter_sweep_step_gdro(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B,
+                                 const int64_t* labels, const int64_t* groups, void* const* params, float* const* bufs,
+                                 void* const* old, float ebd_weight, const float* tn, float temperature, const float* lr,
+                                 float momentum, float weight_decay, int first_step, float* logits, float* loss_rows,
+                                 float* robust_loss, int64_t* counts, double* loss_sum, int64_t G, int counted, float* q,
+                                 float eta, int64_t R, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 
 /* Replica-batched evaluation forward: eval-mode adapters (running statistics; old + new blend when `old`), cosine logits, per-row
  * CE, group counters and the float64 loss sum (loss_sum[r] += sum_b (double)loss_rows[r][b], fixed order) of R replicas over the
