@@ -228,6 +228,40 @@ def _robust_operands(robust, n_rows):
     return groups, state.q, state.step_size
 
 
+class _SimCESupConFn(torch.autograd.Function):
+    """Fused logits + mean CE mixed with the supervised-contrastive loss of z: returns (mixed loss, logits, per-row CE, L_con).  The
+    launches of the one-call step's head: CE rows forward, Gram tiles, reduction + mixed loss; CE rows backward, contrastive
+    backward onto the CE head's dz."""
+
+    @staticmethod
+    def forward(ctx, z, z_old, tn, temperature, ebd_weight, labels, weight, tau):
+        logits, loss_rows, _, _, inv_norm = ops.l2norm_sim_ce_fwd(z, tn, temperature, labels=labels, z_old=z_old, ebd_weight=ebd_weight,
+                                                                  want_mean=False)
+        con, _, stats, n_anchors, ws, mixed = ops.supcon_fwd(z, labels, tau, ce_rows=loss_rows, weight=weight)
+        ctx.save_for_backward(z, inv_norm, tn, logits, labels, stats, n_anchors, ws)
+        ctx.cfg = (temperature, ebd_weight, z_old is not None, weight, tau)
+        ctx.mark_non_differentiable(logits, loss_rows, con)
+        return mixed, logits, loss_rows, con
+
+    @staticmethod
+    def backward(ctx, gloss, _gl, _gr, _gc):
+        z, inv_norm, tn, logits, labels, stats, n_anchors, ws = ctx.saved_tensors
+        T, w, blended, weight, tau = ctx.cfg
+        dz = ops.l2norm_sim_ce_bwd(z, inv_norm, tn, T, logits=logits, labels=labels, blended=blended, ebd_weight=w)
+        dz = ops.supcon_bwd(z, labels, tau, stats, n_anchors, ws, weight, dz_in=dz, dz_in_scale=ops.supcon_ce_weight(weight))
+        return dz * gloss, None, None, None, None, None, None, None
+
+
+def _contrastive_operands(contrastive, robust):
+    """(weight, tau) of a `contrastive=(weight, tau)` argument"""
+    if robust is not None:
+        raise ops.DbmmUnsupported("contrastive= and robust= do not combine: the group-DRO head has no contrastive form")
+    weight, tau = contrastive
+    if not 0.0 <= float(weight) <= 1.0 or not float(tau) > 0.0:
+        raise ValueError(f"contrastive=(weight in [0, 1], temperature > 0) expected, got {contrastive!r}")
+    return float(weight), float(tau)
+
+
 def _step_key(new_ad, old_ad, optimizer):
     """every device address the fused step's argument block holds (15 of the trainable adapter incl. its six momentum buffers, 9 of the
     frozen one), or None while a momentum buffer does not exist yet"""
@@ -353,12 +387,18 @@ class CustomCLIP(nn.Module):
         tn = self._text("spurious", features.device)
         return _SimFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5))
 
-    def loss(self, features, labels, use_group=False, spurious=False, robust=None):
+    def loss(self, features, labels, use_group=False, spurious=False, robust=None, contrastive=None):
         """fused step body: returns (mean CE, logits, per-row CE); `spurious`: against the spurious-attribute prompts
         (forward_spurious + criterion, final_main.py:764-766).  `robust` = (GroupDRO state, group ids of the batch): the loss is the
-        group-DRO robust loss and the state's q is updated in place."""
+        group-DRO robust loss and the state's q is updated in place.  `contrastive` = (weight, temperature): returns (mixed loss,
+        logits, per-row CE, L_con) with mixed = (1 - weight) * mean CE + weight * L_con, L_con the supervised-contrastive loss of the
+        trainable adapter's output under `labels`."""
+        if contrastive is not None:
+            contrastive = _contrastive_operands(contrastive, robust)
         z, z_old = self._features(features)
         tn = self._text("spurious" if spurious else "group" if use_group else "class", features.device)
+        if contrastive is not None:
+            return _SimCESupConFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5), labels.contiguous(), *contrastive)
         if robust is not None:
             groups, q, eta = _robust_operands(robust, features.shape[0])
             return _SimCERobustFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5), labels, groups, q, eta)
@@ -368,14 +408,17 @@ class CustomCLIP(nn.Module):
         """(trainable adapter, frozen old adapter or None)"""
         return self.adapter, None
 
-    def train_step(self, features, labels, optimizer, use_group=False, robust=None):
+    def train_step(self, features, labels, optimizer, use_group=False, robust=None, contrastive=None):
         """The whole step body of final_main.py:455-466 / :610-623 -- forward, mean CE, backward and
         the SGD-momentum update -- as ONE C call (~20 launches back to back, no autograd graph, no
         host round trip).  Uses the optimiser's lr / momentum / weight_decay and its
         `momentum_buffer` state, so it can be mixed freely with `loss.backward(); optimizer.step()`.
         Requires train mode.  Returns (mean CE, logits, per-row CE), all on the device.  `robust` = (GroupDRO state, group ids of
         the batch): the group-DRO step (two launches more) -- the state's q is updated in place, the returned loss is the robust
-        loss."""
+        loss.  `contrastive` = (weight, temperature): the step with the supervised-contrastive head (three launches more); returns
+        (mixed loss, logits, per-row CE, L_con)."""
+        if contrastive is not None:
+            contrastive = _contrastive_operands(contrastive, robust)
         if not self.training:
             raise RuntimeError("train_step needs classifier.train()")
         new_ad, old_ad = self._step_adapters()
@@ -415,7 +458,8 @@ class CustomCLIP(nn.Module):
             return ops.adapter_train_step(
                 features.detach().contiguous(), labels.contiguous(), plan["args"], plan["H"], plan["with_old"],
                 getattr(self, "ebd_weight", 0.5), tn, self.temperature, group["lr"], group.get("momentum", 0.0),
-                group.get("weight_decay", 0.0), first, robust=None if robust is None else _robust_operands(robust, features.shape[0]))
+                group.get("weight_decay", 0.0), first, robust=None if robust is None else _robust_operands(robust, features.shape[0]),
+                contrastive=contrastive)
 
 
 class MultipleAdapter(CustomCLIP):

@@ -606,7 +606,8 @@ extern "C" size_t dbmm_workspace_bytes_adapter_train_step(int64_t B, int64_t D, 
     return train_step_floats(B, D, H, with_old) * sizeof(float);
 }
 
-// `groups` given: the group-DRO step (q [G] updated in place, loss_mean = the robust loss); else the ERM step
+// `groups` given: the group-DRO step (q [G] updated in place, loss_mean = the robust loss); `con_loss` given: the ERM step with the
+// supervised-contrastive head on top (loss_mean = the mixed loss; supcon.hip); else the ERM step
 static int train_step_impl(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
                            float* beta, float* rmean, float* rvar, int64_t* nbt, float* w2, float* b2,
                            float* m_w1, float* m_b1, float* m_gamma, float* m_beta, float* m_w2,
@@ -615,7 +616,7 @@ static int train_step_impl(const float* x, const int64_t* labels, float* w1, flo
                            const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
                            float temperature, float lr, float momentum, float weight_decay,
                            int first_step, float* logits, float* loss_rows, float* loss_mean, const int64_t* groups, float* q, float eta,
-                           int64_t G, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
+                           int64_t G, float con_w, float con_tau, float* con_loss, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
                            void* stream) {
     if (!x || !labels || !w1 || !b1 || !gamma || !beta || !rmean || !rvar || !w2 || !b2 || !m_w1 || !m_b1 ||
         !m_gamma || !m_beta || !m_w2 || !m_b2 || !tn || !logits || !loss_rows || !loss_mean || !workspace)
@@ -623,7 +624,13 @@ static int train_step_impl(const float* x, const int64_t* labels, float* w1, flo
     const int with_old = o_w1 != nullptr;
     if (with_old && (!o_b1 || !o_gamma || !o_beta || !o_rmean || !o_rvar || !o_w2 || !o_b2)) return DBMM_E_ARG;
     if (B < 2 || D <= 0 || H <= 0 || (D & 3) || (H & 3) || C <= 0 || C > 8) return DBMM_E_SHAPE;
-    if (workspace_bytes < dbmm_workspace_bytes_adapter_train_step(B, D, H, with_old)) return DBMM_E_WORKSPACE;
+    const size_t step_bytes = dbmm_workspace_bytes_adapter_train_step(B, D, H, with_old);
+    if (con_loss) {
+        if (!(con_tau > 0.f)) return DBMM_E_SHAPE;
+        if (!dbmm_supcon_workspace_bytes(B, D)) return DBMM_E_UNSUPPORTED;       // B > 2048: nothing has been launched
+        if (workspace_bytes < step_bytes + dbmm_supcon_workspace_bytes(B, D)) return DBMM_E_WORKSPACE;
+    }
+    if (workspace_bytes < step_bytes) return DBMM_E_WORKSPACE;
     if (!dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
     auto up4 = [](size_t n) { return (n + 3) / 4 * 4; };
     float* f = (float*)workspace;
@@ -675,9 +682,22 @@ static int train_step_impl(const float* x, const int64_t* labels, float* w1, flo
         rc = ce_fwdbwd(z, oz, ebd_weight, tn, labels, temperature, logits, loss_rows, dz, B, D, C, stream);
         if (rc) return rc;
     } else {
-        rc = dbmm_l2norm_sim_ce_fwd(z, oz, ebd_weight, tn, labels, temperature, logits, loss_rows, loss_mean, nullptr, inv_norm, B, D, C, stream);
+        rc = dbmm_l2norm_sim_ce_fwd(z, oz, ebd_weight, tn, labels, temperature, logits, loss_rows, con_loss ? nullptr : loss_mean, nullptr, inv_norm,
+                                    B, D, C, stream);
         if (rc) return rc;
         rc = dbmm_l2norm_sim_ce_bwd(z, inv_norm, ebd_weight, with_old, tn, logits, labels, nullptr, temperature, 1.f, dz, B, D, C, stream);
+        if (rc) return rc;
+    }
+    if (con_loss) {
+        // the contrastive head reads the trainable branch's z against itself: Gram tiles, the reduction (which also takes the mean of
+        // the CE rows and writes the mixed loss, so the backward's spare loss-mean block is not launched), and the backward onto
+        // the CE head's dz in place.  Its workspace follows the step's; the statistics live in that workspace's spare floats.
+        void* cws = (char*)workspace + step_bytes;
+        const size_t cbytes = dbmm_supcon_workspace_bytes(B, D);
+        float* sp = dbmm_supcon_spare(cws, B);
+        rc = dbmm_supcon_fwd(z, labels, con_tau, loss_rows, con_w, con_loss, loss_mean, sp + 4 * B, sp, sp + 5 * B, B, D, cws, cbytes, stream);
+        if (rc) return rc;
+        rc = dbmm_supcon_bwd(z, labels, con_tau, sp, sp + 5 * B, con_w, dz, 1.f - con_w, dz, B, D, cws, cbytes, stream);
         if (rc) return rc;
     }
     float* ps[6] = {w1, b1, gamma, beta, w2, b2};
@@ -689,7 +709,8 @@ static int train_step_impl(const float* x, const int64_t* labels, float* w1, flo
         const float *dw1part = nullptr, *db1part = nullptr;
         int nsplit = 1;
         rc = dbmm_adapter_bwd_fast(x, dz, h, mean, invstd, r, gamma, beta, w2, dw1, db1, dgamma, dbeta, dw2, db2, dh, dh + B * H, B, D,
-                                   (hipStream_t)stream, &dw1part, &db1part, &nsplit, groups ? nullptr : loss_rows, groups ? nullptr : loss_mean);
+                                   (hipStream_t)stream, &dw1part, &db1part, &nsplit, groups || con_loss ? nullptr : loss_rows,
+                                   groups || con_loss ? nullptr : loss_mean);
         if (rc) return rc;
         gs[0] = dw1part; gs[1] = db1part;
         const int nsp[6] = {nsplit, nsplit, 1, 1, 1, 1};
@@ -713,7 +734,7 @@ extern "C" int dbmm_adapter_train_step(const float* x, const int64_t* labels, fl
                                        void* stream) {
     return train_step_impl(x, labels, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2, o_w1, o_b1, o_gamma,
                            o_beta, o_rmean, o_rvar, o_nbt, o_w2, o_b2, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, logits,
-                           loss_rows, loss_mean, nullptr, nullptr, 0.f, 0, B, D, H, C, workspace, workspace_bytes, stream);
+                           loss_rows, loss_mean, nullptr, nullptr, 0.f, 0, 0.f, 0.f, nullptr, B, D, H, C, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dbmm_adapter_train_step_gdro(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
@@ -731,7 +752,24 @@ extern "C" int dbmm_adapter_train_step_gdro(const float* x, const int64_t* label
     if (G < 1 || G > GDRO_MAXG) return DBMM_E_SHAPE;
     return train_step_impl(x, labels, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2, o_w1, o_b1, o_gamma,
                            o_beta, o_rmean, o_rvar, o_nbt, o_w2, o_b2, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, logits,
-                           loss_rows, robust_loss, groups, q, eta, G, B, D, H, C, workspace, workspace_bytes, stream);
+                           loss_rows, robust_loss, groups, q, eta, G, 0.f, 0.f, nullptr, B, D, H, C, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dbmm_adapter_train_step_supcon(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
+                                              float* beta, float* rmean, float* rvar, int64_t* nbt, float* w2, float* b2,
+                                              float* m_w1, float* m_b1, float* m_gamma, float* m_beta, float* m_w2,
+                                              float* m_b2, const float* o_w1, const float* o_b1, const float* o_gamma,
+                                              const float* o_beta, float* o_rmean, float* o_rvar, int64_t* o_nbt,
+                                              const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
+                                              float temperature, float lr, float momentum, float weight_decay,
+                                              int first_step, float* logits, float* loss_rows, float* loss_mean,
+                                              float weight, float tau, float* con_loss, int64_t B,
+                                              int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+    if (!con_loss) return DBMM_E_ARG;
+    return train_step_impl(x, labels, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2, o_w1, o_b1, o_gamma,
+                           o_beta, o_rmean, o_rvar, o_nbt, o_w2, o_b2, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, logits,
+                           loss_rows, loss_mean, nullptr, nullptr, 0.f, 0, weight, tau, con_loss, B, D, H, C, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dbmm_version(void) { return 101; }

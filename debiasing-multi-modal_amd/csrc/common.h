@@ -75,6 +75,9 @@ int dbmm_conv1x1_res_stream(const float* a, const float* a_absmax, const void* w
 int dbmm_conv1x1_res_stream_f16(const void* x, const void* w, const float* scale, const float* bias, const void* residual, void* y, void* y_pooled,
                                 int64_t M, int64_t Ho, int64_t Wo, int64_t Cin, int64_t Cout, void* stream);
 
+// supcon.hip: the 5 B + 4 spare floats at the end of a dbmm_supcon_workspace_bytes workspace (the one-call step's stats | l | A)
+float* dbmm_supcon_spare(void* workspace, int64_t B);
+
 static inline bool dbmm_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
 // wave64 butterfly sum / max (all lanes get the result)

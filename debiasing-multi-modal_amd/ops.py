@@ -725,6 +725,68 @@ def l2norm_sim_ce_bwd_weighted(z, inv_norm, tn, temperature, logits, labels, gro
     return dz
 
 
+SUPCON_MAX_B = 2048
+
+
+def _f32(v):
+    """v rounded to float32, as the C ABI's float arguments are"""
+    return ctypes.c_float(v).value
+
+
+def supcon_ce_weight(weight):
+    """1 - weight in float32: the CE term's weight exactly as the library forms it from a float32 `weight`"""
+    return _f32(1.0 - _f32(weight))
+
+
+def _supcon_operands(z, labels, what):
+    require_cuda(z, labels)
+    _f32c(z)
+    B, D = z.shape
+    if labels.dtype != torch.int64 or not labels.is_contiguous():
+        raise _lib.DbmmError(f"{what}: labels must be a contiguous int64 tensor")
+    _sized(f"{what} labels", labels, B)
+    if B > SUPCON_MAX_B:
+        raise DbmmUnsupported(f"{what}: B = {B}; the contrastive head serves 2 <= B <= {SUPCON_MAX_B}")
+    return B, D
+
+
+def supcon_fwd(z, labels, tau, ce_rows=None, weight=0.0):
+    """supervised-contrastive loss of the rows of z [B, D] under `labels` at temperature `tau` (dbmm_supcon_fwd, 2 launches).
+    Returns (L_con (0-dim), per-row l [B], stats [4, B], A (0-dim float), workspace, mixed): stats, A and the workspace (it holds the
+    similarity matrix) are what supcon_bwd needs; `mixed` = (1 - weight) * mean(ce_rows) + weight * L_con when the per-row CE of the
+    batch is given, else None."""
+    B, D = _supcon_operands(z, labels, "supcon_fwd")
+    dev = z.device
+    if ce_rows is not None:
+        require_cuda(ce_rows)
+        _f32c(ce_rows)
+        _sized("supcon_fwd ce_rows", ce_rows, B)
+    nbytes = _lib.lib().dbmm_supcon_workspace_bytes(B, D)
+    ws = _empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+    out = _empty((5 * B + 3,), device=dev, dtype=torch.float32)         # stats [4][B] | l [B] | L_con, A, mixed: one allocation
+    base = out.data_ptr()
+    check(_lib.lib().dbmm_supcon_fwd(ptr(z), ptr(labels), float(tau), ptr(ce_rows), float(weight), base + 20 * B,
+                                     base + 20 * B + 8 if ce_rows is not None else None, base + 16 * B, base, base + 20 * B + 4, B, D,
+                                     ptr(ws), nbytes, stream()), "supcon_fwd")
+    return out[5 * B], out[4 * B:5 * B], out[:4 * B].view(4, B), out[5 * B + 1], ws, (out[5 * B + 2] if ce_rows is not None else None)
+
+
+def supcon_bwd(z, labels, tau, stats, n_anchors, ws, weight=1.0, dz_in=None, dz_in_scale=1.0):
+    """dz = dz_in_scale * dz_in + weight * dL_con/dz (dbmm_supcon_bwd, 1 launch) from supcon_fwd's stats, A and workspace"""
+    B, D = _supcon_operands(z, labels, "supcon_bwd")
+    require_cuda(stats, n_anchors, ws)
+    _f32c(stats)
+    _sized("supcon_bwd stats", stats, 4 * B)
+    if dz_in is not None:
+        require_cuda(dz_in)
+        _f32c(dz_in)
+        _sized("supcon_bwd dz_in", dz_in, B * D)
+    dz = _empty((B, D), device=z.device, dtype=torch.float32)
+    check(_lib.lib().dbmm_supcon_bwd(ptr(z), ptr(labels), float(tau), ptr(stats), ptr(n_anchors), float(weight), ptr(dz_in),
+                                     float(dz_in_scale), ptr(dz), B, D, ptr(ws), ws.numel() * 4, stream()), "supcon_bwd")
+    return dz
+
+
 def adapter_fwd(x, w1, b1, gamma, beta, running_mean, running_var, nbt, w2, b2, train, eps=1e-5, momentum=0.1):
     require_cuda(x, w1)
     _f32c(x)
@@ -789,15 +851,16 @@ def group_loss_sum(loss_rows, g, sums):
 _step_ws = {}
 
 
-def adapter_step_launches(B, D, H, with_old=False, robust=False):
+def adapter_step_launches(B, D, H, with_old=False, robust=False, contrastive=False):
     """kernel launches of one dbmm_adapter_train_step call on the purpose-built kernels (csrc/adapter_step.hip): forward 3
     (K-split fc1, BatchNorm statistics, BatchNorm + ReLU + fc2; 3 more for a frozen old adapter), cosine logits + CE forward
     and backward in one, backward 3 (dW2 / dr + the loss mean, BatchNorm backward + dW2 sums, dW1), SGD (+ dW1 sums); None for
     shapes that take the general GEMM kernel (H != 128 or D % 128 != 0).  `robust` (dbmm_adapter_train_step_gdro): 2 more -- the
-    head is forward rows, group reduction + q update, weighted backward rows, and the loss needs no launch of the backward"""
+    head is forward rows, group reduction + q update, weighted backward rows, and the loss needs no launch of the backward.
+    `contrastive` (dbmm_adapter_train_step_supcon): 3 more -- Gram tiles, the reduction + the mixed loss, the contrastive backward"""
     if H != 128 or D % 128 or not get_option("adapter_step_fused"):
         return None
-    return 8 + (3 if with_old else 0) + (2 if robust else 0)
+    return 8 + (3 if with_old else 0) + (2 if robust else 0) + (3 if contrastive else 0)
 
 
 def adapter_step_args(new, bufs, old):
@@ -808,25 +871,44 @@ def adapter_step_args(new, bufs, old):
     return tuple(ptr(t) for t in list(new) + list(bufs)) + (tuple(ptr(t) for t in old) if old is not None else (None,) * 9)
 
 
-def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, robust=None):
+def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, robust=None,
+                       contrastive=None):
     """one fused training-step body (dbmm_adapter_train_step); `args` from adapter_step_args().  `robust` = (groups int64 [B], q
     float32 [G], eta): the group-DRO step (dbmm_adapter_train_step_gdro) -- q is updated in place, the returned loss is the robust
-    loss."""
+    loss.  `contrastive` = (weight, tau): the step with the supervised-contrastive head (dbmm_adapter_train_step_supcon); returns
+    (mixed loss, logits, per-row CE, L_con)."""
     if not (x.is_cuda and labels.is_cuda and tn.is_cuda):
         require_cuda(x, labels, tn)
     _f32c(x)
     B, D = x.shape
     C = tn.shape[0]
     dev = x.device
-    key = (dev.index, B, D, H, with_old)
+    if contrastive is not None:
+        if robust is not None:
+            raise DbmmUnsupported("adapter_train_step: the contrastive head and group DRO do not combine")
+        if B > SUPCON_MAX_B:
+            raise DbmmUnsupported(f"adapter_train_step: B = {B}; the contrastive head serves 2 <= B <= {SUPCON_MAX_B}")
+    key = (dev.index, B, D, H, with_old, contrastive is not None)
     ws = _step_ws.get(key)
     if ws is None:
         nbytes = _lib.lib().dbmm_workspace_bytes_adapter_train_step(B, D, H, int(with_old))
+        if contrastive is not None:
+            nbytes += _lib.lib().dbmm_supcon_workspace_bytes(B, D)
         ws = _empty(nbytes // 4, device=dev, dtype=torch.float32)
         if len(_step_ws) > 8:
             _step_ws.clear()
         _step_ws[key] = ws
     logits = _empty((B, C), device=dev, dtype=torch.float32)
+    if contrastive is not None:
+        weight, tau = contrastive
+        loss = _empty((B + 2,), device=dev, dtype=torch.float32)    # per-row CE, the mixed loss, L_con
+        rc = _lib.lib().dbmm_adapter_train_step_supcon(
+            x.data_ptr(), labels.data_ptr(), *args, float(ebd_weight), tn.data_ptr(), float(temperature), float(lr), float(momentum),
+            float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * B, float(weight), float(tau),
+            loss.data_ptr() + 4 * B + 4, B, D, H, C, ws.data_ptr(), ws.numel() * 4, stream())
+        if rc:
+            check(rc, "adapter_train_step_supcon")
+        return loss[B], logits, loss[:B], loss[B + 1]
     loss = _empty((B + 1,), device=dev, dtype=torch.float32)        # per-row losses, then their mean: one allocation
     if robust is not None:
         groups, q, eta = robust

@@ -117,15 +117,25 @@ def _pass_rows(p, r=0):
     return len(p.table) if p.rows is None else len(p.rows[r])
 
 
-def _train_passes(classifier, optimizer, target, passes, lr_hook, robust=None, q_log=None):
+def _contrastive_option(opt):
+    """(weight, temperature) of opt.contrastive_weight / opt.cl_temperature (the reference's option names; read with getattr, default
+    0 = off and 0.1), or None when the weight is 0"""
+    weight = float(getattr(opt, "contrastive_weight", 0) or 0)
+    return (weight, float(getattr(opt, "cl_temperature", 0.1))) if weight > 0 else None
+
+
+def _train_passes(classifier, optimizer, target, passes, lr_hook, robust=None, q_log=None, contrastive=None, con_log=None):
     """The loader passes of one epoch of one run, on one pair of device accumulators with ONE host sync at the end.
     `lr_hook(step, n_steps)` runs before every step and restarts with each pass.  Returns (counters [G, 2] numpy, loss sum, the
     epoch's row order).  `robust` (an adapter.GroupDRO state): every step is a group-DRO step over the table's group ids -- also on
-    the group-prompt passes --, the loss summed is the robust loss; `q_log` (a list) receives q after each pass."""
+    the group-prompt passes --, the loss summed is the robust loss; `q_log` (a list) receives q after each pass.  `contrastive` = (weight,
+    temperature): every step is the mixed step (CustomCLIP.train_step(contrastive=)) under the labels its CE uses, the loss summed is
+    the mixed loss; `con_log` (a list) receives the sum of L_con x rows over the counted passes."""
     classifier.train()
     dev = passes[0].table.device
     counts = torch.zeros((passes[0].table.n_groups, 2), dtype=torch.int64, device=dev)
     loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
+    con_sum = torch.zeros((), dtype=torch.float64, device=dev) if contrastive is not None else None
     order, qs = [], []
     for p in passes:
         batches = _epoch_batches(_pass_rows(p), p.batch_size, p.shuffle, None if p.rows is None else p.rows[0])
@@ -138,6 +148,10 @@ def _train_passes(classifier, optimizer, target, passes, lr_hook, robust=None, q
                 lr_hook(step, len(batches))
             if robust is not None:
                 loss, logits, _ = classifier.train_step(emb, labels, optimizer, p.use_group, robust=(robust, groups))
+            elif contrastive is not None:
+                loss, logits, _, con = classifier.train_step(emb, labels, optimizer, p.use_group, contrastive=contrastive)
+                if p.counted:
+                    con_sum += con.double() * idx.numel()
             else:
                 loss, logits, _ = classifier.train_step(emb, labels, optimizer, p.use_group)
             if p.counted:
@@ -149,6 +163,8 @@ def _train_passes(classifier, optimizer, target, passes, lr_hook, robust=None, q
     c = counts.cpu().numpy()
     if q_log is not None:
         q_log.extend(q.cpu().numpy() for q in qs)
+    if con_log is not None and con_sum is not None:
+        con_log.append(con_sum.item())
     return c, loss_sum.item(), torch.cat(order).numpy()
 
 
@@ -259,6 +275,11 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
           step of the adapter methods is a group-DRO step (Sagawa et al. 2020; adapter.GroupDRO) over the table's
           group ids -- also on the group-prompt passes; q is per run, starts at 1 / G, starts over at the switch with the momentum, is
           not part of the best model; a pass counts the robust loss; the train records carry q after each pass; linear_probing raises.
+      opt.contrastive_weight > 0 (the reference's option, dead there; read with getattr, default 0 = off; opt.cl_temperature, default
+          0.1): every training step of the adapter methods of a single run minimises (1 - weight) * CE + weight * L_con, L_con the
+          supervised-contrastive loss of the trainable adapter's output under the labels the pass's CE uses (group ids on a
+          group-prompt pass); a pass counts the mixed loss; the train records carry `con`, the row-weighted
+          average of L_con; linear_probing, a sweep and opt.robust raise.
 
     Random streams are consumed like the reference does (global torch RNG: parameter initialisation and DataLoader orders; global
     numpy RNG: balance_val) through ex.streams.run(r, ...), so the same seeds give the same initial weights and batches.  Returns per
@@ -272,6 +293,15 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
     robust = bool(getattr(opt, "robust", False))
     if robust and linear:
         raise ops.DbmmUnsupported("group DRO (opt.robust) covers the adapter methods; the linear probe's fused step has no weighted form")
+    contrastive = _contrastive_option(opt)
+    if contrastive is not None:
+        if linear:
+            raise ops.DbmmUnsupported("the contrastive term (opt.contrastive_weight) covers the adapter methods; the linear probe has no adapter output")
+        if robust:
+            raise ops.DbmmUnsupported("opt.contrastive_weight and opt.robust do not combine: the group-DRO head has no contrastive form")
+        if not isinstance(ex, _SingleRun):
+            raise ops.DbmmUnsupported("the contrastive term (opt.contrastive_weight) covers single runs; the replica-batched step has no contrastive head")
+        ex.contrastive = contrastive
     streams = ex.streams
     dev = train_table.device
     D = input_dim or train_table.embeddings.shape[1]
@@ -346,6 +376,8 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
             loss, acc, gacc = _scores(train_table, c[r], ls[r], n_rows)
             if robust:                                                    # q after each pass of the epoch
                 extra = dict(extra, q=ex.q_log[r])
+            if contrastive is not None:                                   # row-weighted average of L_con over the counted passes
+                extra = dict(extra, con=ex.con_log[r] / n_rows)
             rec(r, kind=kind, epoch=epoch, loss=loss, acc=acc, group_acc=gacc, counts=c[r], order=orders[r], **extra)
             train_accs[r].append(gacc)
         vc, vl = ex.evaluate(val_table, bs_eval, opt.train_target, val_idx)
@@ -405,6 +437,7 @@ class _SingleRun:
         self.opt = opt
         self.model = self.best = self.device = None
         self.dro, self.q_log = None, None                                # group DRO: the run's state (not part of the best model)
+        self.contrastive, self.con_log = None, None                      # (weight, temperature) of the contrastive term; sum of L_con x rows
 
     def start(self, models, device):
         self.model, self.device = models[0].to(device), device
@@ -423,9 +456,9 @@ class _SingleRun:
         return [O.set_optimizer_reg(self.opt, self.model)]
 
     def train(self, passes, optimizers, hook):
-        qs = []
-        c, loss_sum, order = _train_passes(self.model, optimizers[0], self.opt.train_target, passes, hook, self.dro, qs)
-        self.q_log = [qs]
+        qs, cs = [], []
+        c, loss_sum, order = _train_passes(self.model, optimizers[0], self.opt.train_target, passes, hook, self.dro, qs, self.contrastive, cs)
+        self.q_log, self.con_log = [qs], cs
         return [c], [loss_sum], [order]
 
     def evaluate(self, table, batch_size, target, indices, spurious=False, best=False):
@@ -666,6 +699,8 @@ def train_sweep(opt, train_table, val_table, test_table, seeds, learning_rates=N
 
     Each replica keeps its own pair of global random streams (ReplicaStreams), so its initial weights, batch orders and balanced
     subsets are those of its own sequential run.  `log` (a list) receives one list of records per replica (train_all_epochs' records)."""
+    if _contrastive_option(opt) is not None:
+        raise ops.DbmmUnsupported("train_sweep: the contrastive term (opt.contrastive_weight) covers single runs (train_all_epochs)")
     replicas = _sweep_replicas(opt, list(seeds), learning_rates)
     D = train_table.embeddings.shape[1]
     if opt.tl_method not in _METHODS:

@@ -575,6 +575,49 @@ int dbmm_adapter_train_step_gdro(const float* x, const int64_t* labels, float* w
                                  int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
                                  size_t workspace_bytes, void* stream);
 
+/* Supervised-contrastive head (csrc/supcon.hip; Khosla et al. 2020, the reference's SupervisedContrastiveLoss batched over all
+ * anchors).  z fp32 [B][D] (D % 4 == 0), labels int64 [B] (any values; only equality is used), tau the temperature:
+ *   zn_i = z_i / ||z_i||,  S_ij = zn_i . zn_j / tau (j != i; the diagonal is excluded by index),  P(i) = { j != i : y_j == y_i },
+ *   l_i = logsumexp_{j != i} S_ij - mean_{j in P(i)} S_ij  (0 for a row without positives),
+ *   A = #{ i : |P(i)| > 0 },  L_con = sum_i l_i / A  (A == 0: L_con = 0 and a zero gradient).
+ * The products run on the exact-fp32 MFMA; no floating-point atomics: identical inputs give identical bits.
+ * dbmm_supcon_fwd, 2 launches (64 x 64 Gram tiles with per-row partials; one workgroup that merges them in column-tile order and
+ * sums L_con in float64 in row order).  Outputs: con_loss [1] = L_con, loss_rows [B] = l_i, n_anchors [1] = A (as a float),
+ * stats [4][B] = row max of S | sum_j exp(S_ij - max) | |P(i)| | 1 / ||z_i||.  ce_rows [B] (may be NULL; then mixed_loss may be
+ * NULL too): per-row CE of the same batch, and mixed_loss [1] = fma(1 - weight, mean(ce_rows), weight * L_con).  The workspace
+ * keeps S for the backward.
+ * dbmm_supcon_bwd, 1 launch: dz [B][D] = fma(dz_in_scale, dz_in, weight * dL_con/dz) (dz_in may be NULL: weight * dL_con/dz; or dz
+ * itself), from the forward's stats, n_anchors and workspace.
+ * NULL pointer: DBMM_E_ARG; B < 2, D <= 0, D % 4 != 0 or tau <= 0: DBMM_E_SHAPE; B > 2048: DBMM_E_UNSUPPORTED (nothing is
+ * launched); a workspace below dbmm_supcon_workspace_bytes(B, D): DBMM_E_WORKSPACE; z or the workspace not 16-byte aligned:
+ * DBMM_E_ALIGN.  dbmm_supcon_workspace_bytes is 0 for a B outside 2 .. 2048. */
+size_t dbmm_supcon_workspace_bytes(int64_t B, int64_t D);
+int dbmm_supcon_fwd(const float* z, const int64_t* labels, float temperature, const float* ce_rows, float weight,
+                    float* con_loss, float* mixed_loss, float* loss_rows, float* stats, float* n_anchors, int64_t B,
+                    int64_t D, void* workspace, size_t workspace_bytes, void* stream);
+int dbmm_supcon_bwd(const float* z, const int64_t* labels, float temperature, const float* stats, const float* n_anchors,
+                    float weight, const float* dz_in, float dz_in_scale, float* dz, int64_t B, int64_t D,
+                    const void* workspace, size_t workspace_bytes, void* stream);
+
+/* dbmm_adapter_train_step with the contrastive head: the step minimises (1 - weight) * mean CE + weight * L_con, L_con the
+ * supervised-contrastive loss of the TRAINABLE adapter's output z (not the blend with the old branch) under `labels` at
+ * temperature tau.  loss_mean [1] receives the mixed loss, con_loss [1] L_con.  The workspace is that of
+ * dbmm_adapter_train_step followed by dbmm_supcon_workspace_bytes(B, D) more bytes.  Three launches more than
+ * dbmm_adapter_train_step (11 / 14 on the fast shape): Gram tiles, the reduction + the mixed loss, the contrastive backward onto
+ * the CE head's dz.  B > 2048: DBMM_E_UNSUPPORTED, nothing launched. */
+int dbmm_adapter_train_step_supcon(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
+                                   float* beta, float* running_mean, float* running_var, int64_t* nbt,
+                                   float* w2, float* b2, float* m_w1, float* m_b1, float* m_gamma,
+                                   float* m_beta, float* m_w2, float* m_b2, const float* o_w1,
+                                   const float* o_b1, const float* o_gamma, const float* o_beta,
+                                   float* o_running_mean, float* o_running_var, int64_t* o_nbt,
+                                   const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
+                                   float temperature, float lr, float momentum, float weight_decay,
+                                   int first_step, float* logits, float* loss_rows, float* loss_mean,
+                                   float weight, float tau, float* con_loss,
+                                   int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
 /* Replica-batched adapter step (csrc/adapter_sweep.hip): R <= 16 independent runs of one sweep group take one training step in
  * the launches of ONE dbmm_adapter_train_step (8, or 11 with a frozen old adapter), the replica being a grid dimension.  Fast shape
  * only (H == 128, D % 128 == 0; else DBMM_E_UNSUPPORTED); replica r's results are the bits dbmm_adapter_train_step gives for r alone.
