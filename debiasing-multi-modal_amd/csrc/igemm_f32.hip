@@ -439,6 +439,23 @@ __device__ __forceinline__ void igemm_tile(const IgemmP& p, float* lds, int tile
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    // Long reductions.  One fp32 accumulator summed over all of K is one chain of K roundings: at K = 2048 (the attention pool's score
+    // product) that measured 5 - 6 x the rounding error of a blocked fp32 sum.  The tiles with at most two accumulator blocks per wave
+    // (32 x 128, 128 x 32, 64 x 64, 128 x 64) on the FAST loader therefore move their running sums into a second set every 128
+    // products, so that no chain is longer than 128 products plus K / 128 block sums; up to K = 128 nothing moves and the result is
+    // the single chain's.  (The 128 x 128 tile has no registers for a second set, and the generic loader's staging registers leave none
+    // at these occupancies either -- the second set spilled there: both keep the single chain.)
+    constexpr bool TWO_LEVEL = !FIXUP && FAST && TM * TN <= 2;
+    constexpr int FLUSH = 128 / BK;
+    f32x16 tot[TWO_LEVEL ? TM : 1][TWO_LEVEL ? TN : 1];
+    if constexpr (TWO_LEVEL) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
+    }
 
     const int fr = lane & 31, fh = lane >> 5, fsw = lds_swz<BK>(fr);
 
@@ -475,6 +492,14 @@ __device__ __forceinline__ void igemm_tile(const IgemmP& p, float* lds, int tile
             if constexpr (FAST && DMA) dma_chunk((kc + 1) * BK, buf ^ 1);
             else { load_a((kc + 1) * BK); load_w((kc + 1) * BK); }
         }
+        if constexpr (TWO_LEVEL) {   // behind the barrier and the prefetch: the last block's MFMAs have drained, the loads are in flight
+            if (kc > kb && (kc - kb) % FLUSH == 0) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) { tot[i][j] += acc[i][j]; acc[i][j] = (f32x16)(0.f); }
+            }
+        }
         const float* Ab = As + buf * BM * BK;
         const float* Wb = Ws + buf * BN * BK;
 #pragma unroll
@@ -497,6 +522,12 @@ __device__ __forceinline__ void igemm_tile(const IgemmP& p, float* lds, int tile
             if (kc + 1 < ke) store_lds(buf ^ 1);
         }
         __syncthreads();
+    }
+    if constexpr (TWO_LEVEL) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[i][j] += tot[i][j];
     }
 
     if (partial) {
@@ -1829,6 +1860,10 @@ extern "C" int dbmm_gemm_batched(const float* a, int64_t lda, int64_t stride_a, 
     if (act < 0 || act > 2) return DBMM_E_ARG;
     if ((lda & 3) || (ldw & 3) || (stride_a & 3) || (stride_w & 3)) return DBMM_E_ALIGN;
     if (!dbmm_aligned16(a) || !dbmm_aligned16(w)) return DBMM_E_ALIGN;
+    // the epilogue moves 16 B per lane (bias loads, C stores) whenever N and ldc are multiples of 4: every problem's c and bias
+    // must then start on a 16-B boundary
+    if (ldc < N) return DBMM_E_SHAPE;
+    if (!dbmm_aligned16(c) || (stride_c & 3) || (bias && (!dbmm_aligned16(bias) || (stride_bias & 3)))) return DBMM_E_ALIGN;
     if ((!trans_a && (K & 3)) || (trans_a && (M & 3)) || (!trans_w && (K & 3)) || (trans_w && (N & 3)))
         return DBMM_E_SHAPE;
     IgemmP p{};

@@ -373,7 +373,12 @@ void dbmm_debug_last_igemm(int* out11);
 
 /* `batch` independent GEMMs of identical shape in one launch (grid.y): problem b uses
  * a + b*stride_a, w + b*stride_w, bias + b*stride_bias, c + b*stride_c (element strides,
- * multiples of 4).  Used for the per-head products of the collapsed attention pool. */
+ * multiples of 4).  Used for the per-head products of the collapsed attention pool.
+ *   op(a), op(w), alpha, act as in dbmm_gemm_bias_act (no residual); bias may be NULL; stride_w = 0 / stride_bias = 0 share one
+ *   weight / bias between all problems.  ldc >= N (any value: rows are stored 16 B at a time when N and ldc are multiples of 4).
+ *   1 <= batch <= 65535 (one grid row per problem), else DBMM_E_SHAPE; K % 4 != 0 (M % 4 != 0 with trans_a, N % 4 != 0 with
+ *   trans_w) or ldc < N: DBMM_E_SHAPE; a, w, c or bias not 16-byte aligned, lda, ldw or one of the four strides (stride_bias when
+ *   bias is given) not a multiple of 4: DBMM_E_ALIGN; a NULL a, w or c or an unknown act: DBMM_E_ARG.  Nothing is launched then. */
 int dbmm_gemm_batched(const float* a, int64_t lda, int64_t stride_a, int trans_a, const float* w,
                       int64_t ldw, int64_t stride_w, int trans_w, const float* bias,
                       int64_t stride_bias, float* c, int64_t ldc, int64_t stride_c, int64_t M,

@@ -48,6 +48,9 @@ def test_argument_validation_without_gpu(built):
     # K not a multiple of 4 -> shape error (or alignment if the ctypes buffer is not 16-B aligned)
     assert L.dbmm_gemm_bias_act(p, 4, 0, p, 4, 0, None, None, 0, p, 4, 4, 4, 3, 1.0, 0, None) in (-1, -2)
     assert L.dbmm_avgpool2d(p, p, 1, 3, 3, 4, 2, None) in (-1, -2)
+    # dbmm_gemm_batched: every batch stride a multiple of 4 (stride_c = 6 here), ldc >= N
+    assert L.dbmm_gemm_batched(p, 4, 0, 0, p, 4, 0, 0, None, 0, p, 4, 6, 4, 4, 4, 2, 1.0, 0, None) == -2
+    assert L.dbmm_gemm_batched(p, 4, 0, 0, p, 4, 0, 0, None, 0, p, 2, 0, 4, 4, 4, 2, 1.0, 0, None) in (-1, -2)
     assert L.dbmm_mha_core(p, p, 1, 4, 100, 2, 0, None) == -1          # E != heads*64
     assert L.dbmm_l2norm_sim_ce_fwd(p, None, 0.5, p, None, 0.01, p, None, None, None, None, 4, 8, 9, None) == -1
     assert L.dbmm_sgd_momentum(0, None, None, None, None, 0.1, 0.9, 0.0, 1, None) == -4
