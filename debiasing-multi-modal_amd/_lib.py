@@ -45,6 +45,7 @@ KERNEL_SOURCES = (
     ("linear_", ("linear_step.hip", "linear_bodies.inc", "common.h")),
     ("pairdist_", ("pairdist.hip", "common.h")),
     ("supcon_", ("supcon.hip", "common.h")),
+    ("sets_", ("supcon_sets.hip", "common.h")),
 )
 
 
@@ -182,6 +183,11 @@ _SIGS = {
     "dbmm_supcon_fwd": [_P, _P, _F, _P, _F, _P, _P, _P, _P, _P, _L, _L, _P, _Z, _P],
     "dbmm_supcon_bwd": [_P, _P, _F, _P, _P, _F, _P, _F, _P, _L, _L, _P, _Z, _P],
     "dbmm_adapter_train_step_supcon": [_P] * 26 + [_F, _P, _F, _F, _F, _F, _I, _P, _P, _P, _F, _F, _P, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_supcon_sets_workspace_bytes": [_L, _L, _L],
+    "dbmm_supcon_sets_fwd": [_P, _F, _F, _P, _P, _L, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_supcon_sets_bwd": [_P, _F, _F, _P, _L, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_adapter_train_step_sets": [_L, _L, _L, _L],
+    "dbmm_adapter_train_step_sets": [_P] * 16 + [_F, _F, _F, _I, _F, _F, _P, _P, _L, _L, _L, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_adapter_sweep_step": [_L, _L, _L, _L, _I],
     "dbmm_adapter_sweep_step": [_P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _F, _P, _F, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _I, _L, _L, _L, _L, _L,
                                 _P, _Z, _P],
@@ -222,6 +228,8 @@ _RESTYPES = {
     "dbmm_workspace_bytes_linear_sweep_eval": c_size_t,
     "dbmm_workspace_bytes_pairdist": c_size_t,
     "dbmm_supcon_workspace_bytes": c_size_t,
+    "dbmm_supcon_sets_workspace_bytes": c_size_t,
+    "dbmm_workspace_bytes_adapter_train_step_sets": c_size_t,
 }
 
 EXPORTS = tuple(_SIGS)

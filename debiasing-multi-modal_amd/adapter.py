@@ -252,6 +252,35 @@ class _SimCESupConFn(torch.autograd.Function):
         return dz * gloss, None, None, None, None, None, None, None
 
 
+class _SetsFn(torch.autograd.Function):
+    """The contrastive loss of T sampled sets [anchor(s); positives; negatives] of adapter outputs z: returns (L = scale * sum_t
+    l_t, l_t).  The head's four launches: forward rows, reduction; backward rows, anchor merge (csrc/supcon_sets.hip)."""
+
+    @staticmethod
+    def forward(ctx, z, sets, scale, tau):
+        z = z.contiguous()
+        loss, loss_sets, ws = ops.supcon_sets_fwd(z, sets, scale, tau)
+        ctx.save_for_backward(z, ws)
+        ctx.cfg = (sets, scale, tau)
+        ctx.mark_non_differentiable(loss_sets)
+        return loss, loss_sets
+
+    @staticmethod
+    def backward(ctx, gloss, _gs):
+        z, ws = ctx.saved_tensors
+        sets, scale, tau = ctx.cfg
+        return ops.supcon_sets_bwd(z, sets, scale, tau, ws) * gloss, None, None, None
+
+
+def _sets_operands(sets, contrastive):
+    """((T, A, P, N), scale, tau) of `sets=(T, A, P, N)` and `contrastive=(scale, temperature)`"""
+    T, A, P, N = (int(v) for v in sets)
+    scale, tau = contrastive
+    if min(T, A, P, N) < 1 or not float(tau) > 0.0:
+        raise ValueError(f"sets=(T, A, P, N) all >= 1 and contrastive=(scale, temperature > 0) expected, got {sets!r}, {contrastive!r}")
+    return (T, A, P, N), float(scale), float(tau)
+
+
 def _contrastive_operands(contrastive, robust):
     """(weight, tau) of a `contrastive=(weight, tau)` argument"""
     if robust is not None:
@@ -408,21 +437,11 @@ class CustomCLIP(nn.Module):
         """(trainable adapter, frozen old adapter or None)"""
         return self.adapter, None
 
-    def train_step(self, features, labels, optimizer, use_group=False, robust=None, contrastive=None):
-        """The whole step body of final_main.py:455-466 / :610-623 -- forward, mean CE, backward and
-        the SGD-momentum update -- as ONE C call (~20 launches back to back, no autograd graph, no
-        host round trip).  Uses the optimiser's lr / momentum / weight_decay and its
-        `momentum_buffer` state, so it can be mixed freely with `loss.backward(); optimizer.step()`.
-        Requires train mode.  Returns (mean CE, logits, per-row CE), all on the device.  `robust` = (GroupDRO state, group ids of
-        the batch): the group-DRO step (two launches more) -- the state's q is updated in place, the returned loss is the robust
-        loss.  `contrastive` = (weight, temperature): the step with the supervised-contrastive head (three launches more); returns
-        (mixed loss, logits, per-row CE, L_con)."""
-        if contrastive is not None:
-            contrastive = _contrastive_operands(contrastive, robust)
+    def _plan(self, optimizer, what):
+        """(the argument block of the one-call steps for this module and `optimizer`, whether this is the optimiser's first step)"""
         if not self.training:
-            raise RuntimeError("train_step needs classifier.train()")
+            raise RuntimeError(f"{what} needs classifier.train()")
         new_ad, old_ad = self._step_adapters()
-        group = optimizer.param_groups[0]
         plan = self.__dict__.get("_step_plan")
         first = False
         # The argument block of the C call holds 24 raw pointers.  It is rebuilt whenever ANY tensor it points at was replaced or
@@ -438,7 +457,7 @@ class CustomCLIP(nn.Module):
             trainable = [new[0], new[1], new[2], new[3], new[7], new[8]]
             owned = {id(p) for g in optimizer.param_groups for p in g["params"]}
             if len(optimizer.param_groups) != 1 or any(id(p) not in owned for p in trainable):
-                raise RuntimeError("train_step: the optimiser must hold the adapter's six tensors in one param group")
+                raise RuntimeError(f"{what}: the optimiser must hold the adapter's six tensors in one param group")
             first = any("momentum_buffer" not in optimizer.state[p] for p in trainable)
             bufs = []
             for p in trainable:
@@ -453,6 +472,44 @@ class CustomCLIP(nn.Module):
                                                    [t.data for t in pack(old_ad)] if old_ad is not None else None),
                         H=new[0].shape[0], with_old=old_ad is not None)
             self.__dict__["_step_plan"] = plan
+        return plan, first
+
+    def sets_loss(self, features, sets, contrastive):
+        """The contrastive-adapter loss of one step (Zhang & Re 2022; the reference's train_one_epoch_cl, demo/visualizer_supcon.py:
+        412-508, with its SupervisedContrastiveLoss) on the autograd path.  `features` [T * S, D]: T sets of S = A + P + N rows
+        [anchor, extra anchors; positives; negatives], `sets` = (T, A, P, N), `contrastive` = (scale, temperature).  Returns (L, l_t):
+        l_t = log sum_{P u N} exp(s_j) - mean_P s_p with s_j the cosine of the anchor's and row j's adapter outputs / temperature,
+        L = scale * sum_t l_t; extra anchors take no loss.  No prompts and no CE take part.  Departures from the dead reference
+        path: the step's T * S rows pass the adapter as ONE train-mode BatchNorm batch (the reference would
+        have pushed [anchor; positives] and [anchor; negatives] through separately); no ca_pre_norm and no ca_head -- the adapter
+        is fed raw embeddings, as in forward(); the max subtracted is over P u N, which gives the same value."""
+        sets, scale, tau = _sets_operands(sets, contrastive)
+        return _SetsFn.apply(self.adapter(features), sets, scale, tau)
+
+    def sets_step(self, features, optimizer, sets, contrastive):
+        """sets_loss(...), backward and the SGD-momentum update as ONE C call (dbmm_adapter_train_step_sets); the same bits as
+        `sets_loss(...)[0].backward(); optimizer.step()`.  The adapter's fast shape only (hidden width 128, D % 128 == 0): other
+        shapes raise ops.DbmmUnsupported.  Requires train mode.  Returns (L, l_t), on the device."""
+        sets, scale, tau = _sets_operands(sets, contrastive)
+        plan, first = self._plan(optimizer, "sets_step")
+        group = optimizer.param_groups[0]
+        with torch.no_grad():
+            return ops.adapter_train_step_sets(features.detach().contiguous(), plan["args"], plan["H"], sets, scale, tau, group["lr"],
+                                               group.get("momentum", 0.0), group.get("weight_decay", 0.0), first)
+
+    def train_step(self, features, labels, optimizer, use_group=False, robust=None, contrastive=None):
+        """The whole step body of final_main.py:455-466 / :610-623 -- forward, mean CE, backward and
+        the SGD-momentum update -- as ONE C call (~20 launches back to back, no autograd graph, no
+        host round trip).  Uses the optimiser's lr / momentum / weight_decay and its
+        `momentum_buffer` state, so it can be mixed freely with `loss.backward(); optimizer.step()`.
+        Requires train mode.  Returns (mean CE, logits, per-row CE), all on the device.  `robust` = (GroupDRO state, group ids of
+        the batch): the group-DRO step (two launches more) -- the state's q is updated in place, the returned loss is the robust
+        loss.  `contrastive` = (weight, temperature): the step with the supervised-contrastive head (three launches more); returns
+        (mixed loss, logits, per-row CE, L_con)."""
+        if contrastive is not None:
+            contrastive = _contrastive_operands(contrastive, robust)
+        plan, first = self._plan(optimizer, "train_step")
+        group = optimizer.param_groups[0]
         tn = self._text("group" if use_group else "class", features.device)
         with torch.no_grad():
             return ops.adapter_train_step(
@@ -490,6 +547,12 @@ class MultipleAdapter(CustomCLIP):
 
     def _step_adapters(self):
         return self.new_adapter, self.old_cls.adapter
+
+    def sets_loss(self, features, sets, contrastive):
+        raise ops.DbmmUnsupported("the contrastive adapter (sets_loss / sets_step) covers CustomCLIP; MultipleAdapter has no sets head")
+
+    def sets_step(self, features, optimizer, sets, contrastive):
+        raise ops.DbmmUnsupported("the contrastive adapter (sets_loss / sets_step) covers CustomCLIP; MultipleAdapter has no sets head")
 
 
 # ---------------------------------------------------------------------------------------

@@ -772,6 +772,75 @@ extern "C" int dbmm_adapter_train_step_supcon(const float* x, const int64_t* lab
                            loss_rows, loss_mean, nullptr, nullptr, 0.f, 0, weight, tau, con_loss, B, D, H, C, workspace, workspace_bytes, stream);
 }
 
+// ---- one call = one step of the contrastive adapter on sampled sets (supcon_sets.hip) ----------------------------
+// workspace layout (floats): h, r [B*H]x2 | z [B*D] | mean, invstd [H]x2 | dz [B*D] | dw1 [H*D] db1 dgamma dbeta [H]x3 dw2 [D*H] db2 [D]
+// | bwd scratch | the head's workspace, B = T*S
+static size_t sets_step_floats(int64_t B, int64_t D, int64_t H) {
+    const size_t n = 2 * B * H + 2 * B * D + 2 * H + (H * D + 3 * H + D * H + D) + dbmm_workspace_bytes_adapter_bwd(B, D, H) / sizeof(float);
+    return (n + 3) / 4 * 4 + 64;
+}
+
+extern "C" size_t dbmm_workspace_bytes_adapter_train_step_sets(int64_t T, int64_t S, int64_t D, int64_t H) {
+    const size_t head = dbmm_supcon_sets_workspace_bytes(T, S, D);
+    if (!head || H <= 0 || (H & 3)) return 0;
+    return sets_step_floats(T * S, D, H) * sizeof(float) + head;
+}
+
+extern "C" int dbmm_adapter_train_step_sets(const float* x, float* w1, float* b1, float* gamma, float* beta, float* rmean, float* rvar,
+                                            int64_t* nbt, float* w2, float* b2, float* m_w1, float* m_b1, float* m_gamma, float* m_beta,
+                                            float* m_w2, float* m_b2, float lr, float momentum, float weight_decay, int first_step,
+                                            float scale, float tau, float* loss, float* loss_sets, int64_t T, int64_t A, int64_t P,
+                                            int64_t N, int64_t D, int64_t H, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !w1 || !b1 || !gamma || !beta || !rmean || !rvar || !w2 || !b2 || !m_w1 || !m_b1 || !m_gamma || !m_beta || !m_w2 || !m_b2 ||
+        !loss || !loss_sets || !workspace)
+        return DBMM_E_ARG;
+    if (T < 1 || A < 1 || P < 1 || N < 1 || D <= 0 || H <= 0 || (D & 3) || (H & 3) || !(tau > 0.f) || T > 65535 || A > INT32_MAX ||
+        P > INT32_MAX || N > INT32_MAX || T * (A + P + N) > INT32_MAX)
+        return DBMM_E_SHAPE;
+    const int64_t S = A + P + N, B = T * S;
+    if (!dbmm_adapter_fast_shape(B, D, H) || !dbmm_opt(OPT_ADAPTER_STEP_FUSED) || !dbmm_aligned16(x)) return DBMM_E_UNSUPPORTED;
+    const size_t head_bytes = dbmm_supcon_sets_workspace_bytes(T, S, D);
+    if (!head_bytes) return DBMM_E_UNSUPPORTED;
+    const size_t step_bytes = sets_step_floats(B, D, H) * sizeof(float);
+    if (workspace_bytes < step_bytes + head_bytes) return DBMM_E_WORKSPACE;
+    if (!dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
+    auto up4 = [](size_t n) { return (n + 3) / 4 * 4; };
+    float* f = (float*)workspace;
+    float* h = f;            f += up4(B * H);
+    float* r = f;            f += up4(B * H);
+    float* z = f;            f += up4(B * D);
+    float* mean = f;         f += up4(H);
+    float* invstd = f;       f += up4(H);
+    float* dz = f;           f += up4(B * D);
+    float* dw1 = f;          f += up4(H * D);
+    float* db1 = f;          f += up4(H);
+    float* dgamma = f;       f += up4(H);
+    float* dbeta = f;        f += up4(H);
+    float* dw2 = f;          f += up4(D * H);
+    float* db2 = f;          f += up4(D);
+    float* bws = f;
+    void* hws = (char*)workspace + step_bytes;
+    int rc = dbmm_adapter_fwd(x, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, h, mean, invstd, r, z, B, D, H, 1, 1e-5f, 0.1f, stream);
+    if (rc) return rc;
+    rc = dbmm_supcon_sets_fwd(z, scale, tau, loss, loss_sets, T, A, P, N, D, hws, head_bytes, stream);
+    if (rc) return rc;
+    rc = dbmm_supcon_sets_bwd(z, scale, tau, dz, T, A, P, N, D, hws, head_bytes, stream);
+    if (rc) return rc;
+    float* ps[6] = {w1, b1, gamma, beta, w2, b2};
+    const float* gs[6] = {dw1, db1, dgamma, dbeta, dw2, db2};
+    float* ms[6] = {m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2};
+    const int64_t ns[6] = {H * D, H, H, H, D * H, D};
+    float* dh = bws + B * H;
+    const float *dw1part = nullptr, *db1part = nullptr;
+    int nsplit = 1;
+    rc = dbmm_adapter_bwd_fast(x, dz, h, mean, invstd, r, gamma, beta, w2, dw1, db1, dgamma, dbeta, dw2, db2, dh, dh + B * H, B, D,
+                               (hipStream_t)stream, &dw1part, &db1part, &nsplit);
+    if (rc) return rc;
+    gs[0] = dw1part; gs[1] = db1part;
+    const int nsp[6] = {nsplit, nsplit, 1, 1, 1, 1};
+    return sgd_impl(6, ps, gs, ms, ns, nsp, lr, momentum, weight_decay, first_step, stream);
+}
+
 extern "C" int dbmm_version(void) { return 101; }
 
 extern "C" const char* dbmm_error_string(int code) {

@@ -787,6 +787,86 @@ def supcon_bwd(z, labels, tau, stats, n_anchors, ws, weight=1.0, dz_in=None, dz_
     return dz
 
 
+SETS_CHUNK_ROWS = 32        # rows of a set one workgroup of the sets head takes (csrc/supcon_sets.hip: SETS_ROWS)
+SETS_MAX_D = 8192
+
+
+def _sets_operands(z, sets, what):
+    """(T, A, P, N, D) of z [T * (A + P + N), D] under `sets` = (T, A, P, N)"""
+    require_cuda(z)
+    _f32c(z)
+    T, A, P, N = (int(v) for v in sets)
+    if min(T, A, P, N) < 1:
+        raise ValueError(f"{what}: sets=(T, A, P, N) must all be at least 1, got {tuple(sets)!r}")
+    if z.dim() != 2 or z.shape[0] != T * (A + P + N):
+        raise RuntimeError(f"{what}: {tuple(z.shape)} rows where sets={tuple(sets)!r} means {T * (A + P + N)} rows of one width")
+    if z.shape[1] > SETS_MAX_D:
+        raise DbmmUnsupported(f"{what}: D = {z.shape[1]}; the sets head serves D <= {SETS_MAX_D}")
+    return T, A, P, N, z.shape[1]
+
+
+def supcon_sets_fwd(z, sets, scale, tau):
+    """contrastive loss of T sampled sets (dbmm_supcon_sets_fwd, 2 launches): z [T * S, D], `sets` = (T, A, P, N), S = A + P + N; row 0
+    of a set is the anchor, rows A .. A+P-1 the positives, the last N rows the negatives.  Returns (L = scale * sum_t l_t (0-dim),
+    l_t [T], workspace); the workspace is what supcon_sets_bwd needs."""
+    T, A, P, N, D = _sets_operands(z, sets, "supcon_sets_fwd")
+    nbytes = _lib.lib().dbmm_supcon_sets_workspace_bytes(T, A + P + N, D)
+    ws = _empty(max(nbytes // 4, 4), device=z.device, dtype=torch.float32)
+    out = _empty((T + 1,), device=z.device, dtype=torch.float32)          # l_t, then L: one allocation
+    check(_lib.lib().dbmm_supcon_sets_fwd(ptr(z), float(scale), float(tau), out.data_ptr() + 4 * T, ptr(out), T, A, P, N, D, ptr(ws), nbytes,
+                                          stream()), "supcon_sets_fwd")
+    return out[T], out[:T], ws
+
+
+def supcon_sets_bwd(z, sets, scale, tau, ws):
+    """dz = dL/dz (dbmm_supcon_sets_bwd, 2 launches) from supcon_sets_fwd's workspace; the rows of extra anchors are zero"""
+    T, A, P, N, D = _sets_operands(z, sets, "supcon_sets_bwd")
+    require_cuda(ws)
+    _f32c(ws)
+    dz = _empty((z.shape[0], D), device=z.device, dtype=torch.float32)
+    check(_lib.lib().dbmm_supcon_sets_bwd(ptr(z), float(scale), float(tau), ptr(dz), T, A, P, N, D, ptr(ws), ws.numel() * 4, stream()),
+          "supcon_sets_bwd")
+    return dz
+
+
+def gather_sets(table, idx):
+    """the rows of T sampled sets as one batch: out[t * S + j] = table[idx[t, j]] for int64 idx [T, S] on the table's device"""
+    require_cuda(table, idx)
+    if idx.dtype != torch.int64 or idx.dim() != 2:
+        raise _lib.DbmmError(f"gather_sets: idx must be an int64 tensor [T, S], got {idx.dtype} {tuple(idx.shape)}")
+    return gather_rows(table, idx.reshape(-1))
+
+
+_sets_ws = {}
+
+
+def adapter_train_step_sets(x, args, H, sets, scale, tau, lr, momentum, weight_decay, first_step):
+    """one step of the contrastive adapter on T sampled sets in one call (dbmm_adapter_train_step_sets): adapter forward with
+    train-mode BatchNorm over the T * S rows as one batch, the sets head forward and backward, adapter backward, SGD.  `args`: the
+    first 15 pointers of adapter_step_args().  Returns (L, l_t [T]).  Raises DbmmUnsupported off the adapter's fast shape."""
+    T, A, P, N, D = _sets_operands(x, sets, "adapter_train_step_sets")
+    S = A + P + N
+    dev = x.device
+    key = (dev.index, T, S, D, H)
+    ws = _sets_ws.get(key)
+    if ws is None:
+        nbytes = _lib.lib().dbmm_workspace_bytes_adapter_train_step_sets(T, S, D, H)
+        ws = _empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        if len(_sets_ws) > 4:
+            _sets_ws.clear()
+        _sets_ws[key] = ws
+    out = _empty((T + 1,), device=dev, dtype=torch.float32)
+    rc = _lib.lib().dbmm_adapter_train_step_sets(x.data_ptr(), *args[:15], float(lr), float(momentum), float(weight_decay), int(first_step),
+                                                 float(scale), float(tau), out.data_ptr() + 4 * T, out.data_ptr(), T, A, P, N, D, H,
+                                                 ws.data_ptr(), ws.numel() * 4, stream())
+    if rc == _lib.E_UNSUPPORTED:
+        raise DbmmUnsupported(f"adapter_train_step_sets: no one-call step for D = {D}, H = {H}, {T * S} rows (the adapter's fast shape: "
+                              "H == 128, D % 128 == 0); use sets_loss(...).backward() and optimizer.step()")
+    if rc:
+        check(rc, "adapter_train_step_sets")
+    return out[T], out[:T]
+
+
 def adapter_fwd(x, w1, b1, gamma, beta, running_mean, running_var, nbt, w2, b2, train, eps=1e-5, momentum=0.1):
     require_cuda(x, w1)
     _f32c(x)

@@ -19,7 +19,7 @@ from functools import partial
 import numpy as np
 import torch
 
-from . import adapter, ops
+from . import adapter, contrastive, ops
 from . import optim as O
 
 NEW_ORDER_FOR_PRINT = ["weighted_mean_acc", "worst_acc", "acc_0_0", "acc_0_1", "acc_1_0", "acc_1_1", "mean_acc"]
@@ -471,6 +471,112 @@ class _SingleRun:
 
     def best_model(self, r):
         return self.best
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the contrastive adapter (demo/visualizer_supcon.py: train_one_epoch_cl :412-508 inside train_all_epochs :720-772)
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _contrastive_sets(opt, table):
+    """the anchor sets of a run, built once: zero-shot slices of the train table, contrastive points, batches, order -- [n_sets, A + P +
+    N] int64 row indices into `table`; draws from the global numpy stream (contrastive.py)"""
+    if table.y_pred is None:
+        raise ValueError("train_contrastive_adapter: the train table carries no y_pred (CLIP's zero-shot predictions)")
+    y, c = table.targets.cpu().numpy(), table.targets_spurious.cpu().numpy()
+    slices, correct = contrastive.zero_shot_slices(y, table.y_pred.cpu().numpy())
+    points = contrastive.contrastive_points(y, c, slices, correct)
+    batches = contrastive.contrastive_batches(points, int(getattr(opt, "num_anchor", 1)), int(opt.num_positive), int(opt.num_negative))
+    return contrastive.contrastive_order(batches, bool(getattr(opt, "balance_by_zs_pred", False)), bool(getattr(opt, "re_shuffle_ca_loader", True)),
+                                         bool(getattr(opt, "maintain_alternative_ordering", False)))
+
+
+def _contrastive_epoch(opt, table, classifier, optimizer, epoch, order_dev, sets, contrastive_weight, tau):
+    """train_one_epoch_cl (:412-508): step idx takes the next batch_factor sets of the order (the last step may hold fewer, at the
+    same scale = contrastive_weight / batch_factor); one gather of the step's T * S rows, one sets_step, warmup_learning_rate before
+    it; steps at idx >= opt.ca_update are skipped.  The pass advances the torch stream once, like a loader; ONE host sync.  Returns
+    (mean over the epoch's sets of scale * l_t, sets trained on, steps taken)."""
+    classifier.train()
+    A, P, N = sets
+    bf = int(getattr(opt, "batch_factor", 32))
+    cap = getattr(opt, "ca_update", None)
+    scale = contrastive_weight / bf
+    _loader_base_seed()
+    n_steps = -(-order_dev.shape[0] // bf)
+    loss_sum = torch.zeros((), dtype=torch.float64, device=table.device)
+    n_sets = taken = 0
+    for idx in range(n_steps):
+        if cap is not None and idx >= cap:
+            continue
+        rows = order_dev[idx * bf:(idx + 1) * bf]
+        O.warmup_learning_rate(opt, epoch, idx, n_steps, optimizer)
+        loss, _ = classifier.sets_step(ops.gather_sets(table.embeddings, rows), optimizer, sets=(rows.shape[0], A, P, N), contrastive=(scale, tau))
+        loss_sum += loss.double()
+        n_sets += rows.shape[0]
+        taken += 1
+    return (loss_sum.item() / n_sets if n_sets else 0.0), n_sets, taken
+
+
+def train_contrastive_adapter(opt, train_table, val_table, test_table, log=None):
+    """One run of the contrastive adapter (Zhang & Re 2022), the reference's one debiasing method that needs no group labels
+    (demo/visualizer_supcon.py; dead there because its forward_ca is commented out): the anchors are the train rows CLIP's zero-shot
+    prediction (`train_table.y_pred`) got wrong, each scored against sampled positives (same class, predicted right) and negatives
+    (other class) of its own -- contrastive.py -- and the adapter is trained on scale * sum_t l_t alone (CustomCLIP.sets_step).
+
+    The epoch loop is the reference's train_all_epochs (:720-772): adjust_learning_rate, one contrastive epoch (train_one_epoch_cl),
+    validate the class prompts on the val split, keep the best worst-group model (strict `>`), validate on test; at the end the
+    zero-shot class / spurious pair of the best model.  The sets are built once, after the model is created: slices, points, batches,
+    order, from the global numpy stream.  Options (the reference's names, read with getattr): num_anchor (1), num_positive,
+    num_negative (required), batch_factor (32), ca_update (no cap), contrastive_weight (1), cl_temperature (0.1), balance_by_zs_pred
+    (False), re_shuffle_ca_loader (True), maintain_alternative_ordering (False).
+
+    Departures from the dead reference path: a step's T * S rows are ONE train-mode BatchNorm batch; no
+    ca_pre_norm and no ca_head (the adapter is fed raw embeddings, like the model that is validated and selected); the max subtracted
+    in the loss is over positives and negatives.  Two classes; single run; CustomCLIP on the adapter's fast shape.
+
+    Returns ((best train, best val, best test), (zero-shot class, zero-shot spurious)) like train_all_epochs; the train entry of a
+    contrastive epoch is {"loss": its loss average} (the reference's contrastive epoch scores no accuracy).  `log` (a list) receives
+    one record per initialisation, the sets (`kind="sets"`) and per train / validate pass; a train record carries `loss` = the mean
+    over the epoch's sets of scale * l_t, `n_sets`, `n_steps` and `order` (the sets trained on, [n_sets, S])."""
+    rec = (lambda **k: log.append(k)) if log is not None else (lambda **k: None)
+    dev = train_table.device
+    D = train_table.embeddings.shape[1]
+    classifier = adapter.CustomCLIP(adapter.Adapter(D, opt.adapter_feat_dim), opt.text_embedding_dir, opt.text_spurious_embedding_dir,
+                                    opt.text_group_embedding_dir, temperature=opt.zs_temperature)
+    rec(kind="init", state={k: v.clone() for k, v in classifier.adapter.state_dict().items()})
+    classifier = classifier.to(dev)
+    optimizer = O.set_optimizer(opt, classifier)
+    order = _contrastive_sets(opt, train_table)
+    A, P, N = int(getattr(opt, "num_anchor", 1)), int(opt.num_positive), int(opt.num_negative)
+    weight, tau = float(getattr(opt, "contrastive_weight", 1.0)), float(getattr(opt, "cl_temperature", 0.1))
+    rec(kind="sets", order=order, sets=(A, P, N))
+    order_dev = torch.from_numpy(order).to(dev)
+    ratio = train_table.group_ratio.numpy()
+    bs_eval = max(opt.batch_size, 4096)
+    best_acc, best_epoch, best = 0, 0, None
+    train_accs, val_accs, test_accs = [], [], []
+    for epoch in range(1, opt.epochs + 1):
+        O.adjust_learning_rate(opt, optimizer, epoch)
+        loss, n_sets, n_steps = _contrastive_epoch(opt, train_table, classifier, optimizer, epoch, order_dev, (A, P, N), weight, tau)
+        rec(kind="train_cl", epoch=epoch, loss=loss, n_sets=n_sets, n_steps=n_steps, order=order[:n_sets])
+        train_accs.append({"loss": loss})
+        for split, table, target, accs in (("val", val_table, opt.train_target, val_accs), ("test", test_table, "class", test_accs)):
+            st = {}
+            vloss, vacc, vg = validate(table, classifier, bs_eval, ratio, target=target, stats=st)
+            rec(kind="validate", epoch=epoch, split=split, loss=vloss, acc=vacc, group_acc=vg, counts=st["counts"])
+            accs.append(vg)
+            if split == "val" and vg["worst_acc"] > best_acc:
+                best_acc, best_epoch, best = vg["worst_acc"], epoch, deepcopy(classifier)
+    if best is None:
+        raise RuntimeError("train_contrastive_adapter: the worst-group accuracy never rose above 0, so there is no best model")
+    zero_shot = []
+    for target in ("class", "spurious"):
+        st = {}
+        zl, za, zg = validate(test_table, best, bs_eval, ratio, target=target, spurious=target == "spurious", stats=st)
+        rec(kind="validate_zs", target=target, loss=zl, acc=za, group_acc=zg, counts=st["counts"])
+        zero_shot.append(zg)
+    rec(kind="final", best_epoch=best_epoch, best_model=best)
+    e = best_epoch - 1
+    return (train_accs[e], val_accs[e], test_accs[e]), (zero_shot[0], zero_shot[1])
 
 
 def train_all_epochs(opt, train_table, val_table, test_table, input_dim=None, log=None):

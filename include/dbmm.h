@@ -623,6 +623,39 @@ int dbmm_adapter_train_step_supcon(const float* x, const int64_t* labels, float*
                                    int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* Contrastive head over sampled sets (csrc/supcon_sets.hip; Zhang & Re 2022, "Contrastive Adapters for Foundation Model Group
+ * Robustness": the reference's SupervisedContrastiveLoss, one anchor per call, for T calls at once).  z fp32 [T S][D] (D % 4 == 0):
+ * T sets of S = A + P + N rows; row 0 of a set is the anchor, rows A .. A+P-1 its positives, the last N rows its negatives; the
+ * extra anchors (rows 1 .. A-1) take no loss and get a zero gradient.
+ *   zn = z / ||z||,  c_j = zn_a . zn_j,  s_j = c_j / tau  (j in P u N),
+ *   l_t = log sum_{P u N} exp(s_j) - (1 / P) sum_P s_p,  L = scale * sum_t l_t  (the sum over t in float64, in set order).
+ * The dots are fp32 FMA chains in a fixed order; no floating-point atomics: identical inputs give identical bits.
+ * dbmm_supcon_sets_fwd, 2 launches (one workgroup per set and chunk of 32 rows; one workgroup that merges the chunk partials in a fixed
+ * order).  Outputs: loss [1] = L, loss_sets [T] = l_t (unscaled).  The workspace keeps c_j, 1 / ||z_j|| and the sets' max and sum
+ * of exp for the backward.
+ * dbmm_supcon_sets_bwd, 2 launches: dz [T S][D] = dL/dz from the forward's workspace (the same T, A, P, N, D, scale and tau).
+ * NULL pointer: DBMM_E_ARG; T < 1, A < 1, P < 1, N < 1, D <= 0, D % 4 != 0, tau <= 0, T > 65535 or T S >= 2^31: DBMM_E_SHAPE;
+ * D > 8192: DBMM_E_UNSUPPORTED; a workspace below dbmm_supcon_sets_workspace_bytes(T, S, D): DBMM_E_WORKSPACE; z, dz or the workspace
+ * not 16-byte aligned: DBMM_E_ALIGN.  Nothing is launched on refusal.  dbmm_supcon_sets_workspace_bytes is 0 for a shape that is refused. */
+size_t dbmm_supcon_sets_workspace_bytes(int64_t T, int64_t S, int64_t D);
+int dbmm_supcon_sets_fwd(const float* z, float scale, float temperature, float* loss, float* loss_sets, int64_t T, int64_t A,
+                         int64_t P, int64_t N, int64_t D, void* workspace, size_t workspace_bytes, void* stream);
+int dbmm_supcon_sets_bwd(const float* z, float scale, float temperature, float* dz, int64_t T, int64_t A, int64_t P, int64_t N,
+                         int64_t D, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One training step of the contrastive adapter in one call: dbmm_adapter_fwd (train-mode BatchNorm over the step's T S rows as ONE
+ * batch), dbmm_supcon_sets_fwd, dbmm_supcon_sets_bwd, the adapter backward, SGD-momentum on the six trainable tensors.  The step
+ * minimises L = scale * sum_t l_t and nothing else: no text matrix, no CE.  x fp32 [T S][D]; loss [1] = L, loss_sets [T] = l_t.
+ * 11 launches.  The adapter's fast shape only (H == 128, D % 128 == 0, T S <= 2^20, x 16-byte aligned; else DBMM_E_UNSUPPORTED,
+ * nothing launched); other refusals as dbmm_supcon_sets_fwd.  Workspace: dbmm_workspace_bytes_adapter_train_step_sets(T, S, D, H). */
+size_t dbmm_workspace_bytes_adapter_train_step_sets(int64_t T, int64_t S, int64_t D, int64_t H);
+int dbmm_adapter_train_step_sets(const float* x, float* w1, float* b1, float* gamma, float* beta, float* running_mean,
+                                 float* running_var, int64_t* nbt, float* w2, float* b2, float* m_w1, float* m_b1,
+                                 float* m_gamma, float* m_beta, float* m_w2, float* m_b2, float lr, float momentum,
+                                 float weight_decay, int first_step, float scale, float tau, float* loss, float* loss_sets,
+                                 int64_t T, int64_t A, int64_t P, int64_t N, int64_t D, int64_t H, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 /* Replica-batched adapter step (csrc/adapter_sweep.hip): R <= 16 independent runs of one sweep group take one training step in
  * the launches of ONE dbmm_adapter_train_step (8, or 11 with a frozen old adapter), the replica being a grid dimension.  Fast shape
  * only (H == 128, D % 128 == 0; else DBMM_E_UNSUPPORTED); replica r's results are the bits dbmm_adapter_train_step gives for r alone.
