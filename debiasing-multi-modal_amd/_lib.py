@@ -44,6 +44,8 @@ KERNEL_SOURCES = (
     ("linear_sweep_", ("linear_sweep.hip", "linear_bodies.inc", "common.h")),
     ("linear_", ("linear_step.hip", "linear_bodies.inc", "common.h")),
     ("pairdist_", ("pairdist.hip", "common.h")),
+    ("covariance_", ("covariance.hip", "common.h")),
+    ("project_rows_", ("covariance.hip", "common.h")),
     ("supcon_", ("supcon.hip", "common.h")),
     ("sets_", ("supcon_sets.hip", "common.h")),
 )
@@ -209,6 +211,9 @@ _SIGS = {
     "dbmm_group_loss_sum": [_P, _P, _P, _L, _L, _P],
     "dbmm_workspace_bytes_pairdist": [_L, _L],
     "dbmm_pairdist_group_sums": [_P, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_covariance": [_L, _L],
+    "dbmm_covariance": [_P, _P, _P, _L, _L, _P, _Z, _P],
+    "dbmm_project_rows": [_P, _P, _P, _P, _L, _L, _L, _P],
 }
 _RESTYPES = {
     "dbmm_error_string": ctypes.c_char_p,
@@ -227,6 +232,7 @@ _RESTYPES = {
     "dbmm_workspace_bytes_linear_sweep_step": c_size_t,
     "dbmm_workspace_bytes_linear_sweep_eval": c_size_t,
     "dbmm_workspace_bytes_pairdist": c_size_t,
+    "dbmm_workspace_bytes_covariance": c_size_t,
     "dbmm_supcon_workspace_bytes": c_size_t,
     "dbmm_supcon_sets_workspace_bytes": c_size_t,
     "dbmm_workspace_bytes_adapter_train_step_sets": c_size_t,

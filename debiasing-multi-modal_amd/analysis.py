@@ -1,7 +1,7 @@
 """The numerical half of the reference's representation report (VisHandler.VisRepAll, demo/visualizer.py:182-222) on the device:
 group-wise embedding statistics (GetGroupWiseStatEbd :657-690), group-wise confidences (GetGroupWiseStatConf :692-708), the
-rows nearest to a prompt embedding (find_closest_sample :19-27) and the 3 x 6 table per split.  The plotting (UMAP, MDS,
-matplotlib) is not here.
+rows nearest to a prompt embedding (find_closest_sample :19-27), the 3 x 6 table per split, and the report's map (plot_umap :311-408)
+as a PCA: the coordinates of every row, without the drawing (matplotlib) and without UMAP.
 
 The reference's `Div.` row is scipy.cdist(X, X) summed: an N x N float64 matrix per split and per group, which its own notebook
 switches off (return_dist=False) at CelebA's size.  Here it is one pass of the fused Gram-and-distance kernel
@@ -164,3 +164,126 @@ def representation_report(opt, train_table, val_table, test_table, classifier=No
         all_stats[split] = group_stats(emb, table.targets_group)
         frames.append(representation_table(all_stats[split], acc))
     return frames, all_stats
+
+
+# ---- the map: PCA in place of plot_umap's UMAP / MDS (demo/visualizer.py:311-408) -----------------------------------------------
+# PCA of the rows is classical (Torgerson) MDS of the Euclidean distances group_stats reports, it is deterministic, and a fit can
+# place other rows (val and test in train's map; the embeddings after the adapter in the map of those before).
+
+GATHER_ROWS = 4096        # rows of one group gathered at a time for its mean: a multiple of SUM_ROWS, 16 MB at D = 1024
+
+
+def pca_from_scatter(scatter, center, mean, n, k):
+    """The host step of `pca`, numpy only.  scatter float64 [D, D]: sum_i (x_i - center)(x_i - center)^T about `center` (any
+    vector near the mean); mean float64 [D]: the rows' mean; n rows.  Since sum_i (x_i - center) = n (mean - center), the scatter
+    about the mean is scatter - n (mean - center)(mean - center)^T.  Returns (components float32 [k, D] in descending variance, each
+    signed so that its entry of largest magnitude is positive; explained_variance float64 [k] = eigenvalue / (n - 1);
+    explained_variance_ratio float64 [k]; total_variance = trace / (n - 1))."""
+    scatter = np.asarray(scatter, dtype=np.float64)
+    D = scatter.shape[0]
+    if scatter.shape != (D, D) or not 1 <= k <= min(D, 8):
+        raise ValueError(f"pca: scatter {scatter.shape}, k = {k} (1..8)")
+    if n < 2:
+        raise ValueError(f"pca needs at least two rows, got {n}")
+    d = np.asarray(mean, dtype=np.float64) - np.asarray(center).astype(np.float64)
+    C = scatter - np.float64(n) * np.outer(d, d)
+    w, V = np.linalg.eigh(C)                                        # ascending
+    w, V = w[::-1][:k], V[:, ::-1][:, :k].T
+    comp = np.ascontiguousarray(V, dtype=np.float32)
+    top = np.abs(comp).argmax(axis=1)
+    comp *= np.where(comp[np.arange(k), top] < 0, np.float32(-1), np.float32(1))[:, None]
+    trace = np.trace(C)
+    ratio = w / trace if trace > 0 else np.zeros(k)
+    return comp, w / (n - 1.0), ratio, trace / (n - 1.0)
+
+
+def _group_means(x, dense, counts, center):
+    """float64 [G, D]: the groups' mean rows MINUS `center` (device fp32 [D]), GATHER_ROWS gathered rows at a time (never a sorted
+    copy of x), fixed order.  The centre is subtracted from the gathered rows before they are summed, so the fp32 block sums lose
+    2^-24 of the rows' spread, not of their distance from the origin."""
+    means = np.zeros((len(counts), x.shape[1]), dtype=np.float64)
+    for g in range(len(counts)):
+        idx = torch.from_numpy(np.flatnonzero(dense == g)).to(x.device)
+        for i in range(0, idx.numel(), GATHER_ROWS):
+            means[g] += _column_sums(ops.gather_rows(x, idx[i:i + GATHER_ROWS].contiguous()).sub_(center))
+        means[g] /= counts[g]
+    return means
+
+
+def pca(embeddings, groups=None, k=2):
+    """Principal components of a split and its rows' coordinates in them: the deterministic map of the reference's
+    representation report (plot_umap draws UMAP or MDS; PCA is classical MDS of the distances of group_stats).
+
+    `embeddings`: an EmbeddingTable (its targets_group unless `groups` is given) or a device tensor [N, D] with `groups` [N].
+    Returns {'mean' float32 [D], 'components' float32 [k, D] (descending variance, largest-magnitude entry positive),
+    'explained_variance' float64 [k] (eigenvalue / (N - 1)), 'explained_variance_ratio' [k], 'total_variance',
+    'coords' device tensor [N, k] = (x - mean) components^T, 'centroids' {'full': zeros, g: (mean_g - mean) components^T}} with
+    the groups in np.unique order.
+
+    The scatter matrix comes from the fused kernel (ops.covariance) about float32(mean) -- nothing N x D is allocated --, the
+    difference between that vector and the float64 mean is removed on the host, numpy.linalg.eigh solves the D x D float64
+    problem there, and ops.project_rows reads the rows once more for the coordinates.  The group means behind the centroids are
+    sums of gathered rows minus that centre, so they too lose precision relative to the rows' spread, wherever the split lies.
+    k outside 1..8 and fewer than two rows raise ValueError before anything is launched."""
+    x, g_np = _rows_and_groups(embeddings, groups)
+    x = x.float().contiguous()
+    n = x.shape[0]
+    if not 1 <= k <= min(x.shape[1], 8):
+        raise ValueError(f"pca: k = {k} (1..8)")
+    if n < 2:
+        raise ValueError(f"pca needs at least two rows, got {n}")
+    mean = _column_sums(x) / n
+    center = mean.astype(np.float32)
+    c_dev = torch.from_numpy(center).to(x.device)
+    scatter = ops.covariance(x, c_dev).cpu().numpy()
+    comp, var, ratio, total = pca_from_scatter(scatter, center, mean, n, k)
+    fit = {"mean": center, "components": comp, "explained_variance": var, "explained_variance_ratio": ratio, "total_variance": total}
+    fit["coords"] = ops.project_rows(x, c_dev, torch.from_numpy(comp).to(x.device))
+    uniq, dense, counts = np.unique(g_np, return_inverse=True, return_counts=True)
+    cent = _group_means(x, dense, counts, c_dev) @ comp.astype(np.float64).T
+    fit["centroids"] = {"full": np.zeros(k, dtype=np.float64)}
+    for i, g in enumerate(uniq):
+        fit["centroids"][g] = cent[i]
+    return fit
+
+
+def pca_project(fit, embeddings):
+    """coordinates (device tensor [N, k]) of another split, or of transformed embeddings, in the frame of an existing `pca` fit"""
+    x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+    return ops.project_rows(x.float().contiguous(), torch.from_numpy(fit["mean"]).to(x.device), torch.from_numpy(fit["components"]).to(x.device))
+
+
+def sample_rows(n, num_data, seed=42, offset=0):
+    """The rows plot_umap draws (demo/visualizer.py:321-334), int64 indices: all n with num_data None; with offset == 0 the
+    reference's np.random.seed(seed); np.random.choice(np.arange(n), size=min(num_data, n), replace=False) -- the same stream from a
+    private RandomState, the global one is left alone --; with offset > 0 the slice offset .. offset + num_data."""
+    if num_data is None:
+        return np.arange(n)
+    if offset == 0:
+        return np.random.RandomState(seed).choice(np.arange(n), size=min(int(num_data), n), replace=False)
+    return np.arange(n)[offset:offset + num_data]
+
+
+def projection_report(opt, train_table, val_table, test_table, transform=None, k=2, num_data=None, seed=42):
+    """VisRepAll's map without matplotlib: a PCA fitted on train's rows (`sample_rows(len(train), num_data, seed)` of them; after
+    `transform`, a callable emb -> emb such as classifier.adapter, applied batch by batch in eval mode) and all three splits in that
+    one frame.  Returns ({'train': s, 'val': s, 'test': s}, fit) with s = {'coords' numpy [n, k], 'rows' (indices into the table),
+    'groups', 'targets', 'spurious'} and fit = `pca`'s dict of the train rows."""
+    bs = max(int(getattr(opt, "batch_size", 0) or 0), 4096)
+    out, fit = {}, None
+    for split, table in (("train", train_table), ("val", val_table), ("test", test_table)):
+        rows = sample_rows(len(table), num_data, seed)
+        emb = table.embeddings if transform is None else _transformed(table, transform, bs)
+        if num_data is not None:
+            emb = ops.gather_rows(emb, torch.from_numpy(rows.astype(np.int64)).to(emb.device))
+        groups = table.group_array[rows]
+        if fit is None:
+            fit = pca(emb, groups, k)
+            coords = fit["coords"]
+        else:
+            coords = pca_project(fit, emb)
+        out[split] = {"coords": coords.cpu().numpy(), "rows": rows, "groups": groups,
+                      "targets": table.targets.cpu().numpy()[rows], "spurious": table.targets_spurious.cpu().numpy()[rows]}
+    return out, fit

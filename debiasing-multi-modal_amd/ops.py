@@ -1357,6 +1357,57 @@ def pairdist_group_sums(x, groups, n_groups, center):
     return out
 
 
+def _pca_operands(what, x, center):
+    require_cuda(x, center)
+    _f32c(x)
+    _f32c(center)
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise _lib.DbmmError(f"{what}: x must be [N, D] with N >= 1, got {tuple(x.shape)}")
+    N, D = x.shape
+    _sized(f"{what}: center", center, D)
+    if center.device != x.device:
+        raise _lib.DbmmError(f"{what}: center is on {center.device}, x on {x.device}")
+    if D % 64 or D > 4096:
+        raise DbmmUnsupported(f"{what}: D = {D}; the kernel serves D % 64 == 0, D <= 4096")
+    return N, D
+
+
+def covariance(x, center):
+    """S float64 [D, D]: S[a, b] = sum_i (x[i, a] - center[a]) (x[i, b] - center[b]), about the given center exactly, on the fused
+    scatter kernel (dbmm_covariance): no centred copy of x, exact fp32 products, no fp32 chain longer than 1024 rows, float64 sums
+    in a fixed order; symmetric to the bit and the same bits on every call.  x fp32 [N, D] (D % 64 == 0, D <= 4096), center fp32
+    [D]: a vector near the rows' mean."""
+    N, D = _pca_operands("covariance", x, center)
+    L = _lib.lib()
+    nbytes = L.dbmm_workspace_bytes_covariance(N, D)
+    ws = _empty((nbytes + 7) // 8, device=x.device, dtype=torch.float64)            # the partial tiles: sized by (N, D), not cached
+    out = _empty((D, D), device=x.device, dtype=torch.float64)
+    rc = L.dbmm_covariance(x.data_ptr(), center.data_ptr(), out.data_ptr(), N, D, ws.data_ptr(), ws.numel() * 8, stream())
+    if rc == _lib.E_UNSUPPORTED:
+        raise DbmmUnsupported(f"covariance: no kernel for N = {N}, D = {D}")
+    check(rc, "covariance")
+    return out
+
+
+def project_rows(x, center, basis):
+    """y fp32 [N, K] = (x - center) @ basis.T in one read of x (dbmm_project_rows): basis fp32 [K, D], K in 1..8.  A row's
+    coordinates do not depend on the other rows: projecting a slice gives the bits of the slice of the projection."""
+    N, D = _pca_operands("project_rows", x, center)
+    require_cuda(basis)
+    _f32c(basis)
+    if basis.dim() != 2 or basis.shape[1] != D or not 1 <= basis.shape[0] <= 8:
+        raise _lib.DbmmError(f"project_rows: basis must be [K, {D}] with K in 1..8, got {tuple(basis.shape)}")
+    if basis.device != x.device:
+        raise _lib.DbmmError(f"project_rows: basis is on {basis.device}, x on {x.device}")
+    K = basis.shape[0]
+    out = _empty((N, K), device=x.device, dtype=torch.float32)
+    rc = _lib.lib().dbmm_project_rows(x.data_ptr(), center.data_ptr(), basis.data_ptr(), out.data_ptr(), N, D, K, stream())
+    if rc == _lib.E_UNSUPPORTED:
+        raise DbmmUnsupported(f"project_rows: no kernel for N = {N}, D = {D}")
+    check(rc, "project_rows")
+    return out
+
+
 # ---- fp16 mode of the transformer towers (csrc/f16_ops.hip) -------------------------------------------------------
 
 def _f16c(t):

@@ -772,6 +772,28 @@ size_t dbmm_workspace_bytes_pairdist(int64_t N, int64_t D);
 int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N,
                              int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream);
 
+/* PCA of an embedding split: the scatter matrix without a centred copy of the rows (the deterministic map that stands in for the
+ * UMAP / MDS projection of plot_umap, demo/visualizer.py:311-408; classical MDS of the distances dbmm_pairdist_group_sums reports):
+ *   scatter double [D][D]: scatter[a][b] = sum_i (x[i][a] - center[a]) (x[i][b] - center[b]), about the GIVEN center exactly.
+ * x fp32 [N][D] (contiguous), center fp32 [D]: any vector near the rows' mean -- it is subtracted on load; the caller removes
+ * N (mean - center)(mean - center)^T in float64.  Exact fp32 products (v_mfma_f32_32x32x2_f32) over 64 x 64 tiles of the upper
+ * triangle; no fp32 accumulation chain is longer than 1024 rows: every 1024 rows the tile is added to a float64 running tile.  A
+ * workgroup owns one (tile, row range); the number of row ranges depends on (N, D) only, and a second launch adds the float64
+ * partial tiles in range order and mirrors them: scatter is symmetric to the bit and two calls give the same bits.  Two launches on
+ * `stream`, no memset, no floating-point atomics.
+ * D % 64 != 0 or D > 4096: DBMM_E_UNSUPPORTED; N outside 1..2^23: DBMM_E_SHAPE; x, center and the workspace 16-byte aligned.  The
+ * workspace holds the partial tiles only (32 KB per tile and row range, about 26 MB at D = 1024), never N x anything. */
+size_t dbmm_workspace_bytes_covariance(int64_t N, int64_t D);
+int dbmm_covariance(const float* x, const float* center, double* scatter, int64_t N, int64_t D, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
+/* y fp32 [N][K] = (x - center) . basis^T: the coordinates of the rows in a fitted basis fp32 [K][D], K in 1..8 (else DBMM_E_SHAPE).
+ * One read of x: a wave takes four rows at a time, float4 loads, one fp32 fmaf chain per (row, component) and a fixed shuffle tree,
+ * so a row's coordinates do not depend on its neighbours or on N.  Shape and alignment rules of dbmm_covariance (basis too).  One
+ * launch on `stream`. */
+int dbmm_project_rows(const float* x, const float* center, const float* basis, float* y, int64_t N, int64_t D, int64_t K,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
