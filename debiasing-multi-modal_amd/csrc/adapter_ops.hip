@@ -4,18 +4,7 @@
 // SGD-momentum update and the per-group accuracy counters.  These are HBM/launch-bound
 // (arithmetic intensity ~1 FLOP/B); the four GEMM-shaped products go through
 // dbmm_gemm_bias_act (fp32 MFMA).
-#include "common.h"
-
-// adapter_step.hip: the products of the step for the reference's shapes (H = 128, D % 128 == 0)
-bool dbmm_adapter_fast_shape(int64_t B, int64_t D, int64_t H);
-size_t dbmm_adapter_bwd_fast_floats(int64_t B, int64_t D);
-int dbmm_adapter_fwd_fast(const float* x, const float* w1, const float* b1, const float* gamma, const float* beta, float* running_mean,
-                          float* running_var, int64_t* nbt, const float* w2, const float* b2, float* h, float* mean, float* invstd, float* r,
-                          float* z, int64_t B, int64_t D, int train, float eps, float momentum, hipStream_t s);
-int dbmm_adapter_bwd_fast(const float* x, const float* dz, const float* h, const float* mean, const float* invstd, const float* r, const float* gamma,
-                          const float* beta, const float* w2, float* dw1, float* db1, float* dgamma, float* dbeta, float* dw2, float* db2,
-                          float* dh, float* scratch, int64_t B, int64_t D, hipStream_t s, const float** dw1part = nullptr,
-                          const float** db1part = nullptr, int* nsplit = nullptr, const float* loss_rows = nullptr, float* loss_mean = nullptr);
+#include "adapter_step.h"
 
 namespace {
 
@@ -368,7 +357,7 @@ extern "C" int dbmm_adapter_fwd(const float* x, const float* w1, const float* b1
 
 // dr [B][H] | dh [B][H] | the fast path's partial sums (adapter_step.hip)
 extern "C" size_t dbmm_workspace_bytes_adapter_bwd(int64_t B, int64_t D, int64_t H) {
-    return ((size_t)(2 * B * H) + (dbmm_adapter_fast_shape(B, D, H) ? dbmm_adapter_bwd_fast_floats(B, D) : 0)) * sizeof(float);
+    return ((size_t)(2 * B * H) + (dbmm_adapter_fast_shape(B, D, H) ? dbmm_adapter_bwd_scratch(B, D).total : 0)) * sizeof(float);
 }
 
 extern "C" int dbmm_adapter_bwd(const float* x, const float* dz, const float* h, const float* mean,
@@ -387,7 +376,7 @@ extern "C" int dbmm_adapter_bwd(const float* x, const float* dz, const float* h,
     float* dh = dr + B * H;
     if (dbmm_adapter_fast_shape(B, D, H) && dbmm_aligned16(x) && dbmm_aligned16(dz) && dbmm_aligned16(r) && dbmm_aligned16(w2) && dbmm_aligned16(dw1) &&
         dbmm_aligned16(dw2) && dbmm_aligned16(db1) && dbmm_aligned16(db2) && dbmm_opt(OPT_ADAPTER_STEP_FUSED))
-        return dbmm_adapter_bwd_fast(x, dz, h, mean, invstd, r, gamma, beta, w2, dw1, db1, dgamma, dbeta, dw2, db2, dh, dh + B * H, B, D, s);
+        return dbmm_adapter_bwd_fast(x, dz, h, mean, invstd, r, gamma, beta, w2, dw1, db1, dgamma, dbeta, dw2, db2, dh, dh + B * H, B, D, s, true, nullptr, nullptr);
     int rc;
     // dW2[D][H] = dz^T r   (reduction over the batch: both operands K-major)
     rc = dbmm_gemm_bias_act(dz, D, 1, r, H, 1, nullptr, nullptr, 0, dw2, H, D, H, B, 1.f, DBMM_ACT_NONE, stream);
@@ -448,14 +437,11 @@ extern "C" int dbmm_l2norm_sim_ce_fwd(const float* z, const float* z_old, float 
     if (!dbmm_aligned16(z) || !dbmm_aligned16(tn) || (z_old && !dbmm_aligned16(z_old))) return DBMM_E_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((B + 3) / 4));
-    if (C <= 4)
-        hipLaunchKernelGGL(l2norm_sim_ce_fwd_kernel<4>, grid, dim3(256), 0, s, z, z_old, ebd_weight, tn,
+    dbmm_with_cmax(C, [&](auto cm) {
+        hipLaunchKernelGGL(l2norm_sim_ce_fwd_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, z, z_old, ebd_weight, tn,
                            (const long long*)labels, 1.f / temperature, logits, loss_rows, (long long*)pred, inv_norm,
                            (int)B, (int)(D / 4), (int)C);
-    else
-        hipLaunchKernelGGL(l2norm_sim_ce_fwd_kernel<8>, grid, dim3(256), 0, s, z, z_old, ebd_weight, tn,
-                           (const long long*)labels, 1.f / temperature, logits, loss_rows, (long long*)pred, inv_norm,
-                           (int)B, (int)(D / 4), (int)C);
+    });
     DBMM_CHECK_LAUNCH();
     if (loss_mean) {
         hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(256), 0, s, loss_rows, (int)B, loss_mean);
@@ -476,12 +462,10 @@ extern "C" int dbmm_l2norm_sim_ce_bwd(const float* z, const float* inv_norm, flo
     const float gs = grad_scale / (float)B;
     const dim3 grid((unsigned)((B + 3) / 4));
     hipStream_t s = (hipStream_t)stream;
-    if (C <= 4)
-        hipLaunchKernelGGL(l2norm_sim_ce_bwd_kernel<4>, grid, dim3(256), 0, s, z, inv_norm, w_new, tn, logits,
+    dbmm_with_cmax(C, [&](auto cm) {
+        hipLaunchKernelGGL(l2norm_sim_ce_bwd_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, z, inv_norm, w_new, tn, logits,
                            (const long long*)labels, dlogits, 1.f / temperature, gs, dz, (int)B, (int)(D / 4), (int)C);
-    else
-        hipLaunchKernelGGL(l2norm_sim_ce_bwd_kernel<8>, grid, dim3(256), 0, s, z, inv_norm, w_new, tn, logits,
-                           (const long long*)labels, dlogits, 1.f / temperature, gs, dz, (int)B, (int)(D / 4), (int)C);
+    });
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
 }
@@ -505,40 +489,12 @@ extern "C" int dbmm_l2norm_sim_ce_bwd_weighted(const float* z, const float* inv_
     const float w_new = blended ? (1.f - ebd_weight) : 1.f;
     const dim3 grid((unsigned)((B + 3) / 4));
     hipStream_t s = (hipStream_t)stream;
-    if (C <= 4)
-        hipLaunchKernelGGL(l2norm_sim_ce_bwd_w_kernel<4>, grid, dim3(256), 0, s, z, inv_norm, w_new, tn, logits, (const long long*)labels,
-                           (const long long*)groups, weights, (int)G, 1.f / temperature, dz, (int)B, (int)(D / 4), (int)C);
-    else
-        hipLaunchKernelGGL(l2norm_sim_ce_bwd_w_kernel<8>, grid, dim3(256), 0, s, z, inv_norm, w_new, tn, logits, (const long long*)labels,
-                           (const long long*)groups, weights, (int)G, 1.f / temperature, dz, (int)B, (int)(D / 4), (int)C);
+    dbmm_with_cmax(C, [&](auto cm) {
+        hipLaunchKernelGGL(l2norm_sim_ce_bwd_w_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, z, inv_norm, w_new, tn, logits,
+                           (const long long*)labels, (const long long*)groups, weights, (int)G, 1.f / temperature, dz, (int)B, (int)(D / 4), (int)C);
+    });
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
-}
-
-// forward + backward of the cosine-logits / CE head in one launch (the one-call step): logits, per-row losses, dz
-static int ce_fwdbwd(const float* z, const float* z_old, float ebd_weight, const float* tn, const int64_t* labels, float temperature,
-                     float* logits, float* loss_rows, float* dz, int64_t B, int64_t D, int64_t C, void* stream) {
-    const float w_new = z_old ? (1.f - ebd_weight) : 1.f;
-    const float gs = 1.f / (float)B;
-    const dim3 grid((unsigned)((B + 3) / 4));
-    hipStream_t s = (hipStream_t)stream;
-    if (C <= 4)
-        hipLaunchKernelGGL(l2norm_sim_ce_fwdbwd_kernel<4>, grid, dim3(256), 0, s, z, z_old, ebd_weight, w_new, tn, (const long long*)labels,
-                           1.f / temperature, gs, logits, loss_rows, dz, (int)B, (int)(D / 4), (int)C);
-    else
-        hipLaunchKernelGGL(l2norm_sim_ce_fwdbwd_kernel<8>, grid, dim3(256), 0, s, z, z_old, ebd_weight, w_new, tn, (const long long*)labels,
-                           1.f / temperature, gs, logits, loss_rows, dz, (int)B, (int)(D / 4), (int)C);
-    DBMM_CHECK_LAUNCH();
-    return DBMM_OK;
-}
-
-static int sgd_impl(int64_t n, float* const* params, const float* const* grads, float* const* bufs, const int64_t* sizes, const int* nsplit,
-                    float lr, float momentum, float weight_decay, int first_step, void* stream);
-
-extern "C" int dbmm_sgd_momentum(int64_t n, float* const* params, const float* const* grads, float* const* bufs,
-                                 const int64_t* sizes, float lr, float momentum, float weight_decay, int first_step,
-                                 void* stream) {
-    return sgd_impl(n, params, grads, bufs, sizes, nullptr, lr, momentum, weight_decay, first_step, stream);
 }
 
 static int sgd_impl(int64_t n, float* const* params, const float* const* grads, float* const* bufs, const int64_t* sizes, const int* nsplit,
@@ -558,6 +514,12 @@ static int sgd_impl(int64_t n, float* const* params, const float* const* grads, 
                        weight_decay, first_step);
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
+}
+
+extern "C" int dbmm_sgd_momentum(int64_t n, float* const* params, const float* const* grads, float* const* bufs,
+                                 const int64_t* sizes, float lr, float momentum, float weight_decay, int first_step,
+                                 void* stream) {
+    return sgd_impl(n, params, grads, bufs, sizes, nullptr, lr, momentum, weight_decay, first_step, stream);
 }
 
 extern "C" int dbmm_group_count(const float* logits, const int64_t* y, const int64_t* g, int64_t* counts, int64_t B,
@@ -593,133 +555,198 @@ extern "C" int dbmm_gather_rows(const float* table, const int64_t* idx, float* o
 }
 
 // ---- one call = one training step body (final_main.py:455-466 / :610-623) ----------------------
-// workspace layout (floats): h, r [B*H]x2 | z [B*D] | mean, invstd [H]x2 | (old: h, r, z, mean, invstd)
-// | inv_norm [B] | dz [B*D] | dw1 [H*D] db1 dgamma dbeta [H]x3 dw2 [D*H] db2 [D] | bwd scratch [2*B*H + B*D]
-static size_t train_step_floats(int64_t B, int64_t D, int64_t H, int with_old) {
-    size_t n = 2 * B * H + B * D + 2 * H;
-    if (with_old) n += 2 * B * H + B * D + 2 * H;
-    n += B + B * D + (H * D + 3 * H + D * H + D) + dbmm_workspace_bytes_adapter_bwd(B, D, H) / sizeof(float);
-    return (n + 3) / 4 * 4 + 64;
+namespace {
+
+// the step's workspace, as offsets in floats: h, r [B*H]x2 | z [B*D] | mean, invstd [H]x2 | (old: the same five) | (inv_norm [B])
+// | dz [B*D] | dw1 [H*D] db1 dgamma dbeta [H]x3 dw2 [D*H] db2 [D] | bwd scratch (dbmm_workspace_bytes_adapter_bwd).  Every region
+// is a multiple of 4 floats (16-B aligned) and so is `total`: a head's workspace follows the step's, 64 floats off its grid.
+struct ActOffsets {
+    size_t h, r, z, mean, invstd;
+};
+struct StepWs {
+    ActOffsets a, o;
+    size_t inv_norm, dz, g[6], bws, total;
+    int64_t gn[6];          // sizes of the six gradients (dw1, db1, dgamma, dbeta, dw2, db2), the order of AdapterMomentum
+};
+StepWs step_ws(int64_t B, int64_t D, int64_t H, bool with_old, bool with_inv_norm) {
+    StepWs L{};
+    const int64_t gn[6] = {H * D, H, H, H, D * H, D};
+    size_t f = 0;
+    auto take = [&](size_t n) { const size_t o = f; f += (n + 3) / 4 * 4; return o; };
+    auto acts = [&] { return ActOffsets{take(B * H), take(B * H), take(B * D), take(H), take(H)}; };      // braces: evaluated in order
+    L.a = acts();
+    if (with_old) L.o = acts();
+    if (with_inv_norm) L.inv_norm = take(B);
+    L.dz = take(B * D);
+    for (int i = 0; i < 6; ++i) {
+        L.gn[i] = gn[i];
+        L.g[i] = take(gn[i]);
+    }
+    L.bws = take(dbmm_workspace_bytes_adapter_bwd(B, D, H) / sizeof(float));
+    // 64 floats between the step's regions and a head's workspace: every region above is a multiple of 512 bytes at the reference's shapes, and
+    // the contrastive head's Gram tiles on that same grid cost the mixed step 0.6 us of 141 (HISTORY.md); sizes equal the earlier ones
+    L.total = f + 64;
+    return L;
 }
 
-extern "C" size_t dbmm_workspace_bytes_adapter_train_step(int64_t B, int64_t D, int64_t H, int with_old) {
-    return train_step_floats(B, D, H, with_old) * sizeof(float);
+// nbt (num_batches_tracked) is optional
+bool complete(const FrozenAdapter& p) { return p.w1 && p.b1 && p.gamma && p.beta && p.rmean && p.rvar && p.w2 && p.b2; }
+bool complete(const AdapterMomentum& m) { return m.w1 && m.b1 && m.gamma && m.beta && m.w2 && m.b2; }
+
+// forward of one adapter with train-mode BatchNorm1d (its defaults: eps 1e-5, momentum 0.1) into its activations
+int fwd_train(const float* x, const FrozenAdapter& p, float* f, const ActOffsets& a, int64_t B, int64_t D, int64_t H, void* stream) {
+    return dbmm_adapter_fwd(x, p.w1, p.b1, p.gamma, p.beta, p.rmean, p.rvar, (int64_t*)p.nbt, p.w2, p.b2, f + a.h, f + a.mean, f + a.invstd, f + a.r,
+                            f + a.z, B, D, H, 1, 1e-5f, 0.1f, stream);
 }
 
-// `groups` given: the group-DRO step (q [G] updated in place, loss_mean = the robust loss); `con_loss` given: the ERM step with the
-// supervised-contrastive head on top (loss_mean = the mixed loss; supcon.hip); else the ERM step
-static int train_step_impl(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
-                           float* beta, float* rmean, float* rvar, int64_t* nbt, float* w2, float* b2,
-                           float* m_w1, float* m_b1, float* m_gamma, float* m_beta, float* m_w2,
-                           float* m_b2, const float* o_w1, const float* o_b1, const float* o_gamma,
-                           const float* o_beta, float* o_rmean, float* o_rvar, int64_t* o_nbt,
-                           const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
-                           float temperature, float lr, float momentum, float weight_decay,
-                           int first_step, float* logits, float* loss_rows, float* loss_mean, const int64_t* groups, float* q, float eta,
-                           int64_t G, float con_w, float con_tau, float* con_loss, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
-                           void* stream) {
-    if (!x || !labels || !w1 || !b1 || !gamma || !beta || !rmean || !rvar || !w2 || !b2 || !m_w1 || !m_b1 ||
-        !m_gamma || !m_beta || !m_w2 || !m_b2 || !tn || !logits || !loss_rows || !loss_mean || !workspace)
+// what the cosine-logits heads read and write: z of the trainable branch and of the frozen one (or null), the prompts; logits,
+// per-row losses, 1 / ||z|| and dz.  `fast`: the step runs on the purpose-built kernels (adapter_step.hip)
+struct HeadIo {
+    const float *z, *oz, *tn;
+    const int64_t* labels;
+    float ebd_weight, temperature;
+    float *logits, *loss_rows, *inv_norm, *dz;
+    int64_t B, D, C;
+    bool fast;
+    void* stream;
+};
+struct GdroHead {
+    const int64_t* groups;
+    float* q;
+    float eta;
+    int64_t G;
+};
+struct SupconHead {
+    float weight, tau;
+    float* loss;
+};
+
+// plain CE.  fast: forward AND backward of a row are one launch (row-local) and the batch mean of the losses rides in a spare block
+// of the backward's first launch (*spare); else the two stand-alone calls, the first one followed by the mean's launch -- the same
+// statements, hence the same bits.  `loss_mean` null: a head on top of this one writes the loss
+int head_ce(const HeadIo& io, float* loss_mean, bool* spare) {
+    *spare = io.fast && loss_mean;
+    if (io.fast) {
+        const float w_new = io.oz ? (1.f - io.ebd_weight) : 1.f;
+        dbmm_with_cmax(io.C, [&](auto cm) {
+            hipLaunchKernelGGL(l2norm_sim_ce_fwdbwd_kernel<decltype(cm)::value>, dim3((unsigned)((io.B + 3) / 4)), dim3(256), 0,
+                               (hipStream_t)io.stream, io.z, io.oz, io.ebd_weight, w_new, io.tn, (const long long*)io.labels, 1.f / io.temperature,
+                               1.f / (float)io.B, io.logits, io.loss_rows, io.dz, (int)io.B, (int)(io.D / 4), (int)io.C);
+        });
+        DBMM_CHECK_LAUNCH();
+        return DBMM_OK;
+    }
+    const int rc = dbmm_l2norm_sim_ce_fwd(io.z, io.oz, io.ebd_weight, io.tn, io.labels, io.temperature, io.logits, io.loss_rows, loss_mean, nullptr,
+                                          io.inv_norm, io.B, io.D, io.C, io.stream);
+    if (rc) return rc;
+    return dbmm_l2norm_sim_ce_bwd(io.z, io.inv_norm, io.ebd_weight, io.oz != nullptr, io.tn, io.logits, io.labels, nullptr, io.temperature, 1.f,
+                                  io.dz, io.B, io.D, io.C, io.stream);
+}
+
+// group DRO: a row's weight needs the whole batch's losses, so the head is three launches -- forward rows, the group reduction + q
+// update (one workgroup), weighted backward rows; the robust loss is written by the second.  The [3][G] statistics live in `stats`
+// (the start of the backward scratch, unused until then).
+int head_gdro(const HeadIo& io, const GdroHead& g, float* stats, float* robust_loss) {
+    int rc = dbmm_l2norm_sim_ce_fwd(io.z, io.oz, io.ebd_weight, io.tn, io.labels, io.temperature, io.logits, io.loss_rows, nullptr, nullptr,
+                                    io.inv_norm, io.B, io.D, io.C, io.stream);
+    if (rc) return rc;
+    rc = dbmm_group_dro_weights(io.loss_rows, g.groups, g.q, g.q, stats, robust_loss, io.B, g.G, g.eta, io.stream);
+    if (rc) return rc;
+    return dbmm_l2norm_sim_ce_bwd_weighted(io.z, io.inv_norm, io.ebd_weight, io.oz != nullptr, io.tn, io.logits, io.labels, g.groups, stats, g.G,
+                                           io.temperature, io.dz, io.B, io.D, io.C, io.stream);
+}
+
+// CE + the supervised-contrastive head (supcon.hip), which reads the trainable branch's z against itself: Gram tiles, the reduction
+// (which also takes the mean of the CE rows and writes the mixed loss), and the backward onto the CE head's dz in place.  The
+// statistics live in the spare floats of the contrastive workspace `cws`.
+int head_ce_supcon(const HeadIo& io, const SupconHead& c, float* mixed_loss, void* cws, size_t cbytes) {
+    bool spare;
+    int rc = head_ce(io, nullptr, &spare);
+    if (rc) return rc;
+    float* sp = dbmm_supcon_spare(cws, io.B);
+    rc = dbmm_supcon_fwd(io.z, io.labels, c.tau, io.loss_rows, c.weight, c.loss, mixed_loss, sp + 4 * io.B, sp, sp + 5 * io.B, io.B, io.D, cws,
+                         cbytes, io.stream);
+    if (rc) return rc;
+    return dbmm_supcon_bwd(io.z, io.labels, c.tau, sp, sp + 5 * io.B, c.weight, io.dz, 1.f - c.weight, io.dz, io.B, io.D, cws, cbytes, io.stream);
+}
+
+// the contrastive loss of T sampled sets (supcon_sets.hip) and its gradient
+int head_sets(const float* z, float* dz, float scale, float tau, float* loss, float* loss_sets, int64_t T, int64_t A, int64_t P, int64_t N, int64_t D,
+              void* hws, size_t hbytes, void* stream) {
+    const int rc = dbmm_supcon_sets_fwd(z, scale, tau, loss, loss_sets, T, A, P, N, D, hws, hbytes, stream);
+    if (rc) return rc;
+    return dbmm_supcon_sets_bwd(z, scale, tau, dz, T, A, P, N, D, hws, hbytes, stream);
+}
+
+// the tail of every step: adapter backward from dz, then SGD.  fast: the batch-split dW1 / db1 partial sums stay in the backward's
+// scratch and are summed inside the SGD launch, and `loss_mean` given has the backward's spare block write the mean of loss_rows
+int bwd_sgd(const float* x, const AdapterParams& p, const AdapterMomentum& m, const SgdScalars& sc, float* f, const StepWs& L, bool fast,
+            const float* loss_rows, float* loss_mean, int64_t B, int64_t D, int64_t H, void* stream) {
+    float* ps[6] = {p.w1, p.b1, p.gamma, p.beta, p.w2, p.b2};
+    float* ms[6] = {m.w1, m.b1, m.gamma, m.beta, m.w2, m.b2};
+    float* gs[6];
+    for (int i = 0; i < 6; ++i) gs[i] = f + L.g[i];
+    const float *dz = f + L.dz, *h = f + L.a.h, *mean = f + L.a.mean, *invstd = f + L.a.invstd, *r = f + L.a.r;
+    float* bws = f + L.bws;                                               // dr [B*H] | dh [B*H] | the fast path's scratch
+    if (!fast) {
+        const int rc = dbmm_adapter_bwd(x, dz, h, mean, invstd, r, p.gamma, p.beta, p.w2, gs[0], gs[1], gs[2], gs[3], gs[4], gs[5], B, D, H, bws,
+                                        dbmm_workspace_bytes_adapter_bwd(B, D, H), stream);
+        if (rc) return rc;
+        return sgd_impl(6, ps, gs, ms, L.gn, nullptr, sc.lr, sc.momentum, sc.weight_decay, sc.first_step, stream);
+    }
+    const BwdScratch S = dbmm_adapter_bwd_scratch(B, D);
+    float* scratch = bws + 2 * B * H;
+    const int rc = dbmm_adapter_bwd_fast(x, dz, h, mean, invstd, r, p.gamma, p.beta, p.w2, gs[0], gs[1], gs[2], gs[3], gs[4], gs[5], bws + B * H,
+                                         scratch, B, D, (hipStream_t)stream, false, loss_rows, loss_mean);
+    if (rc) return rc;
+    gs[0] = scratch + S.dw1part;
+    gs[1] = scratch + S.db1part;
+    const int nsp[6] = {S.NS, S.NS, 1, 1, 1, 1};
+    return sgd_impl(6, ps, gs, ms, L.gn, nsp, sc.lr, sc.momentum, sc.weight_decay, sc.first_step, stream);
+}
+
+// `gdro.groups` given: the group-DRO step (q [G] updated in place, loss_mean = the robust loss); `con.loss` given: the ERM step with the
+// supervised-contrastive head on top (loss_mean = the mixed loss); else the ERM step.  `old`: the frozen adapter, or none (w1 null)
+int train_step_impl(const float* x, const int64_t* labels, const AdapterParams& p, const AdapterMomentum& m, const FrozenAdapter& old,
+                    float ebd_weight, const float* tn, float temperature, const SgdScalars& sc, float* logits, float* loss_rows, float* loss_mean,
+                    const GdroHead& gdro, const SupconHead& con, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    if (!x || !labels || !complete(p.forward_only()) || !complete(m) || !tn || !logits || !loss_rows || !loss_mean || !workspace)
         return DBMM_E_ARG;
-    const int with_old = o_w1 != nullptr;
-    if (with_old && (!o_b1 || !o_gamma || !o_beta || !o_rmean || !o_rvar || !o_w2 || !o_b2)) return DBMM_E_ARG;
+    const bool with_old = old.w1 != nullptr, with_con = con.loss != nullptr;
+    if (with_old && !complete(old)) return DBMM_E_ARG;
     if (B < 2 || D <= 0 || H <= 0 || (D & 3) || (H & 3) || C <= 0 || C > 8) return DBMM_E_SHAPE;
-    const size_t step_bytes = dbmm_workspace_bytes_adapter_train_step(B, D, H, with_old);
-    if (con_loss) {
-        if (!(con_tau > 0.f)) return DBMM_E_SHAPE;
-        if (!dbmm_supcon_workspace_bytes(B, D)) return DBMM_E_UNSUPPORTED;       // B > 2048: nothing has been launched
-        if (workspace_bytes < step_bytes + dbmm_supcon_workspace_bytes(B, D)) return DBMM_E_WORKSPACE;
+    const StepWs L = step_ws(B, D, H, with_old, true);
+    const size_t step_bytes = L.total * sizeof(float), cbytes = with_con ? dbmm_supcon_workspace_bytes(B, D) : 0;
+    if (with_con) {
+        if (!(con.tau > 0.f)) return DBMM_E_SHAPE;
+        if (!cbytes) return DBMM_E_UNSUPPORTED;                                  // B > 2048: nothing has been launched
+        if (workspace_bytes < step_bytes + cbytes) return DBMM_E_WORKSPACE;
     }
     if (workspace_bytes < step_bytes) return DBMM_E_WORKSPACE;
     if (!dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
-    auto up4 = [](size_t n) { return (n + 3) / 4 * 4; };
     float* f = (float*)workspace;
-    float* h = f;            f += up4(B * H);
-    float* r = f;            f += up4(B * H);
-    float* z = f;            f += up4(B * D);
-    float* mean = f;         f += up4(H);
-    float* invstd = f;       f += up4(H);
-    float *oh = nullptr, *orr = nullptr, *oz = nullptr, *omean = nullptr, *oinv = nullptr;
-    if (with_old) {
-        oh = f; f += up4(B * H); orr = f; f += up4(B * H); oz = f; f += up4(B * D);
-        omean = f; f += up4(H); oinv = f; f += up4(H);
-    }
-    float* inv_norm = f;     f += up4(B);
-    float* dz = f;           f += up4(B * D);
-    float* dw1 = f;          f += up4(H * D);
-    float* db1 = f;          f += up4(H);
-    float* dgamma = f;       f += up4(H);
-    float* dbeta = f;        f += up4(H);
-    float* dw2 = f;          f += up4(D * H);
-    float* db2 = f;          f += up4(D);
-    float* bws = f;
-    const float eps = 1e-5f, bn_momentum = 0.1f;
-    int rc;
-    rc = dbmm_adapter_fwd(x, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, h, mean, invstd, r, z, B, D, H, 1, eps,
-                          bn_momentum, stream);
+    int rc = fwd_train(x, p.forward_only(), f, L.a, B, D, H, stream);
     if (rc) return rc;
     if (with_old) {   // frozen branch: forward only, but BatchNorm still in train mode
-        rc = dbmm_adapter_fwd(x, o_w1, o_b1, o_gamma, o_beta, o_rmean, o_rvar, o_nbt, o_w2, o_b2, oh, omean, oinv, orr,
-                              oz, B, D, H, 1, eps, bn_momentum, stream);
+        rc = fwd_train(x, old, f, L.o, B, D, H, stream);
         if (rc) return rc;
     }
-    // one-call step on the purpose-built kernels: cosine logits + CE forward AND backward are one launch (row-local), the batch
-    // mean of the losses rides in a spare block of the next launch, the sums of the batch-split dW1 / db1 partials in the SGD
-    // launch -- the same statements as the stand-alone launches the autograd path uses, hence the same bits
     const bool fast = dbmm_adapter_fast_shape(B, D, H) && dbmm_opt(OPT_ADAPTER_STEP_FUSED) && dbmm_aligned16(x);
-    if (groups) {
-        // group DRO: a row's weight needs the whole batch's losses, so the head is three launches -- forward rows, the group
-        // reduction + q update (one workgroup), weighted backward rows; the robust loss is written by the second, so the backward's
-        // spare loss-mean block is not launched.  The [3][G] statistics live at the start of the backward scratch (unused until then).
-        rc = dbmm_l2norm_sim_ce_fwd(z, oz, ebd_weight, tn, labels, temperature, logits, loss_rows, nullptr, nullptr, inv_norm, B, D, C, stream);
-        if (rc) return rc;
-        rc = dbmm_group_dro_weights(loss_rows, groups, q, q, bws, loss_mean, B, G, eta, stream);
-        if (rc) return rc;
-        rc = dbmm_l2norm_sim_ce_bwd_weighted(z, inv_norm, ebd_weight, with_old, tn, logits, labels, groups, bws, G, temperature, dz, B, D, C, stream);
-        if (rc) return rc;
-    } else if (fast) {
-        if ((D & 3) || C <= 0 || C > 8) return DBMM_E_SHAPE;
-        rc = ce_fwdbwd(z, oz, ebd_weight, tn, labels, temperature, logits, loss_rows, dz, B, D, C, stream);
-        if (rc) return rc;
-    } else {
-        rc = dbmm_l2norm_sim_ce_fwd(z, oz, ebd_weight, tn, labels, temperature, logits, loss_rows, con_loss ? nullptr : loss_mean, nullptr, inv_norm,
-                                    B, D, C, stream);
-        if (rc) return rc;
-        rc = dbmm_l2norm_sim_ce_bwd(z, inv_norm, ebd_weight, with_old, tn, logits, labels, nullptr, temperature, 1.f, dz, B, D, C, stream);
-        if (rc) return rc;
-    }
-    if (con_loss) {
-        // the contrastive head reads the trainable branch's z against itself: Gram tiles, the reduction (which also takes the mean of
-        // the CE rows and writes the mixed loss, so the backward's spare loss-mean block is not launched), and the backward onto
-        // the CE head's dz in place.  Its workspace follows the step's; the statistics live in that workspace's spare floats.
-        void* cws = (char*)workspace + step_bytes;
-        const size_t cbytes = dbmm_supcon_workspace_bytes(B, D);
-        float* sp = dbmm_supcon_spare(cws, B);
-        rc = dbmm_supcon_fwd(z, labels, con_tau, loss_rows, con_w, con_loss, loss_mean, sp + 4 * B, sp, sp + 5 * B, B, D, cws, cbytes, stream);
-        if (rc) return rc;
-        rc = dbmm_supcon_bwd(z, labels, con_tau, sp, sp + 5 * B, con_w, dz, 1.f - con_w, dz, B, D, cws, cbytes, stream);
-        if (rc) return rc;
-    }
-    float* ps[6] = {w1, b1, gamma, beta, w2, b2};
-    const float* gs[6] = {dw1, db1, dgamma, dbeta, dw2, db2};
-    float* ms[6] = {m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2};
-    const int64_t ns[6] = {H * D, H, H, H, D * H, D};
-    if (fast) {
-        float* dh = bws + B * H;
-        const float *dw1part = nullptr, *db1part = nullptr;
-        int nsplit = 1;
-        rc = dbmm_adapter_bwd_fast(x, dz, h, mean, invstd, r, gamma, beta, w2, dw1, db1, dgamma, dbeta, dw2, db2, dh, dh + B * H, B, D,
-                                   (hipStream_t)stream, &dw1part, &db1part, &nsplit, groups || con_loss ? nullptr : loss_rows,
-                                   groups || con_loss ? nullptr : loss_mean);
-        if (rc) return rc;
-        gs[0] = dw1part; gs[1] = db1part;
-        const int nsp[6] = {nsplit, nsplit, 1, 1, 1, 1};
-        return sgd_impl(6, ps, gs, ms, ns, nsp, lr, momentum, weight_decay, first_step, stream);
-    }
-    rc = dbmm_adapter_bwd(x, dz, h, mean, invstd, r, gamma, beta, w2, dw1, db1, dgamma, dbeta, dw2, db2, B, D, H, bws,
-                          dbmm_workspace_bytes_adapter_bwd(B, D, H), stream);
+    const HeadIo io{f + L.a.z, with_old ? f + L.o.z : nullptr, tn, labels, ebd_weight, temperature, logits, loss_rows, f + L.inv_norm, f + L.dz,
+                    B, D, C, fast, stream};
+    bool spare = false;                      // the loss mean is still to be written, by the backward's spare block
+    if (gdro.groups) rc = head_gdro(io, gdro, f + L.bws, loss_mean);
+    else if (with_con) rc = head_ce_supcon(io, con, loss_mean, (char*)workspace + step_bytes, cbytes);
+    else rc = head_ce(io, loss_mean, &spare);
     if (rc) return rc;
-    return dbmm_sgd_momentum(6, ps, gs, ms, ns, lr, momentum, weight_decay, first_step, stream);
+    return bwd_sgd(x, p, m, sc, f, L, fast, spare ? loss_rows : nullptr, spare ? loss_mean : nullptr, B, D, H, stream);
+}
+
+}  // namespace
+
+extern "C" size_t dbmm_workspace_bytes_adapter_train_step(int64_t B, int64_t D, int64_t H, int with_old) {
+    return step_ws(B, D, H, with_old != 0, true).total * sizeof(float);
 }
 
 extern "C" int dbmm_adapter_train_step(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
@@ -732,9 +759,10 @@ extern "C" int dbmm_adapter_train_step(const float* x, const int64_t* labels, fl
                                        int first_step, float* logits, float* loss_rows, float* loss_mean, int64_t B,
                                        int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
                                        void* stream) {
-    return train_step_impl(x, labels, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2, o_w1, o_b1, o_gamma,
-                           o_beta, o_rmean, o_rvar, o_nbt, o_w2, o_b2, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, logits,
-                           loss_rows, loss_mean, nullptr, nullptr, 0.f, 0, 0.f, 0.f, nullptr, B, D, H, C, workspace, workspace_bytes, stream);
+    return train_step_impl(x, labels, {w1, b1, gamma, beta, rmean, rvar, (long long*)nbt, w2, b2}, {m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2},
+                           {o_w1, o_b1, o_gamma, o_beta, o_rmean, o_rvar, (long long*)o_nbt, o_w2, o_b2}, ebd_weight, tn, temperature,
+                           {lr, momentum, weight_decay, first_step}, logits, loss_rows, loss_mean, {}, {}, B, D, H, C, workspace,
+                           workspace_bytes, stream);
 }
 
 extern "C" int dbmm_adapter_train_step_gdro(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
@@ -750,9 +778,10 @@ extern "C" int dbmm_adapter_train_step_gdro(const float* x, const int64_t* label
                                             void* stream) {
     if (!groups || !q) return DBMM_E_ARG;
     if (G < 1 || G > GDRO_MAXG) return DBMM_E_SHAPE;
-    return train_step_impl(x, labels, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2, o_w1, o_b1, o_gamma,
-                           o_beta, o_rmean, o_rvar, o_nbt, o_w2, o_b2, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, logits,
-                           loss_rows, robust_loss, groups, q, eta, G, 0.f, 0.f, nullptr, B, D, H, C, workspace, workspace_bytes, stream);
+    return train_step_impl(x, labels, {w1, b1, gamma, beta, rmean, rvar, (long long*)nbt, w2, b2}, {m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2},
+                           {o_w1, o_b1, o_gamma, o_beta, o_rmean, o_rvar, (long long*)o_nbt, o_w2, o_b2}, ebd_weight, tn, temperature,
+                           {lr, momentum, weight_decay, first_step}, logits, loss_rows, robust_loss, {groups, q, eta, G}, {}, B, D, H, C, workspace,
+                           workspace_bytes, stream);
 }
 
 extern "C" int dbmm_adapter_train_step_supcon(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
@@ -767,23 +796,18 @@ extern "C" int dbmm_adapter_train_step_supcon(const float* x, const int64_t* lab
                                               int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
                                               void* stream) {
     if (!con_loss) return DBMM_E_ARG;
-    return train_step_impl(x, labels, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2, o_w1, o_b1, o_gamma,
-                           o_beta, o_rmean, o_rvar, o_nbt, o_w2, o_b2, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, logits,
-                           loss_rows, loss_mean, nullptr, nullptr, 0.f, 0, weight, tau, con_loss, B, D, H, C, workspace, workspace_bytes, stream);
+    return train_step_impl(x, labels, {w1, b1, gamma, beta, rmean, rvar, (long long*)nbt, w2, b2}, {m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2},
+                           {o_w1, o_b1, o_gamma, o_beta, o_rmean, o_rvar, (long long*)o_nbt, o_w2, o_b2}, ebd_weight, tn, temperature,
+                           {lr, momentum, weight_decay, first_step}, logits, loss_rows, loss_mean, {}, {weight, tau, con_loss}, B, D, H, C, workspace,
+                           workspace_bytes, stream);
 }
 
 // ---- one call = one step of the contrastive adapter on sampled sets (supcon_sets.hip) ----------------------------
-// workspace layout (floats): h, r [B*H]x2 | z [B*D] | mean, invstd [H]x2 | dz [B*D] | dw1 [H*D] db1 dgamma dbeta [H]x3 dw2 [D*H] db2 [D]
-// | bwd scratch | the head's workspace, B = T*S
-static size_t sets_step_floats(int64_t B, int64_t D, int64_t H) {
-    const size_t n = 2 * B * H + 2 * B * D + 2 * H + (H * D + 3 * H + D * H + D) + dbmm_workspace_bytes_adapter_bwd(B, D, H) / sizeof(float);
-    return (n + 3) / 4 * 4 + 64;
-}
-
+// workspace: the step's (no frozen adapter, no inv_norm) | the head's, B = T*S
 extern "C" size_t dbmm_workspace_bytes_adapter_train_step_sets(int64_t T, int64_t S, int64_t D, int64_t H) {
     const size_t head = dbmm_supcon_sets_workspace_bytes(T, S, D);
     if (!head || H <= 0 || (H & 3)) return 0;
-    return sets_step_floats(T * S, D, H) * sizeof(float) + head;
+    return step_ws(T * S, D, H, false, false).total * sizeof(float) + head;
 }
 
 extern "C" int dbmm_adapter_train_step_sets(const float* x, float* w1, float* b1, float* gamma, float* beta, float* rmean, float* rvar,
@@ -791,9 +815,9 @@ extern "C" int dbmm_adapter_train_step_sets(const float* x, float* w1, float* b1
                                             float* m_w2, float* m_b2, float lr, float momentum, float weight_decay, int first_step,
                                             float scale, float tau, float* loss, float* loss_sets, int64_t T, int64_t A, int64_t P,
                                             int64_t N, int64_t D, int64_t H, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !w1 || !b1 || !gamma || !beta || !rmean || !rvar || !w2 || !b2 || !m_w1 || !m_b1 || !m_gamma || !m_beta || !m_w2 || !m_b2 ||
-        !loss || !loss_sets || !workspace)
-        return DBMM_E_ARG;
+    const AdapterParams p{w1, b1, gamma, beta, rmean, rvar, (long long*)nbt, w2, b2};
+    const AdapterMomentum m{m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2};
+    if (!x || !complete(p.forward_only()) || !complete(m) || !loss || !loss_sets || !workspace) return DBMM_E_ARG;
     if (T < 1 || A < 1 || P < 1 || N < 1 || D <= 0 || H <= 0 || (D & 3) || (H & 3) || !(tau > 0.f) || T > 65535 || A > INT32_MAX ||
         P > INT32_MAX || N > INT32_MAX || T * (A + P + N) > INT32_MAX)
         return DBMM_E_SHAPE;
@@ -801,44 +825,16 @@ extern "C" int dbmm_adapter_train_step_sets(const float* x, float* w1, float* b1
     if (!dbmm_adapter_fast_shape(B, D, H) || !dbmm_opt(OPT_ADAPTER_STEP_FUSED) || !dbmm_aligned16(x)) return DBMM_E_UNSUPPORTED;
     const size_t head_bytes = dbmm_supcon_sets_workspace_bytes(T, S, D);
     if (!head_bytes) return DBMM_E_UNSUPPORTED;
-    const size_t step_bytes = sets_step_floats(B, D, H) * sizeof(float);
+    const StepWs L = step_ws(B, D, H, false, false);
+    const size_t step_bytes = L.total * sizeof(float);
     if (workspace_bytes < step_bytes + head_bytes) return DBMM_E_WORKSPACE;
     if (!dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
-    auto up4 = [](size_t n) { return (n + 3) / 4 * 4; };
     float* f = (float*)workspace;
-    float* h = f;            f += up4(B * H);
-    float* r = f;            f += up4(B * H);
-    float* z = f;            f += up4(B * D);
-    float* mean = f;         f += up4(H);
-    float* invstd = f;       f += up4(H);
-    float* dz = f;           f += up4(B * D);
-    float* dw1 = f;          f += up4(H * D);
-    float* db1 = f;          f += up4(H);
-    float* dgamma = f;       f += up4(H);
-    float* dbeta = f;        f += up4(H);
-    float* dw2 = f;          f += up4(D * H);
-    float* db2 = f;          f += up4(D);
-    float* bws = f;
-    void* hws = (char*)workspace + step_bytes;
-    int rc = dbmm_adapter_fwd(x, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, h, mean, invstd, r, z, B, D, H, 1, 1e-5f, 0.1f, stream);
+    int rc = fwd_train(x, p.forward_only(), f, L.a, B, D, H, stream);
     if (rc) return rc;
-    rc = dbmm_supcon_sets_fwd(z, scale, tau, loss, loss_sets, T, A, P, N, D, hws, head_bytes, stream);
+    rc = head_sets(f + L.a.z, f + L.dz, scale, tau, loss, loss_sets, T, A, P, N, D, (char*)workspace + step_bytes, head_bytes, stream);
     if (rc) return rc;
-    rc = dbmm_supcon_sets_bwd(z, scale, tau, dz, T, A, P, N, D, hws, head_bytes, stream);
-    if (rc) return rc;
-    float* ps[6] = {w1, b1, gamma, beta, w2, b2};
-    const float* gs[6] = {dw1, db1, dgamma, dbeta, dw2, db2};
-    float* ms[6] = {m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2};
-    const int64_t ns[6] = {H * D, H, H, H, D * H, D};
-    float* dh = bws + B * H;
-    const float *dw1part = nullptr, *db1part = nullptr;
-    int nsplit = 1;
-    rc = dbmm_adapter_bwd_fast(x, dz, h, mean, invstd, r, gamma, beta, w2, dw1, db1, dgamma, dbeta, dw2, db2, dh, dh + B * H, B, D,
-                               (hipStream_t)stream, &dw1part, &db1part, &nsplit);
-    if (rc) return rc;
-    gs[0] = dw1part; gs[1] = db1part;
-    const int nsp[6] = {nsplit, nsplit, 1, 1, 1, 1};
-    return sgd_impl(6, ps, gs, ms, ns, nsp, lr, momentum, weight_decay, first_step, stream);
+    return bwd_sgd(x, p, m, {lr, momentum, weight_decay, first_step}, f, L, true, nullptr, nullptr, B, D, H, stream);
 }
 
 extern "C" int dbmm_version(void) { return 101; }

@@ -24,7 +24,7 @@
 //
 // The kernels' bodies live in adapter_bodies.inc (device functions shared with the replica-batched kernels of adapter_sweep.hip); the
 // __global__ kernels below keep their names and grids and call them with their own blockIdx / gridDim.
-#include "common.h"
+#include "adapter_step.h"
 
 namespace {
 
@@ -82,7 +82,6 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restric
 // ---- launchers (adapter_ops.hip composes dbmm_adapter_fwd / dbmm_adapter_bwd from them) -----------------------------------
 bool dbmm_adapter_fast_shape(int64_t B, int64_t D, int64_t H) { return H == 128 && D >= 128 && (D % 128) == 0 && B >= 2 && B <= (1 << 20); }
 
-// forward: h (pre-BatchNorm), mean / invstd (train), r, z.  `z` doubles as the scratch of the K-split partial sums.
 int dbmm_adapter_fwd_fast(const float* x, const float* w1, const float* b1, const float* gamma, const float* beta, float* running_mean,
                           float* running_var, int64_t* nbt, const float* w2, const float* b2, float* h, float* mean, float* invstd, float* r,
                           float* z, int64_t B, int64_t D, int train, float eps, float momentum, hipStream_t s) {
@@ -103,32 +102,14 @@ int dbmm_adapter_fwd_fast(const float* x, const float* w1, const float* b1, cons
     return DBMM_OK;
 }
 
-// batch splits of the two weight-gradient products: at most 16, each a multiple of 32 rows
-static void bwd_split(int64_t B, int* NS, int* RB) {
-    const int nb = (int)((B + 31) / 32);
-    *NS = nb < 16 ? nb : 16;
-    *RB = ((nb + *NS - 1) / *NS) * 32;
-    *NS = (int)((B + *RB - 1) / *RB);
-}
-void dbmm_adapter_bwd_split(int64_t B, int* NS, int* RB) { bwd_split(B, NS, RB); }
-size_t dbmm_adapter_bwd_fast_floats(int64_t B, int64_t D) {
-    int NS, RB; bwd_split(B, &NS, &RB);
-    return (size_t)B * D + (size_t)NS * (2 * 128 * D + D + 128);
-}
-
-// backward: dW2, db2, dgamma, dbeta, dW1, db1; dh is left in `dh`; `scratch` = dbmm_adapter_bwd_fast_floats(B, D) floats:
-// K-split partial sums of dr [D / 128][B][128] | batch-split partial sums of dW2, db2, dW1, db1
 int dbmm_adapter_bwd_fast(const float* x, const float* dz, const float* h, const float* mean, const float* invstd, const float* r, const float* gamma,
                           const float* beta, const float* w2, float* dw1, float* db1, float* dgamma, float* dbeta, float* dw2, float* db2,
-                          float* dh, float* scratch, int64_t B, int64_t D, hipStream_t s, const float** dw1part_o, const float** db1part_o,
-                          int* nsplit_o, const float* loss_rows, float* loss_mean) {
+                          float* dh, float* scratch, int64_t B, int64_t D, hipStream_t s, bool sum_dw1, const float* loss_rows, float* loss_mean) {
     const int KS = (int)(D / 128), nb = (int)((B + TB - 1) / TB);
-    int NS, RB; bwd_split(B, &NS, &RB);
-    float* drpart = scratch;
-    float* dw2part = drpart + B * D;
-    float* db2part = dw2part + (size_t)NS * D * 128;
-    float* dw1part = db2part + (size_t)NS * D;
-    float* db1part = dw1part + (size_t)NS * 128 * D;
+    const BwdScratch L = dbmm_adapter_bwd_scratch(B, D);
+    const int NS = L.NS, RB = L.RB;
+    float *drpart = scratch + L.drpart, *dw2part = scratch + L.dw2part, *db2part = scratch + L.db2part, *dw1part = scratch + L.dw1part,
+          *db1part = scratch + L.db1part;
     hipLaunchKernelGGL(bwd2_kernel, dim3((unsigned)(D / 32 * NS + nb * KS + (loss_mean ? 1 : 0))), dim3(256), 0, s, dz, r, w2, dw2part, db2part, drpart,
                        (int)B, (int)D, NS, RB, loss_rows, loss_mean);
     DBMM_CHECK_LAUNCH();
@@ -138,10 +119,7 @@ int dbmm_adapter_bwd_fast(const float* x, const float* dz, const float* h, const
     DBMM_CHECK_LAUNCH();
     hipLaunchKernelGGL(bwd1_kernel, dim3((unsigned)(D / 32), NS), dim3(256), 0, s, (const float*)dh, x, dw1part, db1part, (int)B, (int)D, RB);
     DBMM_CHECK_LAUNCH();
-    if (dw1part_o) {       // the caller (the one-call step) sums the batch splits of dW1 / db1 inside its SGD launch, in the same order
-        *dw1part_o = dw1part; *db1part_o = db1part; *nsplit_o = NS;
-        return DBMM_OK;
-    }
+    if (!sum_dw1) return DBMM_OK;
     hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((nw4 + 32 + 255) / 256)), dim3(256), 0, s, (const float*)dw1part, dw1, nw4,
                        (const float*)db1part, db1, 32LL, NS);
     DBMM_CHECK_LAUNCH();

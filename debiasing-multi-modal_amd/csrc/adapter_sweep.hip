@@ -14,24 +14,13 @@
 // BN backward, bwd1, SGD = 8 (11), whatever R is; the group-DRO step (dbmm_adapter_sweep_step_gdro) has CE forward, group weights +
 // q update, weighted CE backward in place of the one CE launch = 10 (13).  Evaluation: fc1 partials, reduce, fc2 [x 2], CE forward, loss sum = 5 (8).
 // No float atomics, no order that depends on timing.
-#include "common.h"
-
-bool dbmm_adapter_fast_shape(int64_t B, int64_t D, int64_t H);
-size_t dbmm_adapter_bwd_fast_floats(int64_t B, int64_t D);
-void dbmm_adapter_bwd_split(int64_t B, int* NS, int* RB);
+#include "adapter_step.h"
 
 namespace {
 
 #include "adapter_bodies.inc"
 
 constexpr int MAXR = 16;
-
-// the nine stacked tensors of R adapters ([R, ...] contiguous each; H = 128)
-struct StackAd {
-    float *w1, *b1, *gamma, *beta, *rmean, *rvar;
-    long long* nbt;
-    float *w2, *b2;
-};
 
 template <bool GATHER>
 __global__ __launch_bounds__(256) void sweep_fc1_kernel(const float* __restrict__ x, const long long* __restrict__ idx, long long idx_stride,
@@ -287,7 +276,7 @@ StepLayout step_layout(int64_t B, int64_t D, int with_old) {
     L.oh = L.orr = L.oz = L.omean = L.oinv = -1;
     if (with_old) { L.oh = take(B * 128); L.orr = take(B * 128); L.oz = take(B * D); L.omean = take(128); L.oinv = take(128); }
     L.dz = take(B * D); L.dgamma = take(128); L.dbeta = take(128); L.dw2 = take(D * 128); L.db2 = take(D); L.dh = take(B * 128);
-    L.scratch = take(dbmm_adapter_bwd_fast_floats(B, D));
+    L.scratch = take(dbmm_adapter_bwd_scratch(B, D).total);
     L.total = f;
     return L;
 }
@@ -316,8 +305,8 @@ bool stack_aligned(void* const* p) {
         if (i != 6 && !dbmm_aligned16(p[i])) return false;
     return true;
 }
-StackAd stack_of(void* const* p) {
-    return StackAd{(float*)p[0], (float*)p[1], (float*)p[2], (float*)p[3], (float*)p[4], (float*)p[5], (long long*)p[6], (float*)p[7], (float*)p[8]};
+AdapterParams stack_of(void* const* p) {                 // the nine stacked tensors of R adapters
+    return AdapterParams{(float*)p[0], (float*)p[1], (float*)p[2], (float*)p[3], (float*)p[4], (float*)p[5], (long long*)p[6], (float*)p[7], (float*)p[8]};
 }
 
 // shapes the replica-batched kernels serve: the fast shape of the single step, R replicas on the grid
@@ -366,13 +355,13 @@ static int sweep_step_impl(const float* table, int64_t n_rows, const int64_t* id
     const StepLayout L = step_layout(B, D, with_old);
     float* ws = (float*)workspace;
     const long long wst = L.total;
-    const StackAd P = stack_of(params);
+    const AdapterParams P = stack_of(params);
     const int KS = (int)(D / 128), nb = (int)((B + 31) / 32), iR = (int)R, iB = (int)B, iD = (int)D;
     const float eps = 1e-5f, bn_momentum = 0.1f;
     const long long* idxl = (const long long*)idx;
 
     for (int pass = 0; pass < 1 + with_old; ++pass) {                 // the trainable adapter, then the frozen one (train-mode BatchNorm too)
-        const StackAd A = pass ? stack_of(old) : P;
+        const AdapterParams A = pass ? stack_of(old) : P;
         const long long zo = pass ? L.oz : L.z, ho = pass ? L.oh : L.h, mo = pass ? L.omean : L.mean, io = pass ? L.oinv : L.invstd,
                         ro = pass ? L.orr : L.r;
         hipLaunchKernelGGL(sweep_fc1_kernel<true>, dim3(nb, 2, KS * iR), dim3(256), 0, s, table, idxl, (long long)B, (long long)n_rows,
@@ -386,51 +375,40 @@ static int sweep_step_impl(const float* table, int64_t n_rows, const int64_t* id
                            iB, iD);
         DBMM_CHECK_LAUNCH();
     }
+    const float w_new = with_old ? (1.f - ebd_weight) : 1.f, invT = 1.f / temperature;
+    unsigned long long* cnt = counted ? (unsigned long long*)counts : nullptr;
+    const dim3 grid((unsigned)((B + 3) / 4), iR);
+    const long long* lab = (const long long*)labels;
+    const long long* grp = (const long long*)groups;
     if (q) {
         // group DRO: forward rows, group reduction + q update (one workgroup per replica), weighted backward rows.  1 / ||z|| and the
         // [3][G] statistics live in the dh region, which nothing uses before the BatchNorm backward
-        const float w_new = with_old ? (1.f - ebd_weight) : 1.f, invT = 1.f / temperature;
-        unsigned long long* cnt = counted ? (unsigned long long*)counts : nullptr;
-        const dim3 grid((unsigned)((B + 3) / 4), iR);
         const long long invoff = L.dh, gwoff = L.dh + (long long)up4(B);
-        const long long* lab = (const long long*)labels;
-        const long long* grp = (const long long*)groups;
-        if (C <= 4)
-            hipLaunchKernelGGL(sweep_ce_fwd_train_kernel<4>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, invoff, ebd_weight, tn, lab, grp, idxl,
-                               (long long)n_rows, invT, logits, loss_rows, cnt, (int)G, iB, (int)(D / 4), (int)C);
-        else
-            hipLaunchKernelGGL(sweep_ce_fwd_train_kernel<8>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, invoff, ebd_weight, tn, lab, grp, idxl,
-                               (long long)n_rows, invT, logits, loss_rows, cnt, (int)G, iB, (int)(D / 4), (int)C);
+        dbmm_with_cmax(C, [&](auto cm) {
+            hipLaunchKernelGGL(sweep_ce_fwd_train_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, invoff, ebd_weight, tn, lab,
+                               grp, idxl, (long long)n_rows, invT, logits, loss_rows, cnt, (int)G, iB, (int)(D / 4), (int)C);
+        });
         DBMM_CHECK_LAUNCH();
         hipLaunchKernelGGL(sweep_gdro_weights_kernel, dim3(iR), dim3(256), 0, s, ws, wst, gwoff, (const float*)loss_rows, grp, idxl, (long long)n_rows, q,
                            loss_mean, counted ? loss_sum : nullptr, iB, (int)G, eta);
         DBMM_CHECK_LAUNCH();
-        if (C <= 4)
-            hipLaunchKernelGGL(sweep_ce_bwd_w_kernel<4>, grid, dim3(256), 0, s, ws, wst, L.z, invoff, gwoff, L.dz, w_new, tn, (const float*)logits, lab, grp,
-                               idxl, (long long)n_rows, (int)G, invT, iB, (int)(D / 4), (int)C);
-        else
-            hipLaunchKernelGGL(sweep_ce_bwd_w_kernel<8>, grid, dim3(256), 0, s, ws, wst, L.z, invoff, gwoff, L.dz, w_new, tn, (const float*)logits, lab, grp,
-                               idxl, (long long)n_rows, (int)G, invT, iB, (int)(D / 4), (int)C);
+        dbmm_with_cmax(C, [&](auto cm) {
+            hipLaunchKernelGGL(sweep_ce_bwd_w_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, ws, wst, L.z, invoff, gwoff, L.dz, w_new, tn,
+                               (const float*)logits, lab, grp, idxl, (long long)n_rows, (int)G, invT, iB, (int)(D / 4), (int)C);
+        });
         DBMM_CHECK_LAUNCH();
     } else {
-        const float w_new = with_old ? (1.f - ebd_weight) : 1.f, gs = 1.f / (float)B;
-        unsigned long long* cnt = counted ? (unsigned long long*)counts : nullptr;
-        const dim3 grid((unsigned)((B + 3) / 4), iR);
-        if (C <= 4)
-            hipLaunchKernelGGL(sweep_ce_fwdbwd_kernel<4>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, L.dz, ebd_weight, w_new, tn, (const long long*)labels,
-                               (const long long*)groups, idxl, (long long)n_rows, 1.f / temperature, gs, logits, loss_rows, cnt, (int)G, iB, (int)(D / 4),
-                               (int)C);
-        else
-            hipLaunchKernelGGL(sweep_ce_fwdbwd_kernel<8>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, L.dz, ebd_weight, w_new, tn, (const long long*)labels,
-                               (const long long*)groups, idxl, (long long)n_rows, 1.f / temperature, gs, logits, loss_rows, cnt, (int)G, iB, (int)(D / 4),
-                               (int)C);
+        dbmm_with_cmax(C, [&](auto cm) {
+            hipLaunchKernelGGL(sweep_ce_fwdbwd_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, L.dz, ebd_weight, w_new, tn, lab,
+                               grp, idxl, (long long)n_rows, invT, 1.f / (float)B, logits, loss_rows, cnt, (int)G, iB, (int)(D / 4), (int)C);
+        });
         DBMM_CHECK_LAUNCH();
     }
     // the single step's backward (dbmm_adapter_bwd_fast) with its scratch at L.scratch: dr partials | dW2, db2, dW1, db1 partials
-    int NS, RB;
-    dbmm_adapter_bwd_split(B, &NS, &RB);
-    const long long drp = L.scratch, dw2p = drp + B * D, db2p = dw2p + (long long)NS * D * 128, dw1p = db2p + (long long)NS * D,
-                    db1p = dw1p + (long long)NS * 128 * D;
+    const BwdScratch S = dbmm_adapter_bwd_scratch(B, D);
+    const int NS = S.NS, RB = S.RB;
+    const long long drp = L.scratch + S.drpart, dw2p = L.scratch + S.dw2part, db2p = L.scratch + S.db2part, dw1p = L.scratch + S.dw1part,
+                    db1p = L.scratch + S.db1part;
     const int nbT = (int)((B + TB - 1) / TB);
     // (group DRO: the robust loss is already written and counted, so the spare loss-mean block is not launched)
     hipLaunchKernelGGL(sweep_bwd2_kernel, dim3((unsigned)(D / 32 * NS + nbT * KS + (q ? 0 : 1)), iR), dim3(256), 0, s, ws, wst, L.dz, L.r, (const float*)P.w2,
@@ -507,14 +485,10 @@ extern "C" int dbmm_adapter_sweep_eval(const float* table, int64_t n_rows, const
     const long long* lab = (const long long*)(idx ? labels : labels + row0);
     const long long* grp = (const long long*)(idx ? groups : groups + row0);
     for (int pass = 0; pass < 1 + with_old; ++pass) {
-        const StackAd A = stack_of(pass ? old : params);
+        const AdapterParams A = stack_of(pass ? old : params);
         const long long zo = pass ? L.oz : L.z, ho = pass ? L.oh : L.h, ro = pass ? L.orr : L.r;
-        if (idx)
-            hipLaunchKernelGGL(sweep_fc1_kernel<true>, dim3(nb, 2, KS * iR), dim3(256), 0, s, x, idxl, 0LL, (long long)n_rows, (const float*)A.w1, ws, wst, zo,
-                               iB, iD, KS);
-        else
-            hipLaunchKernelGGL(sweep_fc1_kernel<false>, dim3(nb, 2, KS * iR), dim3(256), 0, s, x, idxl, 0LL, (long long)n_rows, (const float*)A.w1, ws, wst,
-                               zo, iB, iD, KS);
+        const auto fc1 = idx ? sweep_fc1_kernel<true> : sweep_fc1_kernel<false>;       // rows idx[b] of the table, or rows in place
+        hipLaunchKernelGGL(fc1, dim3(nb, 2, KS * iR), dim3(256), 0, s, x, idxl, 0LL, (long long)n_rows, (const float*)A.w1, ws, wst, zo, iB, iD, KS);
         DBMM_CHECK_LAUNCH();
         const long long total = B * 128;
         hipLaunchKernelGGL(sweep_fc1_reduce_kernel, dim3((unsigned)((total + 255) / 256), iR), dim3(256), 0, s, ws, wst, zo, ho, KS, (const float*)A.b1,
@@ -525,12 +499,10 @@ extern "C" int dbmm_adapter_sweep_eval(const float* table, int64_t n_rows, const
         DBMM_CHECK_LAUNCH();
     }
     const dim3 grid((unsigned)((B + 3) / 4), iR);
-    if (C <= 4)
-        hipLaunchKernelGGL(sweep_ce_fwd_kernel<4>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, ebd_weight, tn, lab, grp, idxl, (long long)n_rows,
-                           1.f / temperature, logits, loss_rows, (unsigned long long*)counts, (int)G, iB, (int)(D / 4), (int)C);
-    else
-        hipLaunchKernelGGL(sweep_ce_fwd_kernel<8>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, ebd_weight, tn, lab, grp, idxl, (long long)n_rows,
-                           1.f / temperature, logits, loss_rows, (unsigned long long*)counts, (int)G, iB, (int)(D / 4), (int)C);
+    dbmm_with_cmax(C, [&](auto cm) {
+        hipLaunchKernelGGL(sweep_ce_fwd_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, ebd_weight, tn, lab, grp, idxl,
+                           (long long)n_rows, 1.f / temperature, logits, loss_rows, (unsigned long long*)counts, (int)G, iB, (int)(D / 4), (int)C);
+    });
     DBMM_CHECK_LAUNCH();
     hipLaunchKernelGGL(sweep_loss_sum_kernel, dim3(iR), dim3(256), 0, s, (const float*)loss_rows, loss_sum, iB);
     DBMM_CHECK_LAUNCH();

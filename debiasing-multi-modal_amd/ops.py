@@ -837,7 +837,24 @@ def gather_sets(table, idx):
     return gather_rows(table, idx.reshape(-1))
 
 
-_sets_ws = {}
+_step_ws, _sets_ws = {}, {}
+
+
+def _cached_ws(cache, limit, key, dev, nbytes):
+    """the workspace of the one-call steps of shape `key`: from `cache`, or allocated with nbytes(*key[1:]) bytes and kept there; a
+    cache that already holds more than `limit` workspaces is emptied first"""
+    ws = cache.get(key)
+    if ws is None:
+        ws = _empty(max(nbytes(*key[1:]) // 4, 4), device=dev, dtype=torch.float32)      # 0 bytes: a shape the library refuses by name
+        if len(cache) > limit:
+            cache.clear()
+        cache[key] = ws
+    return ws
+
+
+def _step_ws_bytes(B, D, H, with_old, contrastive):
+    L = _lib.lib()
+    return L.dbmm_workspace_bytes_adapter_train_step(B, D, H, int(with_old)) + (L.dbmm_supcon_workspace_bytes(B, D) if contrastive else 0)
 
 
 def adapter_train_step_sets(x, args, H, sets, scale, tau, lr, momentum, weight_decay, first_step):
@@ -847,14 +864,7 @@ def adapter_train_step_sets(x, args, H, sets, scale, tau, lr, momentum, weight_d
     T, A, P, N, D = _sets_operands(x, sets, "adapter_train_step_sets")
     S = A + P + N
     dev = x.device
-    key = (dev.index, T, S, D, H)
-    ws = _sets_ws.get(key)
-    if ws is None:
-        nbytes = _lib.lib().dbmm_workspace_bytes_adapter_train_step_sets(T, S, D, H)
-        ws = _empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
-        if len(_sets_ws) > 4:
-            _sets_ws.clear()
-        _sets_ws[key] = ws
+    ws = _cached_ws(_sets_ws, 4, (dev.index, T, S, D, H), dev, _lib.lib().dbmm_workspace_bytes_adapter_train_step_sets)
     out = _empty((T + 1,), device=dev, dtype=torch.float32)
     rc = _lib.lib().dbmm_adapter_train_step_sets(x.data_ptr(), *args[:15], float(lr), float(momentum), float(weight_decay), int(first_step),
                                                  float(scale), float(tau), out.data_ptr() + 4 * T, out.data_ptr(), T, A, P, N, D, H,
@@ -928,9 +938,6 @@ def group_loss_sum(loss_rows, g, sums):
     return sums
 
 
-_step_ws = {}
-
-
 def adapter_step_launches(B, D, H, with_old=False, robust=False, contrastive=False):
     """kernel launches of one dbmm_adapter_train_step call on the purpose-built kernels (csrc/adapter_step.hip): forward 3
     (K-split fc1, BatchNorm statistics, BatchNorm + ReLU + fc2; 3 more for a frozen old adapter), cosine logits + CE forward
@@ -968,45 +975,28 @@ def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature
             raise DbmmUnsupported("adapter_train_step: the contrastive head and group DRO do not combine")
         if B > SUPCON_MAX_B:
             raise DbmmUnsupported(f"adapter_train_step: B = {B}; the contrastive head serves 2 <= B <= {SUPCON_MAX_B}")
-    key = (dev.index, B, D, H, with_old, contrastive is not None)
-    ws = _step_ws.get(key)
-    if ws is None:
-        nbytes = _lib.lib().dbmm_workspace_bytes_adapter_train_step(B, D, H, int(with_old))
-        if contrastive is not None:
-            nbytes += _lib.lib().dbmm_supcon_workspace_bytes(B, D)
-        ws = _empty(nbytes // 4, device=dev, dtype=torch.float32)
-        if len(_step_ws) > 8:
-            _step_ws.clear()
-        _step_ws[key] = ws
+    L = _lib.lib()
+    ws = _cached_ws(_step_ws, 8, (dev.index, B, D, H, with_old, contrastive is not None), dev, _step_ws_bytes)
     logits = _empty((B, C), device=dev, dtype=torch.float32)
+    # per-row losses, then their mean (the robust / the mixed loss), then L_con of the contrastive head: one allocation
+    loss = _empty((B + (1 if contrastive is None else 2),), device=dev, dtype=torch.float32)
     if contrastive is not None:
         weight, tau = contrastive
-        loss = _empty((B + 2,), device=dev, dtype=torch.float32)    # per-row CE, the mixed loss, L_con
-        rc = _lib.lib().dbmm_adapter_train_step_supcon(
-            x.data_ptr(), labels.data_ptr(), *args, float(ebd_weight), tn.data_ptr(), float(temperature), float(lr), float(momentum),
-            float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * B, float(weight), float(tau),
-            loss.data_ptr() + 4 * B + 4, B, D, H, C, ws.data_ptr(), ws.numel() * 4, stream())
-        if rc:
-            check(rc, "adapter_train_step_supcon")
-        return loss[B], logits, loss[:B], loss[B + 1]
-    loss = _empty((B + 1,), device=dev, dtype=torch.float32)        # per-row losses, then their mean: one allocation
-    if robust is not None:
+        step, name = L.dbmm_adapter_train_step_supcon, "adapter_train_step_supcon"
+        head = (float(weight), float(tau), loss.data_ptr() + 4 * B + 4)
+    elif robust is not None:
         groups, q, eta = robust
-        G = _gdro_operands(groups, q, B)
-        rc = _lib.lib().dbmm_adapter_train_step_gdro(
-            x.data_ptr(), labels.data_ptr(), *args, float(ebd_weight), tn.data_ptr(), float(temperature), float(lr), float(momentum),
-            float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * B, groups.data_ptr(), q.data_ptr(),
-            float(eta), G, B, D, H, C, ws.data_ptr(), ws.numel() * 4, stream())
-        if rc:
-            check(rc, "adapter_train_step_gdro")
-        return loss[B], logits, loss[:B]
-    rc = _lib.lib().dbmm_adapter_train_step(
-        x.data_ptr(), labels.data_ptr(), *args, float(ebd_weight), tn.data_ptr(), float(temperature), float(lr), float(momentum),
-        float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * B, B, D, H, C, ws.data_ptr(),
-        ws.numel() * 4, stream())
+        step, name = L.dbmm_adapter_train_step_gdro, "adapter_train_step_gdro"
+        head = (groups.data_ptr(), q.data_ptr(), float(eta), _gdro_operands(groups, q, B))
+    else:
+        step, name, head = L.dbmm_adapter_train_step, "adapter_train_step", ()
+    # the 36 arguments every head shares, the head's own, the shape and the workspace
+    rc = step(x.data_ptr(), labels.data_ptr(), *args, float(ebd_weight), tn.data_ptr(), float(temperature), float(lr), float(momentum),
+              float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * B, *head, B, D, H, C, ws.data_ptr(),
+              ws.numel() * 4, stream())
     if rc:
-        check(rc, "adapter_train_step")
-    return loss[B], logits, loss[:B]
+        check(rc, name)
+    return (loss[B], logits, loss[:B]) if contrastive is None else (loss[B], logits, loss[:B], loss[B + 1])
 
 
 _sweep_ws = {}
@@ -1108,24 +1098,18 @@ def adapter_sweep_step(table, idx, labels, groups, args, ebd_weight, tn, tempera
     loss = _empty((R, B + 1), device=dev, dtype=torch.float32)          # [:, :B] would not be contiguous: rows first, then the R means
     loss = loss.view(-1)
     LR = (ctypes.c_float * R)(*[float(v) for v in lrs])
+    step, name, head = L.dbmm_adapter_sweep_step, "adapter_sweep_step", ()
     if robust is not None:
         q, eta = robust
         if _gdro_operands(groups, q, None, R) != G:
             raise _lib.DbmmError(f"adapter sweep step: q {tuple(q.shape)} for counters of {G} groups")
-        rc = L.dbmm_adapter_sweep_step_gdro(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(),
-                                            args["P"], args["Bf"], args["O"], float(ebd_weight), tn.data_ptr(), float(temperature), LR,
-                                            float(momentum), float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(),
-                                            loss.data_ptr() + 4 * R * B, counts.data_ptr(), loss_sum.data_ptr(), G, int(counted), q.data_ptr(),
-                                            float(eta), R, B, D, H, C, ws.data_ptr(), ws.numel() * 4, stream())
-        if rc:
-            check(rc, "adapter_sweep_step_gdro")
-        return loss[R * B:], logits, loss[:R * B].view(R, B)
-    rc = L.dbmm_adapter_sweep_step(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(),
-                                   args["P"], args["Bf"], args["O"], float(ebd_weight), tn.data_ptr(), float(temperature), LR, float(momentum),
-                                   float(weight_decay), int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * R * B,
-                                   counts.data_ptr(), loss_sum.data_ptr(), G, int(counted), R, B, D, H, C, ws.data_ptr(), ws.numel() * 4, stream())
+        step, name, head = L.dbmm_adapter_sweep_step_gdro, "adapter_sweep_step_gdro", (q.data_ptr(), float(eta))
+    rc = step(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(), args["P"], args["Bf"], args["O"],
+              float(ebd_weight), tn.data_ptr(), float(temperature), LR, float(momentum), float(weight_decay), int(first_step), logits.data_ptr(),
+              loss.data_ptr(), loss.data_ptr() + 4 * R * B, counts.data_ptr(), loss_sum.data_ptr(), G, int(counted), *head, R, B, D, H, C,
+              ws.data_ptr(), ws.numel() * 4, stream())
     if rc:
-        check(rc, "adapter_sweep_step")
+        check(rc, name)
     return loss[R * B:], logits, loss[:R * B].view(R, B)
 
 
