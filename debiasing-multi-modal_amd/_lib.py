@@ -29,21 +29,21 @@ KERNEL_SOURCES = (
     ("bottleneck_chain_kernel", ("bottleneck_chain.hip", "common.h")),
     ("bottleneck_chain8_kernel", ("bottleneck_chain8.hip", "common.h")),
     ("conv3x3_c32_kernel", ("conv_patch.hip", "common.h")),
-    ("gemm_pair_8ph_kernel", ("gemm_pair_8ph.hip", "common.h")),
-    ("conv3x3_halo8", ("conv3x3_halo8.hip", "conv3x3_halo8_epilogue.inc", "common.h")),
+    ("gemm_pair_8ph_kernel", ("gemm_pair_8ph.hip", "gemm_pair_8ph_epilogue.inc", "persistent_tiles.h", "common.h")),
+    ("conv3x3_halo8", ("conv3x3_halo8.hip", "conv3x3_halo8_epilogue.inc", "persistent_tiles.h", "common.h")),
     ("mha_pair_kernel", ("mha_pair.hip", "common.h")),
-    ("gemm_f16", ("f16_ops.hip", "common.h")), ("mha_f16", ("f16_ops.hip", "common.h")), ("layernorm_f16", ("f16_ops.hip", "common.h")),
+    ("gemm_f16", ("f16_ops.hip", "fp16_ring.inc", "gemm_f16_8ph_epilogue.inc", "persistent_tiles.h", "common.h")), ("mha_f16", ("f16_ops.hip", "common.h")), ("layernorm_f16", ("f16_ops.hip", "common.h")),
     ("chain_f16", ("chain_f16.hip", "common.h")),
     ("conv1x1_res_stream", ("conv1x1_res_stream.hip", "common.h")),
     ("conv1x1_res_stream_f16", ("conv1x1_res_stream_f16.hip", "common.h")),
-    ("conv3x3_f16", ("conv_f16.hip", "common.h")), ("conv1x1_f16", ("conv_f16.hip", "common.h")), ("stem_s2_f16", ("conv_f16.hip", "common.h")),
+    ("conv3x3_f16", ("conv_f16.hip", "persistent_tiles.h", "common.h")), ("conv1x1_f16", ("conv_f16.hip", "common.h")), ("stem_s2_f16", ("conv_f16.hip", "common.h")),
     ("avgpool2_f16", ("conv_f16.hip", "common.h")),
     ("stem_s2", ("resnet_ops.hip", "common.h")), ("attnpool", ("resnet_ops.hip", "common.h")),
     ("adapter_step", ("adapter_step.hip", "adapter_bodies.inc", "common.h")),
     ("sweep_", ("adapter_sweep.hip", "adapter_bodies.inc", "common.h")),
     ("linear_sweep_", ("linear_sweep.hip", "linear_bodies.inc", "common.h")),
     ("linear_", ("linear_step.hip", "linear_bodies.inc", "common.h")),
-    ("pairdist_", ("pairdist.hip", "common.h")),
+    ("pairdist_", ("pairdist.hip", "fp16_ring.inc", "persistent_tiles.h", "common.h")),
     ("covariance_", ("covariance.hip", "common.h")),
     ("project_rows_", ("covariance.hip", "common.h")),
     ("supcon_", ("supcon.hip", "common.h")),

@@ -1,11 +1,14 @@
 // Shared helpers for the gfx950 kernels of libdbmm_hip.so, each defined ONCE here:
 //   - the vector typedefs of the MFMA fragments and 8 / 16-byte accesses (f16x8, u32x4, ...);
 //   - DBMM_N_CU and dbmm_cut_slices: persistent-grid sizing;
-//   - wave_sum / wave_max, xcd_remap: wave reductions and the tile -> workgroup map;
+//   - wave_sum / wave_max, xcd_first / xcd_remap: wave reductions, the split of tile ids over the XCDs and the tile -> workgroup map;
 //   - desc / glds16 with OOR and EXT_LIM: rebased buffer descriptors and LDS-DMA loads;
 //   - scale_exp / pow2f / split2h_pair / frag / pack2: the fp16 (hi, lo) split under an exact power-of-two scale, the
 //     library's precision contract.  Every parity kernel splits with THESE functions.
 // plus the internal C entries that one kernel file calls in another.
+// What only the persistent 256-tile kernels share is defined once in persistent_tiles.h (tile_walk, work_item, slice_store / slice_sum,
+// absmax_fold, ring_rows, plan_tiles), the fp16 ring of two of them in fp16_ring.inc, and the epilogues that a main kernel and its fixup
+// kernel both run in gemm_f16_8ph_epilogue.inc, gemm_pair_8ph_epilogue.inc and conv3x3_halo8_epilogue.inc.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -92,14 +95,15 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// Bijective XCD-aware remap of a linear workgroup id: blocks are dealt round-robin over the
-// 8 XCDs, so give each XCD a contiguous range of tile ids (neighbouring tiles share operand
-// panels in that XCD's L2).  Speed only, never correctness.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
+// The split of n tile ids over the 8 XCDs: XCD x owns the contiguous range [xcd_first(x, n), xcd_first(x + 1, n)), the first
+// n % 8 ranges one longer (neighbouring tiles share operand panels in that XCD's L2).  Speed only, never correctness.
+__device__ __forceinline__ int xcd_first(int xcd, int n) {
+    const int tq = n >> 3, trm = n & 7;
+    return xcd < trm ? xcd * (tq + 1) : trm * (tq + 1) + (xcd - trm) * tq;
 }
+// Bijective XCD-aware remap of a linear workgroup id: blocks are dealt round-robin over the 8 XCDs, block bid is the (bid >> 3)-th
+// of XCD bid & 7 and takes that tile of the XCD's range.  (The persistent kernels walk the same ranges: tile_walk, persistent_tiles.h.)
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) { return xcd_first(bid & 7, nwg) + (bid >> 3); }
 
 // Buffer addressing.  OOR: a voffset that is out of range for every descriptor (>= any accepted extent, and OOR + (K offset)
 // cannot wrap): the hardware drops the store / returns 0 for the load, so ragged edges need no branch.

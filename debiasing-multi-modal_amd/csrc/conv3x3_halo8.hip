@@ -1,6 +1,6 @@
 // Parity-mode 3x3 / stride 1 / pad 1 conv (+ folded BatchNorm scale / bias, ReLU, optional fused 2x2 average pool) on the
 // deep-pipelined 256 x 256 structure of gemm_pair_8ph_kernel -- the conv2 of the layer-3 / layer-4 bottlenecks
-// (/root/reference/clip/model.py:24-26, 44-45: conv2 -> bn2 -> relu -> avgpool(stride)), Cout % 256 == 0.
+// (clip/model.py:24-26, 44-45: conv2 -> bn2 -> relu -> avgpool(stride)), Cout % 256 == 0.
 //
 //   y[pixel][n] = act(scale[n] * sum_{kh,kw,c} x[pixel + (kh-1) W + (kw-1)][c] * w[n][(c/32, kh, kw, c%32)] + bias[n])
 //
@@ -25,7 +25,7 @@
 // four LDS fragment reads per phase are spread evenly (B0 | B1 | A1 | next tap's A0) instead of 8 | 4 | 4 | 0.
 // LDS: 2 A buffers x 2 planes x 272 rows x 64 B + 2 W buffers x 16 KB = 100 KB.  Needs Cin % 64 == 0, Cout % 256 == 0.
 #include <stdlib.h>
-#include "common.h"
+#include "persistent_tiles.h"
 
 namespace {
 
@@ -55,21 +55,6 @@ __device__ __forceinline__ int pool_base_pixel(const Halo8P& p, int mp) {
     return (n * p.H + 2 * hp) * p.W + 2 * (rem - hp * wp2);
 }
 
-// one (filtered) atomic per workgroup: all launches of a layer hit ONE address
-__device__ __forceinline__ void halo8_amax(const Halo8P& p, float out_amax, float* red, int tid) {
-    if (!p.c_absmax) return;
-    out_amax = wave_max(out_amax);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = out_amax;
-    __syncthreads();
-    if (tid == 0) {
-        float m = red[0];
-#pragma unroll
-        for (int i = 1; i < 8; ++i) m = fmaxf(m, red[i]);
-        if (m > *(volatile const float*)p.c_absmax) atomicMax((unsigned*)p.c_absmax, __float_as_uint(m));
-    }
-}
-
 template <int POOL, int ACT>
 __global__ __launch_bounds__(512, 1) void conv3x3_halo8_kernel(const Halo8P p) {
     __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES];
@@ -77,11 +62,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo8_kernel(const Halo8P p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 1, wc = wid & 1, grp = wid >> 2;   // 4 x 2 waves, two groups of four
     const int fr = lane & 31, fh = lane >> 5;
-    // this workgroup's tiles: its XCD's contiguous range, walked with the stride of the XCD's workgroups (tiles that share
-    // an activation strip -- the N tiles of one row block -- are neighbours in that range)
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot_in_xcd = blockIdx.x >> 3, wg_per_xcd = (nwg - xcd + 7) >> 3;
-    const int tq = p.n_full >> 3, trm = p.n_full & 7;
-    const int t_lo = xcd < trm ? xcd * (tq + 1) : trm * (tq + 1) + (xcd - trm) * tq, t_hi = t_lo + tq + (xcd < trm ? 1 : 0);
+    // this workgroup's tiles (tiles that share an activation strip -- the N tiles of one row block -- are neighbours in its XCD's range)
+    const int nwg = gridDim.x;
+    const TileWalk walk = tile_walk(blockIdx.x, nwg, p.n_full);
     const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, 0, 0x00020000);   // zero extent: loads return 0
     __amdgpu_buffer_rsrc_t rsA = rs0, rsW = rs0;
     int m0 = 0, n0 = 0;
@@ -299,21 +282,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo8_kernel(const Halo8P p) {
     // the zero line of both planes of both A buffers (never written by the loader)
     if (tid < 64) *(u32x4*)(lds + OFF_A + (tid >> 5) * A_BUF + ((tid >> 4) & 1) * A_PLANE + ZROW * 64 + (tid & 15) * 16) = (u32x4){0u, 0u, 0u, 0u};
 
-    // Work items of this workgroup: its whole tiles (all groups), then its share of the n_cut * n_slices slices (slice i = cut tile i / S,
-    // loop trips [s T / S, (s + 1) T / S) with s = i % S), dealt round-robin over the workgroups.
-    const int n_whole = t_lo + slot_in_xcd < t_hi ? (t_hi - t_lo - slot_in_xcd + wg_per_xcd - 1) / wg_per_xcd : 0;
-    const int n_sl_all = p.n_cut * p.n_slices;                        // slices: number blockIdx.x + j * gridDim.x goes to this workgroup
-    const int n_sl = (int)blockIdx.x < n_sl_all ? (n_sl_all - 1 - (int)blockIdx.x) / nwg + 1 : 0;
-    const int n_items = n_whole + n_sl;
+    // Work items of this workgroup (work_item, persistent_tiles.h): its whole tiles, then its slices of the cut tiles; a loop trip is two groups
+    const int n_items = walk.n_whole + work_slices(blockIdx.x, nwg, p.n_cut * p.n_slices);
     int gb = 0, ge = G, slice_id = 0;                                 // the current item's groups [gb, ge), both even; its slice number
     auto set_item = [&](int k) {
-        if (k < n_whole) { gb = 0; ge = G; set_tile(t_lo + slot_in_xcd + k * wg_per_xcd); }
-        else {
-            slice_id = blockIdx.x + (k - n_whole) * nwg;
-            const int l = slice_id / p.n_slices, sl = slice_id - l * p.n_slices, T = G >> 1;
-            gb = 2 * (sl * T / p.n_slices); ge = 2 * ((sl + 1) * T / p.n_slices);
-            set_tile(p.n_full + l);
-        }
+        const WorkItem it = work_item(walk, k, blockIdx.x, nwg, p.n_full, p.n_slices, G >> 1);
+        gb = 2 * it.trip_lo; ge = 2 * it.trip_hi; slice_id = it.slice;
+        set_tile(it.tile);
     };
     // what an item needs before its first phases: Bh0, Bh1 of its first tap into W buffer 0, Bh0 of the second into buffer 1, its first
     // group's strip in registers
@@ -346,28 +321,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo8_kernel(const Halo8P p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the look-ahead loads / DMA past this item's last tap
         __builtin_amdgcn_s_barrier();                                 // every wave is done with the LDS
         const int em0 = m0, en0 = n0, e_slice = slice_id;
-        const bool whole = k < n_whole;
+        const bool whole = k < walk.n_whole;
         if (k + 1 < n_items) { set_item(k + 1); prologue(); }         // in flight during the epilogue below
         if (whole) {
-            constexpr int EP_NB = 4, EP_WCOLS = 128;
+            constexpr int EP_NI = 2, EP_NB = 4, EP_WCOLS = 128, EP_I0 = 0, EP_J0 = 0;
 #include "conv3x3_halo8_epilogue.inc"
-        } else {                                                      // a slice: the raw accumulators, 16 B per thread and store (8 KB per workgroup instruction)
-            // (buffer stores with the register's offset in soffset: 128 flat addresses would be hoisted out of the item loop and spilled)
-            const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ws + (size_t)e_slice * (128 * 512)), 0, 128 * 512 * 4, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {                     // four registers per store: [register quad][thread][4]
-                        const u32x4 v = {__float_as_uint(acc[i][j][4 * q]), __float_as_uint(acc[i][j][4 * q + 1]), __float_as_uint(acc[i][j][4 * q + 2]),
-                                         __float_as_uint(acc[i][j][4 * q + 3])};
-                        __builtin_amdgcn_raw_buffer_store_b128(v, rsP, (unsigned)tid * 16u, (unsigned)(((i * 4 + j) * 4 + q) * 8192), 0);
-                    }
+        } else {
+            slice_store(acc, p.ws, e_slice, tid);
         }
     }
     __syncthreads();                                                  // all DMA drained (loop exit), the LDS is free
-    halo8_amax(p, out_amax, (float*)lds, tid);
+    absmax_fold(p.c_absmax, out_amax, (float*)lds, tid, lane, wid);
 }
 
 // The cut tiles: sum the slices' accumulators in slice order (same thread <-> element mapping as the main kernel), then the epilogue of
@@ -377,69 +341,15 @@ template <int POOL, int ACT>
 __global__ __launch_bounds__(512) void conv3x3_halo8_fixup_kernel(const Halo8P p) {
     __shared__ float red[8];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 1, wc = wid & 1, fr = lane & 31, fh = lane >> 5;
-    const int tile = p.n_full + blockIdx.x, m0 = (tile / p.tiles_n) * 256, n0 = (tile % p.tiles_n) * 256;
-    const int bi = blockIdx.y >> 2, bj = blockIdx.y & 3;
-    f32x16 a;
-    const f32x4* src = (const f32x4*)(p.ws + (size_t)blockIdx.x * p.n_slices * (128 * 512)) + (size_t)blockIdx.y * 4 * 512 + tid;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x4 v = src[q * 512];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a[4 * q + e] = v[e];
-    }
-    for (int sl = 1; sl < p.n_slices; ++sl) {
-        src += 32 * 512;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = src[q * 512];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a[4 * q + e] += v[e];
-        }
-    }
-    const int s_a = scale_exp(*p.a_absmax);
-    const int n = n0 + wc * 128 + 32 * bj + fr;
-    const float sv = (p.oscale ? p.oscale[n] : 1.f) * pow2f(-s_a - p.w_exp), bv = p.bias ? p.bias[n] : 0.f;
+    const int tile = p.n_full + blockIdx.x, em0 = (tile / p.tiles_n) * 256, en0 = (tile % p.tiles_n) * 256;
+    f32x16 acc[1][1];
+    slice_sum(acc[0], p.ws, blockIdx.x, p.n_slices, blockIdx.y, tid);
+    const float acc_scale = pow2f(-scale_exp(*p.a_absmax) - p.w_exp);
     float out_amax = 0.f;
-    if constexpr (POOL) {
-        const int mpw = (m0 + wr * 64) >> 2;
-        const long long rows_left = (long long)(p.M >> 2) - mpw;
-        const __amdgpu_buffer_rsrc_t rsC = desc(p.c, rows_left > 0 ? ((rows_left - 1) * p.ldc + p.N) * 4 + (long long)mpw * p.ldc * 4 : 0,
-                                                (long long)mpw * p.ldc * 4);
-        const int row_lim = (int)(rows_left < 1024 ? rows_left : 1024) - fh;
-        const unsigned vc = (unsigned)((fh * p.ldc + n) * 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float sum = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float v = a[4 * k + q] * sv + bv;
-                if (ACT == DBMM_ACT_RELU) v = fmaxf(v, 0.f);
-                sum += v;
-            }
-            sum *= 0.25f;
-            const int u = 8 * bi + 2 * k;
-            const bool valid = u < row_lim;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sum), rsC, valid ? vc : OOR, (unsigned)(u * p.ldc * 4), 0);
-            if (valid) out_amax = fmaxf(out_amax, fabsf(sum));
-        }
-    } else {
-        const int mw = m0 + wr * 64;
-        const long long rows_left = (long long)p.M - mw;
-        const __amdgpu_buffer_rsrc_t rsC = desc(p.c, rows_left > 0 ? ((rows_left - 1) * p.ldc + p.N) * 4 + (long long)mw * p.ldc * 4 : 0,
-                                                (long long)mw * p.ldc * 4);
-        const int row_lim = (int)(rows_left < 1024 ? rows_left : 1024) - 4 * fh;
-        const unsigned vc = (unsigned)((4 * fh * p.ldc + n) * 4);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float v = a[r] * sv + bv;
-            if (ACT == DBMM_ACT_RELU) v = fmaxf(v, 0.f);
-            const int u = 32 * bi + (r & 3) + 8 * (r >> 2);
-            const bool valid = u < row_lim;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, valid ? vc : OOR, (unsigned)(u * p.ldc * 4), 0);
-            if (valid) out_amax = fmaxf(out_amax, fabsf(v));
-        }
-    }
-    halo8_amax(p, out_amax, red, tid);
+    const int EP_I0 = blockIdx.y >> 2, EP_J0 = blockIdx.y & 3;
+    constexpr int EP_NI = 1, EP_NB = 1, EP_WCOLS = 128;
+#include "conv3x3_halo8_epilogue.inc"
+    absmax_fold(p.c_absmax, out_amax, red, tid, lane, wid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -461,9 +371,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo8n_kernel(const Halo8P p) 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 1, wc = wid & 1, grp = wid >> 2;
     const int fr = lane & 31, fh = lane >> 5;
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot_in_xcd = blockIdx.x >> 3, wg_per_xcd = (nwg - xcd + 7) >> 3;
-    const int tq = p.n_tiles >> 3, trm = p.n_tiles & 7;
-    const int t_lo = xcd < trm ? xcd * (tq + 1) : trm * (tq + 1) + (xcd - trm) * tq, t_hi = t_lo + tq + (xcd < trm ? 1 : 0);
+    const TileWalk walk = tile_walk(blockIdx.x, gridDim.x, p.n_tiles);
     __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, 0, 0x00020000), rsW = rsA;
     int m0 = 0, n0 = 0;
     const int G = 3 * (p.Cin >> 5);
@@ -638,13 +546,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo8n_kernel(const Halo8P p) 
     // the zero line of both planes of the three A buffers
     if (tid < 96) *(u32x4*)(lds + N_OFF_A + (tid >> 5) * A_BUF + ((tid >> 4) & 1) * A_PLANE + ZROW * 64 + (tid & 15) * 16) = (u32x4){0u, 0u, 0u, 0u};
 
-    const int n_items = t_lo + slot_in_xcd < t_hi ? (t_hi - t_lo - slot_in_xcd + wg_per_xcd - 1) / wg_per_xcd : 0;
+    const int n_items = walk.n_whole;
     // what a tile needs before its first phases: the weight tiles of its first three taps, its first two groups' strips in registers
     auto prologue = [&]() {
         dma_w(0, 0); dma_w(1, 1); dma_w(2, 2);
         load_strip(ar, ar2, 0); load_strip(br, br2, 1);
     };
-    if (n_items > 0) { set_tile(t_lo + slot_in_xcd); prologue(); }
+    if (n_items > 0) { set_tile(walk.first); prologue(); }
     for (int k = 0; k < n_items; ++k) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -666,14 +574,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo8n_kernel(const Halo8P p) 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         const int em0 = m0, en0 = n0;
-        if (k + 1 < n_items) { set_tile(t_lo + slot_in_xcd + (k + 1) * wg_per_xcd); prologue(); }
+        if (k + 1 < n_items) { set_tile(walk.first + (k + 1) * walk.stride); prologue(); }
         {
-            constexpr int EP_NB = 2, EP_WCOLS = 64;
+            constexpr int EP_NI = 2, EP_NB = 2, EP_WCOLS = 64, EP_I0 = 0, EP_J0 = 0;
 #include "conv3x3_halo8_epilogue.inc"
         }
     }
     __syncthreads();
-    halo8_amax(p, out_amax, (float*)lds, tid);
+    // (lane and wave index as vector values here: with the scalar wave index <0, 1> of THIS kernel picks up 8 bytes of scratch)
+    absmax_fold(p.c_absmax, out_amax, (float*)lds, tid, tid & 63, tid >> 6);
 }
 
 }  // namespace
@@ -705,8 +614,7 @@ int dbmm_conv3x3_halo8(const float* x, const float* x_absmax, const void* w_plan
     if (Cout % 256) {                                                 // 128-channel tiles (layer 2)
         p.tiles_n = (int)(Cout / 128);
         p.n_tiles = (int)((M + 255) / 256) * p.tiles_n;
-        p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-        const int gridn = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;
+        const int gridn = plan_tiles(p, 0, nullptr, 0);              // no K cut (layer 2 has 49+ rounds)
 #define DBMM_H8N(P, A) hipLaunchKernelGGL((conv3x3_halo8n_kernel<P, A>), dim3(gridn), dim3(512), 0, s, p)
         if (pool) { if (act == DBMM_ACT_RELU) DBMM_H8N(1, 1); else DBMM_H8N(1, 0); }
         else { if (act == DBMM_ACT_RELU) DBMM_H8N(0, 1); else DBMM_H8N(0, 0); }
@@ -716,15 +624,7 @@ int dbmm_conv3x3_halo8(const float* x, const float* x_absmax, const void* w_plan
     }
     p.tiles_n = (int)(Cout / 256);
     p.n_tiles = (int)((M + 255) / 256) * p.tiles_n;
-    p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-    const int rem = p.n_tiles % DBMM_N_CU, trips = (int)(3 * (Cin / 32) / 2);
-    if (split && workspace && dbmm_aligned16(workspace) && p.n_tiles > DBMM_N_CU && rem != 0) {
-        const int S = dbmm_cut_slices(rem, trips);
-        if (S >= 2 && (size_t)rem * S * (128 * 512 * sizeof(float)) <= workspace_bytes) {
-            p.n_full = p.n_tiles - rem; p.n_cut = rem; p.n_slices = S; p.ws = (float*)workspace;
-        }
-    }
-    const int grid = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;             // persistent: one workgroup per CU
+    const int grid = plan_tiles(p, split ? dbmm_cut_slices(p.n_tiles % DBMM_N_CU, (int)(3 * (Cin / 32) / 2)) : 0, workspace, workspace_bytes);
 #define DBMM_H8(P, A) hipLaunchKernelGGL((conv3x3_halo8_kernel<P, A>), dim3(grid), dim3(512), 0, s, p)
     if (pool) { if (act == DBMM_ACT_RELU) DBMM_H8(1, 1); else DBMM_H8(1, 0); }
     else { if (act == DBMM_ACT_RELU) DBMM_H8(0, 1); else DBMM_H8(0, 0); }

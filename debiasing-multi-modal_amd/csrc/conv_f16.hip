@@ -30,7 +30,7 @@
 //
 // Bounds: conv3x3 MFMA (2500 TFLOP/s dense fp16); stem / pool HBM.
 #include <stdlib.h>
-#include "common.h"
+#include "persistent_tiles.h"
 
 namespace {
 
@@ -684,9 +684,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16_8ph_kernel(const ConvHP p)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 1, wc = wid & 1, grp = wid >> 2;
     const int fr = lane & 31, fh = lane >> 5;
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot_in_xcd = blockIdx.x >> 3, wg_per_xcd = (nwg - xcd + 7) >> 3;
-    const int tq = p.n_tiles >> 3, trm = p.n_tiles & 7;
-    const int t_lo = xcd < trm ? xcd * (tq + 1) : trm * (tq + 1) + (xcd - trm) * tq, t_hi = t_lo + tq + (xcd < trm ? 1 : 0);
+    const TileWalk walk = tile_walk(blockIdx.x, gridDim.x, p.n_tiles);
     __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, 0, 0x00020000), rsW = rsA;
     int m0 = 0, n0 = 0;
     const int G = 3 * (p.Cin >> 5);
@@ -824,13 +822,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16_8ph_kernel(const ConvHP p)
     if (tid < 48) *(u32x4*)(lds + E_OFF_A + (tid >> 4) * E_ABUF + E_ZROW * 64 + (tid & 15) * 16) = (u32x4){0u, 0u, 0u, 0u};
     __syncthreads();
 
-    const int n_items = t_lo + slot_in_xcd < t_hi ? (t_hi - t_lo - slot_in_xcd + wg_per_xcd - 1) / wg_per_xcd : 0;
+    const int n_items = walk.n_whole;
     // what a tile needs before its first phases: both halves of taps 0 and 1, half 0 of tap 2; the strips of groups 0 and 1
     auto prologue = [&]() {
         dma_w(0, 0, 0); dma_w(1, 0, 0); dma_w(0, 1, 1); dma_w(1, 1, 1); dma_w(0, 2, 2);
         dma_a(0, 0); dma_a(1, 1);
     };
-    if (n_items > 0) { set_tile(t_lo + slot_in_xcd); prologue(); }
+    if (n_items > 0) { set_tile(walk.first); prologue(); }
     for (int k = 0; k < n_items; ++k) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -854,7 +852,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16_8ph_kernel(const ConvHP p)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the look-ahead DMAs past the last tap
         __builtin_amdgcn_s_barrier();
         const int em0 = m0, en0 = n0;
-        if (k + 1 < n_items) { set_tile(t_lo + slot_in_xcd + (k + 1) * wg_per_xcd); prologue(); }   // in flight during the epilogue below
+        if (k + 1 < n_items) { set_tile(walk.first + (k + 1) * walk.stride); prologue(); }   // in flight during the epilogue below
 
         // epilogue: BatchNorm scale / bias, ReLU, (2x2 average), packed fp16 stores straight from the accumulators (as conv3x3_f16_kernel)
 #pragma unroll

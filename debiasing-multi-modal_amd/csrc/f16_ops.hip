@@ -12,7 +12,7 @@
 //
 // Bounds: GEMM and attention MFMA (2500 TFLOP/s dense fp16), the rest HBM.
 #include <stdlib.h>
-#include "common.h"
+#include "persistent_tiles.h"
 
 namespace {
 
@@ -240,26 +240,16 @@ __global__ __launch_bounds__(256, MINB) void gemm_f16_kernel(const GemmHP p) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // GEMM, deep-pipelined: 256 x 256 x 64 tiles, 8 waves (2 x 4, 128 x 64 of output each), one workgroup per CU.
-// The structure of cdna_hip_programming.md section 5 ("256^2 8-phase"), re-derived for this kernel's 32x32x16 fp16 MFMA:
-//   * operands reach LDS by LDS-DMA (buffer_load ... lds, 1 KB per wave instruction): no staging registers, no ds_write;
-//     the XOR swizzle that keeps ds_read_b128 conflict-free is applied to the SOURCE chunk index;
-//   * a K tile is four HALF-TILES of 128 rows x 64 k (16 KB): Ah0 / Ah1 = the first / second 64 rows of both wave rows'
-//     A blocks, Bh0 / Bh1 = the first / second 32 columns of all four wave columns' W blocks.  A wave walks its 128 x 64
-//     block as four 64 x 32 quadrants, one per PHASE: (A0,B0) (A0,B1) (A1,B1) (A1,B0), so a phase needs at most one new
-//     half of each operand (12 / 4 / 8 / 0 ds_read_b128) and every half-tile has ONE phase in which it is first needed;
-//   * each phase also stages one half-tile (2 DMA instructions per thread) for five phases later; s_waitcnt vmcnt(6)
-//     (three half-tiles stay in flight -- the queue is never drained in the loop) retires the one staged three phases ago,
-//     which is read one phase after that wait; a slot is restaged >= 3 phases after its last read.  Two LDS buffers
-//     x four half-tiles = 128 KB;
-//   * the wave rows run ONE BARRIER APART: while waves 0-3 issue their 8 MFMAs (256 cycles, s_setprio 1) waves 4-7 do
-//     their LDS reads, DMA issue and waits, and vice versa -- each SIMD's two waves alternate on the matrix pipe.
+// The structure of cdna_hip_programming.md section 5 ("256^2 8-phase"), re-derived for this kernel's 32x32x16 fp16 MFMA: the ring of
+// LDS-DMA half-tiles, its phases and counted waits are fp16_ring.inc (shared with pairdist_tile_kernel); what is this kernel's:
+//   * how a K tile maps to its operands (ring_src below; TWO: a second operand pair runs first);
 //   * with one workgroup per CU nothing else hides a tile's first round trip or its epilogue, so the workgroups are
-//     PERSISTENT (one per CU, each walking a contiguous tile range of its XCD) and the next tile's first five half-tiles
+//     PERSISTENT (tile_walk / work_item, persistent_tiles.h) and the next item's first five half-tiles
 //     are issued BEFORE the current tile's epilogue, which needs no LDS: the W half-tiles are the even / odd columns,
-//     so a lane's two accumulator blocks are adjacent columns and every register is one packed dword of a full row segment.
+//     so a lane's two accumulator blocks are adjacent columns and every register is one packed dword of a full row segment
+//     (gemm_f16_8ph_epilogue.inc).
 // Needs N % 256 == 0 and K % 128 == 0 (two K tiles per loop trip).  Epilogue as in gemm_f16_kernel.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int PH_HALF = 128 * 64 * 2;                              // bytes of a half-tile
 #ifndef GF16_DEPHASE
 #define GF16_DEPHASE 0
 #endif
@@ -273,21 +263,14 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_8ph_kernel(const GemmHP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 2, wc = wid & 3;
     const int fr = lane & 31, fh = lane >> 5;
-    // this workgroup's tiles: the XCD's contiguous range (xcd_remap's split), walked with the stride of the XCD's workgroups
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot_in_xcd = blockIdx.x >> 3, wg_per_xcd = (nwg - xcd + 7) >> 3;
-    const int tq = p.n_full >> 3, trm = p.n_full & 7;
-    const int t_lo = xcd < trm ? xcd * (tq + 1) : trm * (tq + 1) + (xcd - trm) * tq, t_hi = t_lo + tq + (xcd < trm ? 1 : 0);
+    const int nwg = gridDim.x;
+    const TileWalk walk = tile_walk(blockIdx.x, nwg, p.n_full);
     const __amdgpu_buffer_rsrc_t rsA0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, 0, 0x00020000);
     __amdgpu_buffer_rsrc_t rsA = rsA0, rsW = rsW0, rsA2 = rsA0, rsW2 = rsW0;
     int m0 = 0, n0 = 0;
     float rr0 = 1.f, rr1 = 1.f;                                      // TWO: ratio of this lane's two output columns
-    // stager: thread -> LDS chunk (tid + 512 i) of a half-tile = local row (tid >> 3) + 64 i, slot tid & 7; it fetches
-    // source chunk slot ^ swz(row).  Half-tile kind k = 0..3 (Ah0, Bh0, Bh1, Ah1) -> operand rows:
-    //   A half h: tile row (lr >> 6) * 128 + h * 64 + (lr & 63);   W half h: tile column (lr >> 5) * 64 + 2 * (lr & 31) + h
-    //   (W half 0 = the EVEN columns of every wave column's 64, half 1 = the odd ones: accumulator blocks j = 0 / 1 of a lane
-    //    are then two ADJACENT output columns -- one packed dword in the epilogue)
-    unsigned voff[4][2];
+    unsigned voff[4][2];                                             // the stager's lane offsets per half-tile kind (Ah0, Bh0, Bh1, Ah1); rows >= M masked
     auto set_tile = [&](int tile) {
         m0 = (tile / p.tiles_n) * 256; n0 = (tile % p.tiles_n) * 256;
         rsA = desc(p.a, p.a_total, (long long)m0 * p.lda * 2);
@@ -301,125 +284,51 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_8ph_kernel(const GemmHP p) {
         if constexpr (!TWO)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int lr = (tid >> 3) + 64 * i, c = (tid & 7) ^ ((lr >> 1) & 7);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const int ra = (lr >> 6) * 128 + h * 64 + (lr & 63), rw = (lr >> 5) * 64 + 2 * (lr & 31) + h;
-                voff[h ? 3 : 0][i] = m0 + ra < p.M ? (unsigned)ra * (unsigned)(p.lda * 2) + c * 16u : OOR;
-                voff[h ? 2 : 1][i] = (unsigned)rw * (unsigned)(p.ldw * 2) + c * 16u;
+                int ra, rw;
+                unsigned cb;
+                ring_rows(tid, i, h, ra, rw, cb);
+                voff[h ? 3 : 0][i] = m0 + ra < p.M ? (unsigned)ra * (unsigned)(p.lda * 2) + cb : OOR;
+                voff[h ? 2 : 1][i] = (unsigned)rw * (unsigned)(p.ldw * 2) + cb;
             }
         }
     };
     const int nT2 = TWO ? p.K2 / 64 : 0, nT = nT2 + p.K / 64;       // K tiles of the second pair (they run first) / in all
-    // stage number q: kind q & 3 of K tile q >> 2 into buffer (q >> 2) & 1; tiles past the end go through the zero-extent
-    // descriptors so that every phase issues exactly two DMA instructions per wave (the vmcnt arithmetic relies on it)
+    // K tile t of half-tile kind `kind`: tiles past the end go through the zero-extent descriptors
     // (TWO: the second pair's lane offsets are recomputed here -- eight more registers spilled inside the loop --, and tiles past the end
     //  fetch whatever follows into buffers no phase reads again: two-way descriptor selects only)
-    auto stage = [&](int kind, int buf, int t) {
+    auto ring_src = [&](int kind, int t, __amdgpu_buffer_rsrc_t& rs, unsigned (&vo)[2], unsigned& so) {
         const bool isA = kind == 0 || kind == 3, valid = t < nT, second = TWO && t < nT2;
-        unsigned char* slot = lds + (buf * 4 + kind) * PH_HALF + wid * 1024;
         if constexpr (TWO) {
-            const __amdgpu_buffer_rsrc_t rs = isA ? (second ? rsA2 : rsA) : (second ? rsW2 : rsW);
+            rs = isA ? (second ? rsA2 : rsA) : (second ? rsW2 : rsW);
             const int h = kind >> 1;                                  // kinds 0, 1 -> half 0; 2, 3 -> half 1
             int tid_o = tid;
             asm volatile("" : "+v"(tid_o));                           // opaque: the offsets below are loop-invariant and would be hoisted (and spilled)
             const unsigned ld2 = (unsigned)((isA ? (second ? p.lda2 : p.lda) : (second ? p.ldw2 : p.ldw)) * 2);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int lr = (tid_o >> 3) + 64 * i, c = (tid_o & 7) ^ ((lr >> 1) & 7);
-                const int ra = (lr >> 6) * 128 + h * 64 + (lr & 63), rw = (lr >> 5) * 64 + 2 * (lr & 31) + h;
-                const unsigned vo = isA ? (m0 + ra < p.M ? (unsigned)ra * ld2 + c * 16u : OOR) : (unsigned)rw * ld2 + c * 16u;
-                glds16(rs, slot + i * 8192, vo, (unsigned)(second ? t : t - nT2) * 128u);
+                int ra, rw;
+                unsigned cb;
+                ring_rows(tid_o, i, h, ra, rw, cb);
+                vo[i] = isA ? (m0 + ra < p.M ? (unsigned)ra * ld2 + cb : OOR) : (unsigned)rw * ld2 + cb;
             }
+            so = (unsigned)(second ? t : t - nT2) * 128u;
         } else {
-            const __amdgpu_buffer_rsrc_t rs = isA ? (valid ? rsA : rsA0) : (valid ? rsW : rsW0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) glds16(rs, slot + i * 8192, voff[kind][i], (unsigned)t * 128u);
+            rs = isA ? (valid ? rsA : rsA0) : (valid ? rsW : rsW0);
+            vo[0] = voff[kind][0]; vo[1] = voff[kind][1];
+            so = (unsigned)t * 128u;
         }
     };
-    // fragment addresses inside a half-tile (bytes): A rows wr * 64 + blk * 32 + fr, W rows wc * 32 + fr, chunk (2 ks + fh) ^ swz
-    int aoff[2][4], boff[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int r = wr * 64 + b * 32 + fr;
-            aoff[b][ks] = r * 128 + (((2 * ks + fh) ^ ((r >> 1) & 7)) << 4);
-        }
-        const int r = wc * 32 + fr;
-        boff[ks] = r * 128 + (((2 * ks + fh) ^ ((r >> 1) & 7)) << 4);
-    }
-    f32x16 acc[4][2];
-    u32x4 fa[2][4], fb0[4], fb1[4];
+#include "fp16_ring.inc"
 
-    // one phase: j = phase within the loop trip (static), t2 = first K tile of the trip
-    // `first`: the tile's first trip.  Its prologue has staged both K tiles of the trip (stages 0 .. 7), so phases 0 - 2 stage
-    // nothing and phases 0 - 4 wait for nothing: the first counted wait (phase 5) is where the previous tile's epilogue stores
-    // -- older in the queue than every DMA of this tile -- have to be acknowledged, 2000+ cycles after they were issued,
-    // instead of at the top of the tile.
-    auto phase = [&](int j, int t2, bool first) {
-        const int ph = j & 3, buf = (j >> 2) & 1;
-        const unsigned char* base = lds + buf * 4 * PH_HALF;
-        if (ph == 0) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) fb0[ks] = *(const u32x4*)(base + 1 * PH_HALF + boff[ks]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) fa[b][ks] = *(const u32x4*)(base + 0 * PH_HALF + aoff[b][ks]);
-        } else if (ph == 1) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) fb1[ks] = *(const u32x4*)(base + 2 * PH_HALF + boff[ks]);
-        } else if (ph == 2) {
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) fa[b][ks] = *(const u32x4*)(base + 3 * PH_HALF + aoff[b][ks]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(first && j < 3)) {
-            const int q = j + 5;                                      // stage number relative to the trip's first tile
-            stage(q & 3, (q >> 2) & 1, t2 + (q >> 2));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(first && j < 5)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-        const int ai = (ph >= 2) ? 2 : 0, bj = (ph == 1 || ph == 2) ? 1 : 0;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-                acc[ai + b][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[b][ks]),
-                                                                         __builtin_bit_cast(f16x8, bj ? fb1[ks] : fb0[ks]), acc[ai + b][bj], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-    };
-
-    // Work items of this workgroup: its whole tiles (all K tiles), then -- if there are cut tiles and this workgroup's index is below
-    // n_cut * n_slices -- one slice: a cut tile's loop trips [s T / S, (s + 1) T / S)
-    const int n_whole = t_lo + slot_in_xcd < t_hi ? (t_hi - t_lo - slot_in_xcd + wg_per_xcd - 1) / wg_per_xcd : 0;
-    const bool has_slice = !TWO && (int)blockIdx.x < p.n_cut * p.n_slices;
-    const int n_items = n_whole + (has_slice ? 1 : 0);
-    int tb = 0, te = nT;                                              // the current item's K tiles [tb, te), both even
+    const int n_items = walk.n_whole + work_slices(blockIdx.x, nwg, TWO ? 0 : p.n_cut * p.n_slices);
+    WorkItem item{};                                                  // the item whose prologue was issued last; its loop trips are two K tiles each
     auto set_item = [&](int k) {
-        if (k < n_whole) { tb = 0; te = nT; set_tile(t_lo + slot_in_xcd + k * wg_per_xcd); }
-        else {
-            const int l = blockIdx.x / p.n_slices, sl = blockIdx.x - l * p.n_slices, T = nT >> 1;
-            tb = 2 * (sl * T / p.n_slices); te = 2 * ((sl + 1) * T / p.n_slices);
-            set_tile(p.n_full + l);
-        }
+        item = work_item(walk, k, blockIdx.x, nwg, p.n_full, p.n_slices, nT >> 1);
+        set_tile(item.tile);
+        ring_prologue(2 * item.trip_lo);
     };
-    // prologue of an item: stages 0 .. 7 = its first two K tiles, both buffers
-    auto prologue = [&]() {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) stage(q & 3, (q >> 2) & 1, tb + (q >> 2));
-    };
-    const int wm0 = wr * 128, wn0 = wc * 64;
 
     bool first_tile = true;
     // De-phase the workgroups.  Every tile takes the same time, so persistent workgroups that start together reach their
@@ -427,115 +336,33 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_8ph_kernel(const GemmHP p) {
     // the main loops -- measured as a FIXED 14-16 us per tile whatever K (K sweep, tools/bench_gemm_f16.py).  The groups
     // of workgroups that share an A tile (tiles_n consecutive slots of an XCD; kept in step for the L2) start spread
     // over one tile time instead.
-    if (GF16_DEPHASE && (t_hi - t_lo) >= 3 * wg_per_xcd) {
-        const int per = (wg_per_xcd + p.tiles_n - 1) / p.tiles_n, grp = (slot_in_xcd / p.tiles_n) + per * xcd, ngrp = per * 8;
+    if (GF16_DEPHASE && walk.span >= 3 * walk.stride) {
+        const int per = (walk.stride + p.tiles_n - 1) / p.tiles_n, grp = ((blockIdx.x >> 3) / p.tiles_n) + per * (blockIdx.x & 7), ngrp = per * 8;
         const int units = (int)((long long)grp * nT * 1400 / ngrp) >> 10;       // ~1400 cycles per K tile, s_sleep 16 = 1024 cycles
         for (int u = 0; u < units; ++u) __builtin_amdgcn_s_sleep(16);
     }
-    if (n_items > 0) { set_item(0); prologue(); }
+    if (n_items > 0) set_item(0);
     for (int k = 0; k < n_items; ++k) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    // The prologue's 16 DMA instructions must have landed; the 64 epilogue stores issued AFTER them need not have been
-    // acknowledged yet (4.6 us of a tile's fixed cost when they were waited for here): vmcnt(63) leaves at most 63 of the
-    // 80 outstanding, i.e. retires the 16 DMAs (and one store).  The first tile has no stores behind its prologue.
-    if (first_tile) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-    first_tile = false;
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();                        // the second wave row runs one barrier behind
-#pragma unroll
-    for (int j = 0; j < 8; ++j) phase(j, tb, true);
-    for (int t2 = tb + 2; t2 < ((GF16_ABL & 8) ? tb + 2 : te); t2 += 2) {
-        if (TWO && t2 == nT2) {                                       // the second pair's sums -> the main pair's scale (K2 / 64 and t2 are even)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { acc[i][0][r] *= rr0; acc[i][1][r] *= rr1; }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) phase(j, t2, false);
-    }
-    if (wr == 0) __builtin_amdgcn_s_barrier();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the look-ahead DMA past this item's last K tile
-    __builtin_amdgcn_s_barrier();                                     // every wave is done with the ring
-    const int em0 = m0, en0 = n0;
-    const bool whole = k < n_whole;
-    if (k + 1 < n_items) { set_item(k + 1); prologue(); }             // in flight during the epilogue below
-    if (!whole) {                                                     // a slice: the raw accumulators, 16 B per thread and store
-        const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ws + (size_t)blockIdx.x * (128 * 512)), 0, 128 * 512 * 4, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const u32x4 v = {__float_as_uint(acc[i][j][4 * q]), __float_as_uint(acc[i][j][4 * q + 1]), __float_as_uint(acc[i][j][4 * q + 2]),
-                                     __float_as_uint(acc[i][j][4 * q + 3])};
-                    __builtin_amdgcn_raw_buffer_store_b128(v, rsP, (unsigned)tid * 16u, (unsigned)(((i * 2 + j) * 4 + q) * 8192), 0);
-                }
-        continue;
-    }
-
-    // epilogue straight from the accumulators, no LDS: lane (fr, fh) holds output columns 2 fr and 2 fr + 1 (blocks j = 0 / 1,
-    // see the stager's column map) of rows 32 i + (r & 3) + 8 (r >> 2) + 4 fh: one packed dword per register, 32 lanes = one
-    // whole 128-B row segment, two rows per wave instruction -- the full-rate access shape, residual loads likewise.
-    // (Through the LDS transpose of gemm_f16_kernel the 68 KB of fp32 staging writes cost as much as the MFMAs of two K
-    //  tiles; with swapped MFMA operands -- a lane owning 4 columns of ITS row, 8-B accesses to 32 different lines per
-    //  instruction -- the vector-memory path made it slower still: 848 -> 663 TF on the out-projection shape.)
-    {
-        const int n = en0 + wn0 + 2 * fr;
-        float bn0 = 0.f, bn1 = 0.f, sn0 = 1.f, sn1 = 1.f;
-        if (p.bias) { bn0 = p.bias[n]; bn1 = p.bias[n + 1]; }
-        if (p.oscale) { sn0 = p.oscale[n]; sn1 = p.oscale[n + 1]; }
-        const bool rf = p.res_first != 0;
-        // descriptors rebased to the wave's first row: the extent ends with the last valid row, so rows past M are dropped
-        // by the hardware (no branches); lane offset = its column pair + its half's 4-row step, the row of a register is a
-        // wave-uniform scalar offset
-        const int mw = em0 + wm0;
-        const long long rows_left = (long long)p.M - mw;
-        const __amdgpu_buffer_rsrc_t rsC = desc(p.c, rows_left > 0 ? ((rows_left - 1) * p.ldc + p.N) * 2 + (long long)mw * p.ldc * 2 : 0, (long long)mw * p.ldc * 2);
-        const __amdgpu_buffer_rsrc_t rsR = p.res ? desc(p.res, rows_left > 0 ? ((rows_left - 1) * p.ldr + p.N) * 2 + (long long)mw * p.ldr * 2 : 0, (long long)mw * p.ldr * 2)
-                                                 : __builtin_amdgcn_make_buffer_rsrc((void*)p.c, 0, 0, 0x00020000);
-        const unsigned vc = (unsigned)((4 * fh * p.ldc + n) * 2), vr = (unsigned)((4 * fh * p.ldr + n) * 2);
-        // Rows >= M of a ragged last tile are masked BY LANE (an out-of-range voffset) instead of being left to the extent:
-        // their row offset travels in soffset, which can exceed num_records there (range check: offset >= num_records -
-        // soffset).  A full tile pays nothing.
-        const int row_lim = (int)(rows_left < 1024 ? rows_left : 1024) - 4 * fh;     // row u of this lane is valid iff u < row_lim
-        auto epilogue = [&](auto full_tag) {
-            constexpr bool FULL = decltype(full_tag)::value;
-            // all 64 residual loads in flight together (the fragment registers are dead here): one round trip, not four
-            unsigned rvv[RES ? 4 : 1][16];
-            if constexpr (RES) {
+        const int tb = 2 * item.trip_lo, te = 2 * item.trip_hi, e_slice = item.slice;
+        // (the first item has no epilogue stores behind its prologue: drain)
+        ring_item(tb, (GF16_ABL & 8) ? tb + 2 : te, first_tile, [&](int t2) {
+            if (TWO && t2 == nT2) {                                   // the second pair's sums -> the main pair's scale (K2 / 64 and t2 are even)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int ru = 32 * i + (r & 3) + 8 * (r >> 2);
-                        rvv[i][r] = __builtin_amdgcn_raw_buffer_load_b32(rsR, (FULL || ru < row_lim) ? vr : OOR, (unsigned)(ru * p.ldr * 2), 0);
-                    }
+                    for (int r = 0; r < 16; ++r) { acc[i][0][r] *= rr0; acc[i][1][r] *= rr1; }
             }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const f16x2 rh = __builtin_bit_cast(f16x2, RES ? rvv[i][r] : 0u);
-                    const float r0 = RES ? (float)rh[0] : 0.f, r1 = RES ? (float)rh[1] : 0.f;
-                    float o0 = act_f(fmaf(acc[i][0][r], sn0, bn0) + (rf ? r0 : 0.f), ACT), o1 = act_f(fmaf(acc[i][1][r], sn1, bn1) + (rf ? r1 : 0.f), ACT);
-                    if (RES) { o0 += rf ? 0.f : r0; o1 += rf ? 0.f : r1; }
-                    if (GF16_ABL & 2) { asm volatile("" ::"v"(acc[i][0][r]), "v"(acc[i][1][r]), "v"(rh)); continue; }
-                    if (GF16_ABL & 1) { asm volatile("" ::"v"(pack2(o0, o1))); continue; }
-                    const int ru = 32 * i + (r & 3) + 8 * (r >> 2);
-                    __builtin_amdgcn_raw_buffer_store_b32(pack2(o0, o1), rsC, (FULL || ru < row_lim) ? vc : OOR, (unsigned)(ru * p.ldc * 2), 0);
-                }
-            }
-        };
-        if (rows_left >= 128) epilogue(std::true_type{}); else epilogue(std::false_type{});
-    }
+        });
+        first_tile = false;
+        const int em0 = m0, en0 = n0;
+        const bool whole = k < walk.n_whole;
+        if (k + 1 < n_items) set_item(k + 1);                         // in flight during the epilogue below
+        if (!whole) { slice_store(acc, p.ws, e_slice, tid); continue; }
+        {
+            constexpr int EP_NI = 4, EP_I0 = 0;
+            constexpr bool EP_FULL = true;
+#include "gemm_f16_8ph_epilogue.inc"
+        }
     }
 }
 
@@ -544,52 +371,13 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_8ph_kernel(const GemmHP p) {
 template <int ACT, int RES>
 __global__ __launch_bounds__(512) void gemm_f16_8ph_fixup_kernel(const GemmHP p) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3, fr = lane & 31, fh = lane >> 5;
-    const int tile = p.n_full + blockIdx.x, m0 = (tile / p.tiles_n) * 256, n0 = (tile % p.tiles_n) * 256, bi = blockIdx.y;
-    f32x16 a0, a1;
-    const f32x4* src = (const f32x4*)(p.ws + (size_t)blockIdx.x * p.n_slices * (128 * 512)) + (size_t)bi * 8 * 512 + tid;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x4 v = src[q * 512], u = src[(4 + q) * 512];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { a0[4 * q + e] = v[e]; a1[4 * q + e] = u[e]; }
-    }
-    for (int sl = 1; sl < p.n_slices; ++sl) {
-        src += 32 * 512;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = src[q * 512], u = src[(4 + q) * 512];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { a0[4 * q + e] += v[e]; a1[4 * q + e] += u[e]; }
-        }
-    }
-    const int n = n0 + wc * 64 + 2 * fr, mw = m0 + wr * 128;
-    float bn0 = 0.f, bn1 = 0.f, sn0 = 1.f, sn1 = 1.f;
-    if (p.bias) { bn0 = p.bias[n]; bn1 = p.bias[n + 1]; }
-    if (p.oscale) { sn0 = p.oscale[n]; sn1 = p.oscale[n + 1]; }
-    const bool rf = p.res_first != 0;
-    const long long rows_left = (long long)p.M - mw;
-    const __amdgpu_buffer_rsrc_t rsC = desc(p.c, rows_left > 0 ? ((rows_left - 1) * p.ldc + p.N) * 2 + (long long)mw * p.ldc * 2 : 0, (long long)mw * p.ldc * 2);
-    const __amdgpu_buffer_rsrc_t rsR = p.res ? desc(p.res, rows_left > 0 ? ((rows_left - 1) * p.ldr + p.N) * 2 + (long long)mw * p.ldr * 2 : 0, (long long)mw * p.ldr * 2)
-                                             : __builtin_amdgcn_make_buffer_rsrc((void*)p.c, 0, 0, 0x00020000);
-    const unsigned vc = (unsigned)((4 * fh * p.ldc + n) * 2), vr = (unsigned)((4 * fh * p.ldr + n) * 2);
-    const int row_lim = (int)(rows_left < 1024 ? rows_left : 1024) - 4 * fh;
-    unsigned rvv[16];
-    if constexpr (RES) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ru = 32 * bi + (r & 3) + 8 * (r >> 2);
-            rvv[r] = __builtin_amdgcn_raw_buffer_load_b32(rsR, ru < row_lim ? vr : OOR, (unsigned)(ru * p.ldr * 2), 0);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const f16x2 rh = __builtin_bit_cast(f16x2, RES ? rvv[r] : 0u);
-        const float r0 = RES ? (float)rh[0] : 0.f, r1 = RES ? (float)rh[1] : 0.f;
-        float o0 = act_f(fmaf(a0[r], sn0, bn0) + (rf ? r0 : 0.f), ACT), o1 = act_f(fmaf(a1[r], sn1, bn1) + (rf ? r1 : 0.f), ACT);
-        if (RES) { o0 += rf ? 0.f : r0; o1 += rf ? 0.f : r1; }
-        const int ru = 32 * bi + (r & 3) + 8 * (r >> 2);
-        __builtin_amdgcn_raw_buffer_store_b32(pack2(o0, o1), rsC, ru < row_lim ? vc : OOR, (unsigned)(ru * p.ldc * 2), 0);
-    }
+    const int tile = p.n_full + blockIdx.x, em0 = (tile / p.tiles_n) * 256, en0 = (tile % p.tiles_n) * 256;
+    f32x16 acc[1][2];
+    slice_sum(acc[0], p.ws, blockIdx.x, p.n_slices, 2 * blockIdx.y, tid);
+    const int EP_I0 = blockIdx.y;
+    constexpr int EP_NI = 1;
+    constexpr bool EP_FULL = false;
+#include "gemm_f16_8ph_epilogue.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1026,8 +814,7 @@ extern "C" int dbmm_conv1x1_dual_bn_act_f16(const void* y2, const void* w3, cons
     p.M = (int)M; p.N = (int)Cout; p.K = (int)K; p.act = act;
     p.tiles_n = (int)(Cout / 256);
     p.n_tiles = (int)((M + 255) / 256) * p.tiles_n;
-    p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-    const int grid = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;
+    const int grid = plan_tiles(p, 0, nullptr, 0);                   // no K cut with two operand pairs
     if (act == DBMM_ACT_RELU) hipLaunchKernelGGL((gemm_f16_8ph_kernel<1, 0, 1>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((gemm_f16_8ph_kernel<0, 0, 1>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p);
     DBMM_CHECK_LAUNCH();
@@ -1065,20 +852,17 @@ int gemm_f16_impl(const void* a, int64_t lda, const void* w, int64_t ldw, const 
             // launch of <= 512 tiles (one pass over the chip's 2 x 256 slots) that costs about 0.4 of an eight-phase round.
             // With a workspace the tiles of the short last round (at most 128) are instead cut along K into S = min(256 / tiles, trips)
             // slices, one workgroup each, and gemm_f16_8ph_fixup_kernel sums them and runs the epilogue (as gemm_pair_8ph.hip).
-            p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-            if (part == 0 && dbmm_opt(OPT_TAIL_SPLIT) && p.n_tiles > DBMM_N_CU && (p.n_tiles % DBMM_N_CU) != 0) {
-                const int rem = p.n_tiles % DBMM_N_CU, trips = (int)(K / 128);
-                int S = rem <= DBMM_N_CU / 2 ? DBMM_N_CU / rem : 1;
-                S = S < trips ? S : trips;
-                const int mode = dbmm_opt(OPT_TAIL_SPLIT);            // 1: by rule, 2: the K cut wherever it applies, 3: the row split only
-                // same box, tools/bench_tail_f16.py (profiles/r04_ab_tail_f16.log): the cut pays on long K only -- ViT-B/32's c_proj (K 3072, 300 /
-                // 600 tiles) 160 -> 149 us / 261 -> 251 us; K <= 2048 shapes lose 1-10 % to the slices' fixed cost (prologue, 256 KB of fp32
-                // partial sums per slice against a 128-KB fp16 tile, the second launch)
-                const bool cut_pays = K >= 3072 && rem >= 32;
-                if ((mode == 2 || (mode == 1 && cut_pays)) && workspace && dbmm_aligned16(workspace) && S >= 2 &&
-                    (size_t)rem * S * (128 * 512 * sizeof(float)) <= workspace_bytes) {
-                    p.n_full = p.n_tiles - rem; p.n_cut = rem; p.n_slices = S; p.ws = (float*)workspace;
-                } else {
+            const int rem = p.n_tiles % DBMM_N_CU, trips = (int)(K / 128);
+            // a short last round of more than one: 1: by rule, 2: the K cut wherever it applies, 3: the row split only
+            const int mode = part == 0 && p.n_tiles > DBMM_N_CU && rem != 0 ? dbmm_opt(OPT_TAIL_SPLIT) : 0;
+            int S = rem <= DBMM_N_CU / 2 && rem > 0 ? DBMM_N_CU / rem : 1;
+            S = S < trips ? S : trips;
+            // same box, tools/bench_tail_f16.py (profiles/r04_ab_tail_f16.log): the cut pays on long K only -- ViT-B/32's c_proj (K 3072, 300 /
+            // 600 tiles) 160 -> 149 us / 261 -> 251 us; K <= 2048 shapes lose 1-10 % to the slices' fixed cost (prologue, 256 KB of fp32
+            // partial sums per slice against a 128-KB fp16 tile, the second launch)
+            const bool cut_pays = K >= 3072 && rem >= 32;
+            const int grid = plan_tiles(p, mode == 2 || (mode == 1 && cut_pays) ? S : 0, workspace, workspace_bytes);   // persistent: one workgroup per CU
+            if (mode && !p.n_cut) {
                 const int64_t mt = (M + 255) / 256, full_rounds = p.n_tiles / DBMM_N_CU, mt_full = full_rounds * DBMM_N_CU / p.tiles_n;
                 const int64_t m_split = mt_full * 256, tail_rows = M - m_split;
                 const int64_t tail_tiles = ((tail_rows + 127) / 128) * ((N + 127) / 128);
@@ -1090,9 +874,7 @@ int gemm_f16_impl(const void* a, int64_t lda, const void* w, int64_t ldw, const 
                                          residual ? (const void*)((const u16*)residual + m_split * ldr) : nullptr, ldr, res_first,
                                          (u16*)c + m_split * ldc, ldc, tail_rows, N, K, act, stream, 2, nullptr, 0);
                 }
-                }
             }
-            const int grid = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;   // persistent: one workgroup per CU
             hipStream_t s8 = (hipStream_t)stream;
 #define DBMM_8PH(A, R) hipLaunchKernelGGL((gemm_f16_8ph_kernel<A, R>), dim3(grid), dim3(512), 0, s8, p)
             if (residual) { if (act == 0) DBMM_8PH(0, 1); else if (act == 1) DBMM_8PH(1, 1); else DBMM_8PH(2, 1); }

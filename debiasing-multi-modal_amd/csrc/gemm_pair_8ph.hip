@@ -18,7 +18,7 @@
 // accumulator layout (one register = two 128-B fp32 row segments), branch-free buffer accesses, activation / residual
 // compile-time.  Needs N % 256 == 0, K % 64 == 0.
 #include <stdlib.h>
-#include "common.h"
+#include "persistent_tiles.h"
 
 namespace {
 
@@ -50,10 +50,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pair_8ph_kernel(const PairP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 1, wc = wid & 1, grp = wid >> 2;   // 4 x 2 waves, two groups of four
     const int fr = lane & 31, fh = lane >> 5;
-    // this workgroup's tiles: its XCD's contiguous range (xcd_remap's split), walked with the stride of the XCD's workgroups
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot_in_xcd = blockIdx.x >> 3, wg_per_xcd = (nwg - xcd + 7) >> 3;
-    const int tq = p.n_full >> 3, trm = p.n_full & 7;
-    const int t_lo = xcd < trm ? xcd * (tq + 1) : trm * (tq + 1) + (xcd - trm) * tq, t_hi = t_lo + tq + (xcd < trm ? 1 : 0);
+    const int nwg = gridDim.x;
+    const TileWalk walk = tile_walk(blockIdx.x, nwg, p.n_full);
     const __amdgpu_buffer_rsrc_t rsA0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, 0, 0x00020000);
     __amdgpu_buffer_rsrc_t rsA = rsA0, rsW = rsW0, rsA2 = rsA0, rsW2 = rsW0;
@@ -215,24 +213,15 @@ __global__ __launch_bounds__(512, 1) void gemm_pair_8ph_kernel(const PairP p) {
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
     };
-    const int wm0 = wr * 64, wn0 = wc * 128;
     float out_amax = 0.f;
 
-    // Work items of this workgroup: its whole tiles (all K tiles), then -- if there are cut tiles and this workgroup's index is below
-    // n_cut * n_slices -- one slice: a cut tile's loop trips [s T / S, (s + 1) T / S)
-    const int n_whole = t_lo + slot_in_xcd < t_hi ? (t_hi - t_lo - slot_in_xcd + wg_per_xcd - 1) / wg_per_xcd : 0;
-    const int n_sl_all = TWO ? 0 : p.n_cut * p.n_slices;              // slices: number blockIdx.x + j * gridDim.x goes to this workgroup
-    const int n_sl = (int)blockIdx.x < n_sl_all ? (n_sl_all - 1 - (int)blockIdx.x) / nwg + 1 : 0;
-    const int n_items = n_whole + n_sl;
+    // Work items of this workgroup (work_item, persistent_tiles.h): its whole tiles, then its slices of the cut tiles; a loop trip is two K tiles
+    const int n_items = walk.n_whole + work_slices(blockIdx.x, nwg, TWO ? 0 : p.n_cut * p.n_slices);
     int tb = 0, te = nT, slice_id = 0;                                // the current item's K tiles [tb, te), both even; its slice number
     auto set_item = [&](int k) {
-        if (k < n_whole) { tb = 0; te = nT; set_tile(t_lo + slot_in_xcd + k * wg_per_xcd); }
-        else {
-            slice_id = blockIdx.x + (k - n_whole) * nwg;
-            const int l = slice_id / p.n_slices, sl = slice_id - l * p.n_slices, T = nT >> 1;
-            tb = 2 * (sl * T / p.n_slices); te = 2 * ((sl + 1) * T / p.n_slices);
-            set_tile(p.n_full + l);
-        }
+        const WorkItem it = work_item(walk, k, blockIdx.x, nwg, p.n_full, p.n_slices, nT >> 1);
+        tb = 2 * it.trip_lo; te = 2 * it.trip_hi; slice_id = it.slice;
+        set_tile(it.tile);
     };
     // the W half-tiles an item needs before its first phases: Bh0, Bh1 of its first K tile into buffer 0, Bh0 of the second into buffer 1
     auto prologue_w = [&]() { dma_w(0, tb, 0); dma_w(1, tb, 0); dma_w(0, tb + 1, 1); };
@@ -270,98 +259,16 @@ __global__ __launch_bounds__(512, 1) void gemm_pair_8ph_kernel(const PairP p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the look-ahead loads / DMA past this item's last K tile
         __builtin_amdgcn_s_barrier();                                 // every wave is done with the ring
         const int em0 = m0, en0 = n0, e_slice = slice_id;
-        const bool whole = k < n_whole;
+        const bool whole = k < walk.n_whole;
         if (k + 1 < n_items) { set_item(k + 1); prologue_w(); }       // in flight during the epilogue below
-        if (!whole) {                                                 // a slice: the raw accumulators, 16 B per thread and store
-            const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ws + (size_t)e_slice * (128 * 512)), 0, 128 * 512 * 4, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const u32x4 v = {__float_as_uint(acc[i][j][4 * q]), __float_as_uint(acc[i][j][4 * q + 1]), __float_as_uint(acc[i][j][4 * q + 2]),
-                                         __float_as_uint(acc[i][j][4 * q + 3])};
-                        __builtin_amdgcn_raw_buffer_store_b128(v, rsP, (unsigned)tid * 16u, (unsigned)(((i * 4 + j) * 4 + q) * 8192), 0);
-                    }
-            continue;
-        }
-
-        // epilogue straight from the accumulators: lane (fr, fh) holds column 32 j + fr of the wave's 128 (blocks j = 0..3), rows
-        // 32 i + (r & 3) + 8 (r >> 2) + 4 fh: one register = two 128-B row segments per wave instruction.  Rows >= M fall off
-        // the descriptors' extents; residual in units of (row block, column-block pair), the next unit's in flight behind
-        // the current one.
-        const int mw = em0 + wm0;
-        const long long rows_left = (long long)p.M - mw;
-        const __amdgpu_buffer_rsrc_t rsC = desc(p.c, rows_left > 0 ? ((rows_left - 1) * p.ldc + p.N) * 4 + (long long)mw * p.ldc * 4 : 0,
-                                                (long long)mw * p.ldc * 4);
-        const __amdgpu_buffer_rsrc_t rsR = RES ? desc(p.res, rows_left > 0 ? ((rows_left - 1) * p.ldr + p.N) * 4 + (long long)mw * p.ldr * 4 : 0,
-                                                      (long long)mw * p.ldr * 4)
-                                               : rsW0;
-        unsigned vc[4], vr[4];
-        float sv[4], bv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = en0 + wn0 + 32 * j + fr;
-            vc[j] = (unsigned)((4 * fh * p.ldc + n) * 4); vr[j] = (unsigned)((4 * fh * p.ldr + n) * 4);
-            sv[j] = (p.oscale ? p.oscale[n] : 1.f) * acc_scale;
-            bv[j] = p.bias ? p.bias[n] : 0.f;
-        }
-        float rv[RES ? 2 : 1][2][16];
-        // Rows >= M of a ragged last tile are masked BY LANE (an out-of-range voffset), not left to the descriptor's extent:
-        // their row offset travels in soffset, which can exceed num_records there, and the range check is
-        // `offset >= num_records - soffset`.  A full tile (FULL) pays nothing for it.
-        const int row_lim = (int)(rows_left < 1024 ? rows_left : 1024) - 4 * fh;     // row u of this lane is valid iff u < row_lim
-        auto epilogue = [&](auto full_tag) {
-            constexpr bool FULL = decltype(full_tag)::value;
-            auto load_res = [&](int u, int slot) {                    // unit u = (i = u >> 1, column blocks 2 (u & 1), + 1)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int ru = 32 * (u >> 1) + (r & 3) + 8 * (r >> 2);
-                        const unsigned vo = (FULL || ru < row_lim) ? vr[2 * (u & 1) + jj] : 0x80000000u;
-                        rv[slot][jj][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsR, vo, (unsigned)(ru * p.ldr * 4), 0));
-                    }
-            };
-            if constexpr (RES) load_res(0, 0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if constexpr (RES) { if (u + 1 < 4) load_res(u + 1, (u + 1) & 1); }
-                const int i = u >> 1;
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    const int j = 2 * (u & 1) + jj;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float v = (acc[i][j][r] * sv[j] + bv[j]) * p.alpha;
-                        if constexpr (RES) v += rv[u & 1][jj][r];
-                        if (ACT == DBMM_ACT_RELU) v = fmaxf(v, 0.f);
-                        else if (ACT == DBMM_ACT_QUICKGELU) v = v / (1.f + expf(-1.702f * v));
-                        const int ru = 32 * i + (r & 3) + 8 * (r >> 2);
-                        const bool valid = FULL || ru < row_lim;
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, valid ? vc[j] : 0x80000000u,
-                                                              (unsigned)(ru * p.ldc * 4), 0);
-                        if (valid) out_amax = fmaxf(out_amax, fabsf(v));
-                    }
-                }
-            }
-        };
-        if (rows_left >= 64) epilogue(std::true_type{}); else epilogue(std::false_type{});
-    }
-    if (p.c_absmax) {                                                 // one (filtered) atomic per workgroup
-        out_amax = wave_max(out_amax);
-        __syncthreads();                                              // all DMA drained (loop exit), the ring is free
-        float* red = (float*)lds;
-        if (lane == 0) red[wid] = out_amax;
-        __syncthreads();
-        if (tid == 0) {
-            float m = red[0];
-#pragma unroll
-            for (int i = 1; i < 8; ++i) m = fmaxf(m, red[i]);
-            if (m > *(volatile const float*)p.c_absmax) atomicMax((unsigned*)p.c_absmax, __float_as_uint(m));
+        if (!whole) { slice_store(acc, p.ws, e_slice, tid); continue; }
+        {
+            constexpr int EP_NI = 2, EP_NJ = 4, EP_I0 = 0, EP_J0 = 0;
+            constexpr bool EP_FULL = true;
+#include "gemm_pair_8ph_epilogue.inc"
         }
     }
+    absmax_fold(p.c_absmax, out_amax, (float*)lds, tid, lane, wid);              // (its first barrier: all DMA drained at loop exit, the ring is free)
 }
 
 }  // namespace
@@ -373,65 +280,16 @@ template <int ACT, int RES>
 __global__ __launch_bounds__(512) void gemm_pair_8ph_fixup_kernel(const PairP p) {
     __shared__ float red[8];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 1, wc = wid & 1, fr = lane & 31, fh = lane >> 5;
-    const int tile = p.n_full + blockIdx.x, m0 = (tile / p.tiles_n) * 256, n0 = (tile % p.tiles_n) * 256;
-    const int bi = blockIdx.y >> 2, bj = blockIdx.y & 3;
-    f32x16 a;
-    const f32x4* src = (const f32x4*)(p.ws + (size_t)blockIdx.x * p.n_slices * (128 * 512)) + (size_t)blockIdx.y * 4 * 512 + tid;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x4 v = src[q * 512];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a[4 * q + e] = v[e];
-    }
-    for (int sl = 1; sl < p.n_slices; ++sl) {
-        src += 32 * 512;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = src[q * 512];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a[4 * q + e] += v[e];
-        }
-    }
-    const int s_a = scale_exp(*p.a_absmax);
-    const int n = n0 + wc * 128 + 32 * bj + fr, mw = m0 + wr * 64;
-    const float sv = (p.oscale ? p.oscale[n] : 1.f) * pow2f(-s_a - p.w_exp), bv = p.bias ? p.bias[n] : 0.f;
-    const long long rows_left = (long long)p.M - mw;
-    const __amdgpu_buffer_rsrc_t rsC = desc(p.c, rows_left > 0 ? ((rows_left - 1) * p.ldc + p.N) * 4 + (long long)mw * p.ldc * 4 : 0, (long long)mw * p.ldc * 4);
-    const __amdgpu_buffer_rsrc_t rsR = RES ? desc(p.res, rows_left > 0 ? ((rows_left - 1) * p.ldr + p.N) * 4 + (long long)mw * p.ldr * 4 : 0,
-                                                  (long long)mw * p.ldr * 4)
-                                           : __builtin_amdgcn_make_buffer_rsrc((void*)p.c, 0, 0, 0x00020000);
-    const unsigned vc = (unsigned)((4 * fh * p.ldc + n) * 4), vr = (unsigned)((4 * fh * p.ldr + n) * 4);
-    const int row_lim = (int)(rows_left < 1024 ? rows_left : 1024) - 4 * fh;
-    float rv[16], out_amax = 0.f;
-    if constexpr (RES) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ru = 32 * bi + (r & 3) + 8 * (r >> 2);
-            rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsR, ru < row_lim ? vr : 0x80000000u, (unsigned)(ru * p.ldr * 4), 0));
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float v = (a[r] * sv + bv) * p.alpha;
-        if constexpr (RES) v += rv[r];
-        if (ACT == DBMM_ACT_RELU) v = fmaxf(v, 0.f);
-        else if (ACT == DBMM_ACT_QUICKGELU) v = v / (1.f + expf(-1.702f * v));
-        const int ru = 32 * bi + (r & 3) + 8 * (r >> 2);
-        const bool valid = ru < row_lim;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsC, valid ? vc : 0x80000000u, (unsigned)(ru * p.ldc * 4), 0);
-        if (valid) out_amax = fmaxf(out_amax, fabsf(v));
-    }
-    if (p.c_absmax) {
-        out_amax = wave_max(out_amax);
-        if (lane == 0) red[wid] = out_amax;
-        __syncthreads();
-        if (tid == 0) {
-            float m = red[0];
-#pragma unroll
-            for (int i = 1; i < 8; ++i) m = fmaxf(m, red[i]);
-            if (m > *(volatile const float*)p.c_absmax) atomicMax((unsigned*)p.c_absmax, __float_as_uint(m));
-        }
-    }
+    const int tile = p.n_full + blockIdx.x, em0 = (tile / p.tiles_n) * 256, en0 = (tile % p.tiles_n) * 256;
+    f32x16 acc[1][1];
+    slice_sum(acc[0], p.ws, blockIdx.x, p.n_slices, blockIdx.y, tid);
+    const float acc_scale = pow2f(-scale_exp(*p.a_absmax) - p.w_exp);
+    float out_amax = 0.f;
+    const int EP_I0 = blockIdx.y >> 2, EP_J0 = blockIdx.y & 3;
+    constexpr int EP_NI = 1, EP_NJ = 1;
+    constexpr bool EP_FULL = false;
+#include "gemm_pair_8ph_epilogue.inc"
+    absmax_fold(p.c_absmax, out_amax, red, tid, lane, wid);
 }
 
 // Tile quantisation: the persistent grid works in rounds of DBMM_N_CU tiles.  With a workspace the tiles of a short last round are cut along K into
@@ -440,15 +298,7 @@ __global__ __launch_bounds__(512) void gemm_pair_8ph_fixup_kernel(const PairP p)
 int pair_8ph_launch(PairP& p, int act, bool two, void* workspace, size_t workspace_bytes, void* stream) {
     p.tiles_n = p.N / 256;
     p.n_tiles = ((p.M + 255) / 256) * p.tiles_n;
-    p.n_full = p.n_tiles; p.n_cut = 0; p.n_slices = 1; p.ws = nullptr;
-    const int rem = p.n_tiles % DBMM_N_CU, trips = p.K / 64;
-    if (!two && workspace && dbmm_aligned16(workspace) && p.n_tiles > DBMM_N_CU && rem != 0) {
-        const int S = dbmm_cut_slices(rem, trips);
-        if (S >= 2 && (size_t)rem * S * (128 * 512 * sizeof(float)) <= workspace_bytes) {
-            p.n_full = p.n_tiles - rem; p.n_cut = rem; p.n_slices = S; p.ws = (float*)workspace;
-        }
-    }
-    const int grid = p.n_tiles < DBMM_N_CU ? p.n_tiles : DBMM_N_CU;             // persistent: one workgroup per CU
+    const int grid = plan_tiles(p, two ? 0 : dbmm_cut_slices(p.n_tiles % DBMM_N_CU, p.K / 64), workspace, workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
 #define DBMM_P8(A, R, T) hipLaunchKernelGGL((gemm_pair_8ph_kernel<A, R, T>), dim3(grid), dim3(512), 0, s, p)
     if (two) { if (act == 0) DBMM_P8(0, 0, 1); else if (act == 1) DBMM_P8(1, 0, 1); else return DBMM_E_UNSUPPORTED; }

@@ -12,9 +12,10 @@
 // index, not by value.
 //
 // Structure.  pairdist_split_kernel writes the planes as ONE fp16 matrix P [N][2 Dp] (row = hi | lo, Dp = D rounded up to 128,
-// zero padded) plus {norm, group} per row.  The tile product is the deep-pipelined structure of gemm_f16_8ph_kernel (f16_ops.hip:
-// 256 x 256 x 64 tiles, LDS-DMA half-tiles staged five phases ahead, two wave rows one barrier apart, persistent workgroups, the
-// next tile's prologue in flight during the epilogue) run over a K of 3 Dp: K tile t reads A from plane columns (t < T ? t : t - T)
+// zero padded) plus {norm, group} per row.  The tile product runs on the shared fp16 ring (fp16_ring.inc, the one gemm_f16_8ph_kernel
+// uses: 256 x 256 x 64 tiles, LDS-DMA half-tiles staged five phases ahead, two wave rows one barrier apart) under persistent workgroups
+// (tile_walk, persistent_tiles.h; the next tile's prologue in flight during the epilogue).  What is this kernel's own is the source map
+// (ring_src), the range check of the B rows and the epilogue.  K is 3 Dp: K tile t reads A from plane columns (t < T ? t : t - T)
 // and B from (t < 2 T ? t : t - 2 T), T = Dp / 64, i.e. the segments hi.hi, hi.lo, lo.hi.  Both operands are row blocks of P.
 //
 // Determinism.  No floating-point atomics: a lane sums its 128 distances in float64, a wave folds them by butterfly, eight wave
@@ -23,11 +24,10 @@
 // nearly every tile single-bucket (the fast path: no predicates); mixed, ragged and diagonal tiles take the predicated path.
 // Workspace: the planes (4 Dp bytes per row), 8 bytes per row, 512 bytes per workgroup -- O(N D), never O(N^2).
 #include <stdlib.h>
-#include "common.h"
+#include "persistent_tiles.h"
 
 namespace {
 
-constexpr int PH_HALF = 128 * 64 * 2;                              // bytes of a half-tile
 constexpr int MAX_WG = DBMM_N_CU;                                  // persistent grid: one workgroup per CU
 constexpr int NO_GROUP = 15;                                       // rows past N / labels outside [0, G): in no bucket
 constexpr size_t HEAD_BYTES = 256;                                 // workspace head: the centred absmax (uint bits)
@@ -105,17 +105,11 @@ __global__ __launch_bounds__(512, 1) void pairdist_tile_kernel(const PairDistP p
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 2, wc = wid & 3;
     const int fr = lane & 31, fh = lane >> 5;
-    // this workgroup's tiles: the XCD's contiguous range (xcd_remap's split), walked with the stride of the XCD's workgroups
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot_in_xcd = blockIdx.x >> 3, wg_per_xcd = (nwg - xcd + 7) >> 3;
-    const int tq = p.n_tiles >> 3, trm = p.n_tiles & 7;
-    const int t_lo = xcd < trm ? xcd * (tq + 1) : trm * (tq + 1) + (xcd - trm) * tq, t_hi = t_lo + tq + (xcd < trm ? 1 : 0);
+    const TileWalk walk = tile_walk(blockIdx.x, gridDim.x, p.n_tiles);
     const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.P, 0, 0, 0x00020000);
     __amdgpu_buffer_rsrc_t rsA = rs0, rsW = rs0;
     int m0 = 0, n0 = 0;
-    // stager: thread -> LDS chunk (tid + 512 i) of a half-tile = local row (tid >> 3) + 64 i, slot tid & 7; it fetches
-    // source chunk slot ^ swz(row).  Half-tile kind k = 0..3 (Ah0, Bh0, Bh1, Ah1) -> operand rows:
-    //   A half h: tile row (lr >> 6) * 128 + h * 64 + (lr & 63);   B half h: tile column (lr >> 5) * 64 + 2 * (lr & 31) + h
-    unsigned voff[4][2];
+    unsigned voff[4][2];                                           // the stager's lane offsets per half-tile kind (Ah0, Bh0, Bh1, Ah1); rows >= N masked
     // tile number -> (row block bi <= column block bj) of the upper triangle, row-major: row bi starts at bi * nb - bi (bi - 1) / 2
     auto set_tile = [&](int tile) {
         const double w = 2.0 * p.nb + 1.0;
@@ -130,116 +124,36 @@ __global__ __launch_bounds__(512, 1) void pairdist_tile_kernel(const PairDistP p
         rsW = desc(p.P, p.p_total, (long long)n0 * p.ldp * 2);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int lr = (tid >> 3) + 64 * i, c = (tid & 7) ^ ((lr >> 1) & 7);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const int ra = (lr >> 6) * 128 + h * 64 + (lr & 63), rw = (lr >> 5) * 64 + 2 * (lr & 31) + h;
-                voff[h ? 3 : 0][i] = m0 + ra < p.N ? (unsigned)ra * (unsigned)(p.ldp * 2) + c * 16u : OOR;
-                voff[h ? 2 : 1][i] = n0 + rw < p.N ? (unsigned)rw * (unsigned)(p.ldp * 2) + c * 16u : OOR;
+                int ra, rw;
+                unsigned cb;
+                ring_rows(tid, i, h, ra, rw, cb);
+                voff[h ? 3 : 0][i] = m0 + ra < p.N ? (unsigned)ra * (unsigned)(p.ldp * 2) + cb : OOR;
+                voff[h ? 2 : 1][i] = n0 + rw < p.N ? (unsigned)rw * (unsigned)(p.ldp * 2) + cb : OOR;
             }
         }
     };
     const int nT = 3 * p.T;                                          // K tiles of the three products: hi.hi, hi.lo, lo.hi
-    // stage number q: kind q & 3 of K tile q >> 2 into buffer (q >> 2) & 1; tiles past the end go through the zero-extent
-    // descriptor so that every phase issues exactly two DMA instructions per wave (the vmcnt arithmetic relies on it)
-    auto stage = [&](int kind, int buf, int t) {
+    // K tile t of half-tile kind `kind`: its K tile inside P's row (hi | lo); tiles past the end go through the zero-extent descriptor
+    auto ring_src = [&](int kind, int t, __amdgpu_buffer_rsrc_t& rs, unsigned (&vo)[2], unsigned& so) {
         const bool isA = kind == 0 || kind == 3, valid = t < nT;
-        unsigned char* slot = lds + (buf * 4 + kind) * PH_HALF + wid * 1024;
-        const __amdgpu_buffer_rsrc_t rs = valid ? (isA ? rsA : rsW) : rs0;
-        const int kt = isA ? (t < p.T ? t : t - p.T) : (t < 2 * p.T ? t : t - 2 * p.T);     // the K tile inside P's row (hi | lo)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) glds16(rs, slot + i * 8192, voff[kind][i], (unsigned)kt * 128u);
+        rs = valid ? (isA ? rsA : rsW) : rs0;
+        const int kt = isA ? (t < p.T ? t : t - p.T) : (t < 2 * p.T ? t : t - 2 * p.T);
+        vo[0] = voff[kind][0]; vo[1] = voff[kind][1];
+        so = (unsigned)kt * 128u;
     };
-    // fragment addresses inside a half-tile (bytes): A rows wr * 64 + blk * 32 + fr, B rows wc * 32 + fr, chunk (2 ks + fh) ^ swz
-    int aoff[2][4], boff[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int r = wr * 64 + b * 32 + fr;
-            aoff[b][ks] = r * 128 + (((2 * ks + fh) ^ ((r >> 1) & 7)) << 4);
-        }
-        const int r = wc * 32 + fr;
-        boff[ks] = r * 128 + (((2 * ks + fh) ^ ((r >> 1) & 7)) << 4);
-    }
-    f32x16 acc[4][2];
-    u32x4 fa[2][4], fb0[4], fb1[4];
+#include "fp16_ring.inc"
 
-    // one phase: j = phase within the loop trip (static), t2 = first K tile of the trip.  `first`: the tile's first trip; its
-    // prologue has staged both K tiles of the trip (stages 0 .. 7), so phases 0 - 2 stage nothing and phases 0 - 4 wait for nothing.
-    auto phase = [&](int j, int t2, bool first) {
-        const int ph = j & 3, buf = (j >> 2) & 1;
-        const unsigned char* base = lds + buf * 4 * PH_HALF;
-        if (ph == 0) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) fb0[ks] = *(const u32x4*)(base + 1 * PH_HALF + boff[ks]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) fa[b][ks] = *(const u32x4*)(base + 0 * PH_HALF + aoff[b][ks]);
-        } else if (ph == 1) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) fb1[ks] = *(const u32x4*)(base + 2 * PH_HALF + boff[ks]);
-        } else if (ph == 2) {
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) fa[b][ks] = *(const u32x4*)(base + 3 * PH_HALF + aoff[b][ks]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(first && j < 3)) {
-            const int q = j + 5;                                      // stage number relative to the trip's first tile
-            stage(q & 3, (q >> 2) & 1, t2 + (q >> 2));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(first && j < 5)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-        const int ai = (ph >= 2) ? 2 : 0, bj = (ph == 1 || ph == 2) ? 1 : 0;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-                acc[ai + b][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[b][ks]),
-                                                                         __builtin_bit_cast(f16x8, bj ? fb1[ks] : fb0[ks]), acc[ai + b][bj], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-    };
-
-    const int n_items = t_lo + slot_in_xcd < t_hi ? (t_hi - t_lo - slot_in_xcd + wg_per_xcd - 1) / wg_per_xcd : 0;
-    auto prologue = [&]() {                                           // stages 0 .. 7 = a tile's first two K tiles, both buffers
-#pragma unroll
-        for (int q = 0; q < 8; ++q) stage(q & 3, (q >> 2) & 1, q >> 2);
-    };
+    const int n_items = walk.n_whole;
     const int wm0 = wr * 128, wn0 = wc * 64;
     double total = 0.0;                                               // thread b < 64: this workgroup's sum of bucket b
     if (tid < 2) e_mask[tid] = 0u;
-    if (n_items > 0) { set_tile(t_lo + slot_in_xcd); prologue(); }
+    if (n_items > 0) { set_tile(walk.first); ring_prologue(0); }
     for (int k = 0; k < n_items; ++k) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the prologue's 16 DMA instructions have landed
-        __builtin_amdgcn_s_barrier();
-        if (wr == 1) __builtin_amdgcn_s_barrier();                    // the second wave row runs one barrier behind
-#pragma unroll
-        for (int j = 0; j < 8; ++j) phase(j, 0, true);
-        for (int t2 = 2; t2 < nT; t2 += 2) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) phase(j, t2, false);
-        }
-        if (wr == 0) __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the look-ahead DMA past the last K tile
-        __builtin_amdgcn_s_barrier();                                 // every wave is done with the ring
+        ring_item(0, nT, true, [](int) {});                           // (no epilogue stores: every item waits for all of its prologue)
         const int em0 = m0, en0 = n0;
-        if (k + 1 < n_items) { set_tile(t_lo + slot_in_xcd + (k + 1) * wg_per_xcd); prologue(); }   // in flight during the epilogue
+        if (k + 1 < n_items) { set_tile(walk.first + (k + 1) * walk.stride); ring_prologue(0); }   // in flight during the epilogue
 
         // ---- epilogue: distances and bucket sums straight from the accumulators -------------------------------------------
         // lane (fr, fh) holds columns wn0 + 2 fr + j (blocks j = 0 / 1: the B halves are the even / odd columns) of rows

@@ -48,3 +48,20 @@ def test_constant_defined_once_in_common_h(name):
 @pytest.mark.parametrize("name", FUNCTIONS + CONSTANTS + ("pow2", "split_pair", "f16x8", "u32x4"))
 def test_no_stem_prefixed_twin(name):
     assert _where(r"\bstem_%s\b" % name) == []
+
+
+# What the persistent 256-tile kernels share (csrc/persistent_tiles.h, csrc/fp16_ring.inc): a kernel file that carries
+# its own copy of the XCD split, the slice store, the slice sum or the fp16 ring's phase again fails here.
+@pytest.mark.parametrize("statement,where", [
+    ("const int tq = ", "common.h"),                                  # the split of tile ids over the XCDs (xcd_first)
+    ("raw_buffer_store_b128(v, rsP", "persistent_tiles.h"),           # slice_store
+    ("src += 32 * 512", "persistent_tiles.h"),                        # slice_sum
+    ("fb1[ks] = *(const u32x4*)(base + 2 * PH_HALF + boff[ks])", "fp16_ring.inc"),   # the fp16 ring's phase
+])
+def test_persistent_tile_statement_stated_once(statement, where):
+    assert _where(re.escape(statement)) == [(where, 1)]
+
+
+@pytest.mark.parametrize("name", ("tile_walk", "work_item", "work_slices", "slice_store", "slice_sum", "absmax_fold", "ring_rows"))
+def test_persistent_tile_helper_defined_once(name):
+    assert _where(r"__device__\s[^;(){}]*?\b%s\s*\([^;{}]*\)\s*\{" % name) == [("persistent_tiles.h", 1)]
