@@ -8,7 +8,7 @@ import ctypes
 import glob
 import os
 import subprocess
-from ctypes import c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -46,6 +46,7 @@ KERNEL_SOURCES = (
     ("pairdist_", ("pairdist.hip", "fp16_ring.inc", "persistent_tiles.h", "common.h")),
     ("covariance_", ("covariance.hip", "common.h")),
     ("project_rows_", ("covariance.hip", "common.h")),
+    ("sym_eig_", ("sym_eig.hip", "common.h")),
     ("supcon_", ("supcon.hip", "common.h")),
     ("sets_", ("supcon_sets.hip", "common.h")),
 )
@@ -214,6 +215,9 @@ _SIGS = {
     "dbmm_workspace_bytes_covariance": [_L, _L],
     "dbmm_covariance": [_P, _P, _P, _L, _L, _P, _Z, _P],
     "dbmm_project_rows": [_P, _P, _P, _P, _L, _L, _L, _P],
+    "dbmm_workspace_bytes_sym_eig": [_L],
+    "dbmm_sym_eig_begin": [_P, _L, _L, c_double, _P, _Z, _P],
+    "dbmm_sym_eig_iterate": [_P, _L, _L, _P, _Z, _P],
 }
 _RESTYPES = {
     "dbmm_error_string": ctypes.c_char_p,
@@ -233,6 +237,7 @@ _RESTYPES = {
     "dbmm_workspace_bytes_linear_sweep_eval": c_size_t,
     "dbmm_workspace_bytes_pairdist": c_size_t,
     "dbmm_workspace_bytes_covariance": c_size_t,
+    "dbmm_workspace_bytes_sym_eig": c_size_t,
     "dbmm_supcon_workspace_bytes": c_size_t,
     "dbmm_supcon_sets_workspace_bytes": c_size_t,
     "dbmm_workspace_bytes_adapter_train_step_sets": c_size_t,

@@ -188,11 +188,17 @@ def pca_from_scatter(scatter, center, mean, n, k):
     d = np.asarray(mean, dtype=np.float64) - np.asarray(center).astype(np.float64)
     C = scatter - np.float64(n) * np.outer(d, d)
     w, V = np.linalg.eigh(C)                                        # ascending
-    w, V = w[::-1][:k], V[:, ::-1][:, :k].T
+    return _components_and_variances(w[::-1][:k], V[:, ::-1][:, :k].T, np.trace(C), n)
+
+
+def _components_and_variances(w, V, trace, n):
+    """The rules every eigen-solver's answer goes through, numpy only.  w float64 [k] descending eigenvalues of the scatter matrix
+    about the mean, V float64 [k, D] their unit vectors as rows, trace of that matrix, n rows.  Returns pca_from_scatter's tuple:
+    float32 components, each signed so that its entry of largest magnitude is positive; eigenvalue / (n - 1); ratio; total variance."""
+    k = len(w)
     comp = np.ascontiguousarray(V, dtype=np.float32)
     top = np.abs(comp).argmax(axis=1)
     comp *= np.where(comp[np.arange(k), top] < 0, np.float32(-1), np.float32(1))[:, None]
-    trace = np.trace(C)
     ratio = w / trace if trace > 0 else np.zeros(k)
     return comp, w / (n - 1.0), ratio, trace / (n - 1.0)
 
@@ -210,7 +216,24 @@ def _group_means(x, dense, counts, center):
     return means
 
 
-def pca(embeddings, groups=None, k=2):
+SOLVERS = ("host", "device")
+
+
+def _device_eigen_step(scatter, center, mean, n, k, tol, max_iter):
+    """`pca`'s eigen step without the D x D copy to the host.  scatter: ops.covariance's device tensor about float32 `center`.  The
+    n (mean - center)(mean - center)^T correction and the trace are float64 torch ops on the device (torch.outer(d, d) is symmetric
+    to the bit, so the corrected matrix is too), ops.sym_eig_topk solves, and only the [k, D] vectors and k values come back.
+    Returns (pca_from_scatter's tuple or None when the solver did not converge, info)."""
+    d = torch.from_numpy(np.asarray(mean, dtype=np.float64) - np.asarray(center).astype(np.float64)).to(scatter.device)
+    C = scatter - float(n) * torch.outer(d, d)
+    values, vectors, info = ops.sym_eig_topk(C, k, tol=tol, max_iter=max_iter)
+    if not info["converged"]:
+        return None, info
+    trace = torch.trace(C).item()
+    return _components_and_variances(values.cpu().numpy(), vectors.cpu().numpy(), np.float64(trace), n), info
+
+
+def pca(embeddings, groups=None, k=2, solver="host", tol=1e-10, max_iter=256):
     """Principal components of a split and its rows' coordinates in them: the deterministic map of the reference's
     representation report (plot_umap draws UMAP or MDS; PCA is classical MDS of the distances of group_stats).
 
@@ -224,7 +247,19 @@ def pca(embeddings, groups=None, k=2):
     difference between that vector and the float64 mean is removed on the host, numpy.linalg.eigh solves the D x D float64
     problem there, and ops.project_rows reads the rows once more for the coordinates.  The group means behind the centroids are
     sums of gathered rows minus that centre, so they too lose precision relative to the rows' spread, wherever the split lies.
-    k outside 1..8 and fewer than two rows raise ValueError before anything is launched."""
+    k outside 1..8 and fewer than two rows raise ValueError before anything is launched.
+
+    `solver`: "host" (the default) is the path above.  "device" keeps the scatter matrix on the device and finds the top k
+    eigenpairs there (ops.sym_eig_topk: blocked subspace iteration on 16 vectors, stopped at a residual of `tol` theta_1 or after
+    `max_iter` iterations); only k vectors and values come to the host, where the same rules apply (order, float32, sign,
+    / (n - 1), ratio).  The fit then has one more key, 'eig': the solver's info (iterations, converged, state, residual) and
+    'used', "device" or "host".  Known limit: the iteration converges by lambda_17 / lambda_k per step; when the k-th eigenvalue
+    sits in a flat noise bulk (isotropic noise plus fewer than k directions) it does not get there in max_iter iterations.
+    Then, and after a breakdown (a zero or rank-deficient matrix), `pca` silently solves the same scatter matrix on the host, so
+    the answer is as good as the default's; the attempt is wasted time.  Any other solver name raises ValueError before anything
+    is launched."""
+    if solver not in SOLVERS:
+        raise ValueError(f"pca: solver = {solver!r}; one of {SOLVERS}")
     x, g_np = _rows_and_groups(embeddings, groups)
     x = x.float().contiguous()
     n = x.shape[0]
@@ -235,9 +270,17 @@ def pca(embeddings, groups=None, k=2):
     mean = _column_sums(x) / n
     center = mean.astype(np.float32)
     c_dev = torch.from_numpy(center).to(x.device)
-    scatter = ops.covariance(x, c_dev).cpu().numpy()
-    comp, var, ratio, total = pca_from_scatter(scatter, center, mean, n, k)
+    scatter = ops.covariance(x, c_dev)
+    solved, eig = None, None
+    if solver == "device":
+        solved, eig = _device_eigen_step(scatter, center, mean, n, k, tol, max_iter)
+        eig = dict(eig, used="device" if solved is not None else "host")
+    if solved is None:
+        solved = pca_from_scatter(scatter.cpu().numpy(), center, mean, n, k)
+    comp, var, ratio, total = solved
     fit = {"mean": center, "components": comp, "explained_variance": var, "explained_variance_ratio": ratio, "total_variance": total}
+    if eig is not None:
+        fit["eig"] = eig
     fit["coords"] = ops.project_rows(x, c_dev, torch.from_numpy(comp).to(x.device))
     uniq, dense, counts = np.unique(g_np, return_inverse=True, return_counts=True)
     cent = _group_means(x, dense, counts, c_dev) @ comp.astype(np.float64).T
@@ -266,11 +309,12 @@ def sample_rows(n, num_data, seed=42, offset=0):
     return np.arange(n)[offset:offset + num_data]
 
 
-def projection_report(opt, train_table, val_table, test_table, transform=None, k=2, num_data=None, seed=42):
+def projection_report(opt, train_table, val_table, test_table, transform=None, k=2, num_data=None, seed=42, solver="host", tol=1e-10,
+                      max_iter=256):
     """VisRepAll's map without matplotlib: a PCA fitted on train's rows (`sample_rows(len(train), num_data, seed)` of them; after
     `transform`, a callable emb -> emb such as classifier.adapter, applied batch by batch in eval mode) and all three splits in that
     one frame.  Returns ({'train': s, 'val': s, 'test': s}, fit) with s = {'coords' numpy [n, k], 'rows' (indices into the table),
-    'groups', 'targets', 'spurious'} and fit = `pca`'s dict of the train rows."""
+    'groups', 'targets', 'spurious'} and fit = `pca`'s dict of the train rows.  `solver`, `tol`, `max_iter`: `pca`'s."""
     bs = max(int(getattr(opt, "batch_size", 0) or 0), 4096)
     out, fit = {}, None
     for split, table in (("train", train_table), ("val", val_table), ("test", test_table)):
@@ -280,7 +324,7 @@ def projection_report(opt, train_table, val_table, test_table, transform=None, k
             emb = ops.gather_rows(emb, torch.from_numpy(rows.astype(np.int64)).to(emb.device))
         groups = table.group_array[rows]
         if fit is None:
-            fit = pca(emb, groups, k)
+            fit = pca(emb, groups, k, solver=solver, tol=tol, max_iter=max_iter)
             coords = fit["coords"]
         else:
             coords = pca_project(fit, emb)

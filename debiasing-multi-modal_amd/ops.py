@@ -6,6 +6,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1390,6 +1391,58 @@ def project_rows(x, center, basis):
         raise DbmmUnsupported(f"project_rows: no kernel for N = {N}, D = {D}")
     check(rc, "project_rows")
     return out
+
+
+SYM_EIG_BLOCK = 16                  # vectors of the subspace iteration's block (csrc/sym_eig.hip)
+SYM_EIG_STATES = ("running", "converged", "breakdown")
+_SYM_EIG_STATUS = 64                # doubles of the status block at the head of the workspace (include/dbmm.h)
+
+
+def sym_eig_topk(C, k, tol=1e-10, max_iter=256, check_every=8):
+    """The top k eigenpairs of a symmetric positive semi-definite float64 matrix C [D, D] (D % 64 == 0, D <= 4096; symmetric to
+    the bit, as `covariance` returns it) on the device: blocked subspace iteration on 16 vectors with a Rayleigh-Ritz step per
+    iteration (dbmm_sym_eig_begin / dbmm_sym_eig_iterate).  Returns (values float64 [k] descending, vectors float64 [k, D] of unit
+    norm, info): device tensors, views of the call's workspace, and info = {'iterations', 'converged', 'state' ('running' |
+    'converged' | 'breakdown'), 'residual': max_j ||C v_j - theta_j v_j|| / theta_1 as the device reports it}.
+
+    The start block is np.random.RandomState(0x5EED).standard_normal((D, 16)) (a private stream), so two calls give the same bits.
+    The loop enqueues min(check_every, remaining) iterations, reads the status block (one small copy to the host) and stops on
+    'converged', 'breakdown' or max_iter; iterations enqueued after convergence are no-ops on the device, so the result does not
+    depend on check_every.  Non-convergence is reported, never raised: the iteration converges by lambda_17 / lambda_k per step and
+    does not get there when the k-th eigenvalue sits in a flat bulk."""
+    require_cuda(C)
+    if C.dtype != torch.float64 or not C.is_contiguous() or C.dim() != 2 or C.shape[0] != C.shape[1]:
+        raise _lib.DbmmError(f"sym_eig_topk: C must be a contiguous float64 [D, D] tensor, got {C.dtype} {tuple(C.shape)}")
+    D = C.shape[0]
+    k, max_iter, check_every = int(k), int(max_iter), int(check_every)
+    if not 1 <= k <= 8:
+        raise _lib.DbmmError(f"sym_eig_topk: k = {k} outside 1..8")
+    if max_iter < 1 or check_every < 1:
+        raise _lib.DbmmError(f"sym_eig_topk: max_iter = {max_iter}, check_every = {check_every}; both at least 1")
+    if not (tol > 0 and math.isfinite(tol)):
+        raise _lib.DbmmError(f"sym_eig_topk: tol = {tol} is not a positive finite number")
+    if D % 64 or D > 4096 or D == 0:
+        raise DbmmUnsupported(f"sym_eig_topk: D = {D}; the kernels serve D % 64 == 0, D <= 4096")
+    L = _lib.lib()
+    nbytes = L.dbmm_workspace_bytes_sym_eig(D)
+    ws = _empty(nbytes // 8, device=C.device, dtype=torch.float64)
+    q0 = _empty((D, SYM_EIG_BLOCK), device=C.device, dtype=torch.float64)
+    q0.copy_(torch.from_numpy(np.random.RandomState(0x5EED).standard_normal((D, SYM_EIG_BLOCK))))
+    check(L.dbmm_sym_eig_begin(q0.data_ptr(), D, k, float(tol), ws.data_ptr(), nbytes, stream()), "sym_eig_begin")
+    done = 0
+    while True:
+        n = min(check_every, max_iter - done)
+        check(L.dbmm_sym_eig_iterate(C.data_ptr(), D, n, ws.data_ptr(), nbytes, stream()), "sym_eig_iterate")
+        done += n
+        status = ws[:_SYM_EIG_STATUS].cpu().numpy()
+        state = int(status[1])
+        if state != 0 or done >= max_iter:
+            break
+    theta1 = status[2]
+    info = {"iterations": int(status[0]), "converged": state == 1, "state": SYM_EIG_STATES[state],
+            "residual": float(status[18:18 + k].max() / theta1) if theta1 > 0 else float("inf")}
+    vectors = ws[_SYM_EIG_STATUS:_SYM_EIG_STATUS + SYM_EIG_BLOCK * D].view(SYM_EIG_BLOCK, D)[:k]
+    return ws[2:2 + k], vectors, info
 
 
 # ---- fp16 mode of the transformer towers (csrc/f16_ops.hip) -------------------------------------------------------

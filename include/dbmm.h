@@ -794,6 +794,36 @@ int dbmm_covariance(const float* x, const float* center, double* scatter, int64_
 int dbmm_project_rows(const float* x, const float* center, const float* basis, float* y, int64_t N, int64_t D, int64_t K,
                       void* stream);
 
+/* The top k eigenpairs of a symmetric positive semi-definite matrix C double [D][D] (symmetric to the bit, as dbmm_covariance writes
+ * it) WITHOUT leaving the device: blocked subspace iteration on 16 vectors (k <= 8 plus oversampling) with a Rayleigh-Ritz step in
+ * every iteration, all in float64.  One iteration, Q [D][16] orthonormal: Z = C Q; T = Q^T Z (symmetrised), G = Z^T Z; T = W theta W^T
+ * by cyclic Jacobi in one workgroup (theta descending); Ritz vectors X = Q W, Y = Z W; residuals r_j = ||Y_j - theta_j X_j||_2 from
+ * the vectors; converged when max_{j < k} r_j <= tol theta_1; else Q <- Y L^-T with L L^T = W^T G W.  The convergence factor per
+ * iteration is lambda_17 / lambda_k: a k-th eigenvalue inside a flat bulk does not converge in any useful number of iterations.
+ *   dbmm_sym_eig_begin    orthonormalises the start block q0 double [D][16] (Cholesky QR) into the workspace and resets the status.
+ *                         One launch.
+ *   dbmm_sym_eig_iterate  enqueues exactly n_iter iterations, three launches each (matvec and 16 x 16 partials per 16 rows; merge,
+ *                         Jacobi, Cholesky in one workgroup; rotate per 16 rows), and one small launch that tests the last one's
+ *                         residuals.  Every kernel reads the state first and does nothing unless it is `running`: iterations enqueued
+ *                         after convergence are no-ops, and the result and the iteration count do not depend on how n_iter is cut
+ *                         into calls.  Plain launches on `stream`; no memset, no floating-point atomics, partial sums in a fixed
+ *                         order: two runs give the same bits.
+ * Workspace, in doubles (Python reads views of it):
+ *   [0]       iterations done
+ *   [1]       state: 0 running, 1 converged, 2 breakdown (theta_1 not positive or not finite, Jacobi not converged after its cap of
+ *             sweeps, a residual that is not finite, or -- after that iteration's residual test -- a Cholesky pivot that is not
+ *             positive, not finite or below 2^-40 of the largest: a zero matrix, rank below 16)
+ *   [2..17]   theta[16], descending, of the last completed Rayleigh-Ritz step
+ *   [18..33]  r[16], the residual norms of the last tested iteration
+ *   [34..63]  k, tol and internal words
+ *   [64 ..]   the Ritz vectors VECTOR-MAJOR [16][D] (unit norm; the first k rows are the result), then Q, Z and the partials.
+ * D % 64 != 0 or D > 4096: DBMM_E_UNSUPPORTED; k outside 1..8, n_iter < 0, tol not a positive finite number: DBMM_E_SHAPE; null
+ * pointers, a short workspace and pointers that are not 16-byte aligned as dbmm_covariance answers them; every check precedes the
+ * first launch.  dbmm_workspace_bytes_sym_eig: (64 + 81 D + 512) doubles, 0 for a D that is not served. */
+size_t dbmm_workspace_bytes_sym_eig(int64_t D);
+int dbmm_sym_eig_begin(const double* q0, int64_t D, int64_t k, double tol, void* workspace, size_t workspace_bytes, void* stream);
+int dbmm_sym_eig_iterate(const double* C, int64_t D, int64_t n_iter, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
