@@ -49,6 +49,7 @@ KERNEL_SOURCES = (
     ("sym_eig_", ("sym_eig.hip", "common.h")),
     ("supcon_", ("supcon.hip", "common.h")),
     ("sets_", ("supcon_sets.hip", "common.h")),
+    ("kmeans_", ("kmeans.hip", "common.h")),
 )
 
 
@@ -218,6 +219,10 @@ _SIGS = {
     "dbmm_workspace_bytes_sym_eig": [_L],
     "dbmm_sym_eig_begin": [_P, _L, _L, c_double, _P, _Z, _P],
     "dbmm_sym_eig_iterate": [_P, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_kmeans": [_L, _L, _L],
+    "dbmm_kmeans_begin": [_P, _L, _L, _L, _P, _Z, _P],
+    "dbmm_kmeans_iterate": [_P, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_kmeans_assign": [_P, _P, _P, _P, _L, _L, _L, _P],
 }
 _RESTYPES = {
     "dbmm_error_string": ctypes.c_char_p,
@@ -238,6 +243,7 @@ _RESTYPES = {
     "dbmm_workspace_bytes_pairdist": c_size_t,
     "dbmm_workspace_bytes_covariance": c_size_t,
     "dbmm_workspace_bytes_sym_eig": c_size_t,
+    "dbmm_workspace_bytes_kmeans": c_size_t,
     "dbmm_supcon_workspace_bytes": c_size_t,
     "dbmm_supcon_sets_workspace_bytes": c_size_t,
     "dbmm_workspace_bytes_adapter_train_step_sets": c_size_t,

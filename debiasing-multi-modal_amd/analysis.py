@@ -131,16 +131,20 @@ def representation_table(stats, zs_group_acc):
 
 
 @torch.no_grad()
-def _transformed(table, transform, batch_size):
+def _transformed_rows(x, transform, batch_size):
     was_training = getattr(transform, "training", False)
     if hasattr(transform, "eval"):
         transform.eval()
-    out = torch.empty_like(table.embeddings)
-    for i in range(0, len(table), batch_size):
-        out[i:i + batch_size] = transform(table.embeddings[i:i + batch_size])
+    out = torch.empty_like(x)
+    for i in range(0, x.shape[0], batch_size):
+        out[i:i + batch_size] = transform(x[i:i + batch_size])
     if was_training:
         transform.train()
     return out
+
+
+def _transformed(table, transform, batch_size):
+    return _transformed_rows(table.embeddings, transform, batch_size)
 
 
 def representation_report(opt, train_table, val_table, test_table, classifier=None, transform=None):
@@ -331,3 +335,127 @@ def projection_report(opt, train_table, val_table, test_table, transform=None, k
         out[split] = {"coords": coords.cpu().numpy(), "rows": rows, "groups": groups,
                       "targets": table.targets.cpu().numpy()[rows], "spurious": table.targets_spurious.cpu().numpy()[rows]}
     return out, fit
+
+
+# ---- k-means pseudo-groups: the label-free route to group DRO (Sohoni et al. 2020, "GEORGE") ------------------------------------
+# Cluster the embeddings of each class, train on the clusters as groups; and the report's open question in one number: does a
+# representation, before or after the adapter, separate the spurious attribute at all (cluster_agreement)?
+
+TRANSFORM_ROWS = 4096     # rows per batch of `transform`
+
+
+def kmeans_pp_rows(x, k, rng):
+    """k-means++ (Arthur & Vassilvitskii 2007): the indices (numpy int64 [k]) of k rows of the device tensor x as start centres,
+    drawn from `rng` (a numpy RandomState).  The first uniformly; each further one by D^2 sampling from dmin of ops.kmeans_assign
+    against the rows chosen so far: one N-float copy to the host, a float64 cumulative sum and searchsorted.  A chosen row has
+    dmin == 0 exactly and is never drawn again; when every row coincides with a chosen one the draw is uniform."""
+    n = x.shape[0]
+    rows = [int(rng.randint(n))]
+    while len(rows) < k:
+        centers = ops.gather_rows(x, torch.tensor(rows, dtype=torch.int64, device=x.device))
+        cum = np.cumsum(ops.kmeans_assign(x, centers)[1].cpu().numpy().astype(np.float64))
+        if not cum[-1] > 0:
+            rows.append(int(rng.randint(n)))
+            continue
+        rows.append(min(int(np.searchsorted(cum, rng.random_sample() * cum[-1], side="right")), n - 1))
+    return np.asarray(rows, dtype=np.int64)
+
+
+def size_order(counts):
+    """the renumbering rule of `kmeans`: the clusters' old indices by size, descending; the lower old index first on a tie"""
+    return np.argsort(-np.asarray(counts, dtype=np.int64), kind="stable")
+
+
+def kmeans(embeddings, k, init="k-means++", seed=0, n_init=1, max_iter=100, transform=None):
+    """Lloyd's k-means of a split's rows into k <= 16 clusters on the device (ops.kmeans_fit: two reads of the rows per iteration,
+    fixed-order float64 sums, the same bits on every call).
+
+    `embeddings`: an EmbeddingTable or a device tensor [N, D].  `transform` (a callable emb -> emb, e.g. the stage-1 adapter) is
+    applied batch by batch in eval mode first, as in representation_report.  `init`: "k-means++" -- `kmeans_pp_rows` drawn from a
+    private np.random.RandomState(seed), the global stream is left alone -- or an fp32 [k, D] array of start centres.  With
+    n_init > 1 (k-means++ only) the restarts continue the same stream and the fit of lowest inertia wins, the lowest restart index
+    on a tie.  Returns {'labels' device int64 [N], 'centers' numpy fp32 [k, D], 'inertia' float, 'counts' numpy int64 [k],
+    'iterations', 'converged'}; the clusters are renumbered by size, descending (size_order), so cluster 0 is the majority.  A fit
+    that reaches max_iter reports converged False; nothing is raised."""
+    x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+    k, n_init = int(k), int(n_init)
+    if not 1 <= k <= ops.KMEANS_MAX_K:
+        raise ValueError(f"kmeans: k = {k} (1..{ops.KMEANS_MAX_K})")
+    if x.shape[0] < k:
+        raise ValueError(f"kmeans: {x.shape[0]} rows for {k} clusters")
+    x = x.float().contiguous()
+    if transform is not None:
+        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
+    best = None
+    if isinstance(init, str):
+        if init != "k-means++" or n_init < 1:
+            raise ValueError(f"kmeans: init = {init!r}, n_init = {n_init}; 'k-means++' with n_init >= 1, or an array of start centres")
+        rng = np.random.RandomState(seed)
+        for _ in range(n_init):
+            start = ops.gather_rows(x, torch.from_numpy(kmeans_pp_rows(x, k, rng)).to(x.device))
+            fit = ops.kmeans_fit(x, start, max_iter=max_iter)
+            if best is None or fit[2]["inertia"] < best[2]["inertia"]:
+                best = fit
+    else:
+        start = np.ascontiguousarray(init, dtype=np.float32)
+        if start.shape != (k, x.shape[1]):
+            raise ValueError(f"kmeans: init has shape {start.shape}, not {(k, x.shape[1])}")
+        best = ops.kmeans_fit(x, torch.from_numpy(start).to(x.device), max_iter=max_iter)
+    centers, labels, info = best
+    order = size_order(info["counts"])
+    rank = np.empty(k, dtype=np.int64)
+    rank[order] = np.arange(k)
+    return {"labels": torch.from_numpy(rank).to(x.device)[labels.long()], "centers": centers.cpu().numpy()[order],
+            "inertia": info["inertia"], "counts": info["counts"][order], "iterations": info["iterations"], "converged": info["converged"]}
+
+
+def pseudo_groups(table, k=2, **kw):
+    """GEORGE's groups: `kmeans` (its keywords in `kw`) within every class of an EmbeddingTable.  The rows are sorted by class with
+    one gather, as group_stats sorts them by group, and each class is a slice.  Returns (clusters numpy int64 [N]: the cluster id,
+    0 .. k-1 and 0 the class's largest, of every row in the table's order; {class: that class's `kmeans` dict without its labels})."""
+    y = table.targets.cpu().numpy()
+    uniq, counts = np.unique(y, return_counts=True)
+    order = np.argsort(y, kind="stable")
+    xs = ops.gather_rows(table.embeddings.float().contiguous(), torch.from_numpy(order).to(table.embeddings.device))
+    bounds = np.concatenate([[0], np.cumsum(counts)])
+    clusters, fits = np.empty(len(y), dtype=np.int64), {}
+    for i, cls in enumerate(uniq):
+        fit = kmeans(xs[bounds[i]:bounds[i + 1]], k, **kw)
+        clusters[order[bounds[i]:bounds[i + 1]]] = fit.pop("labels").cpu().numpy()
+        fits[int(cls)] = fit
+    return clusters, fits
+
+
+def cluster_agreement(clusters, groups):
+    """How well a partition recovers another, on the host: {'table': the contingency table int64 [clusters, groups] in np.unique
+    order of both, 'purity': sum over clusters of their largest cell / N, 'ari': the adjusted Rand index (Hubert & Arabie 1985): 1
+    for the same partition up to a renaming, about 0 for independent ones; 1 when both are one block}."""
+    a, b = np.asarray(clusters).ravel(), np.asarray(groups).ravel()
+    if a.shape != b.shape or a.size == 0:
+        raise ValueError(f"cluster_agreement: {a.shape} cluster ids for {b.shape} group ids")
+    ua, ia = np.unique(a, return_inverse=True)
+    ub, ib = np.unique(b, return_inverse=True)
+    table = np.zeros((len(ua), len(ub)), dtype=np.int64)
+    np.add.at(table, (ia, ib), 1)
+    pairs = lambda m: (m.astype(np.float64) * (m - 1.0) / 2.0).sum()
+    cells, rows, cols, total = pairs(table), pairs(table.sum(1)), pairs(table.sum(0)), pairs(np.array([a.size]))
+    expected = rows * cols / total if total > 0 else 0.0
+    ceiling = 0.5 * (rows + cols)
+    ari = 1.0 if ceiling == expected else (cells - expected) / (ceiling - expected)
+    return {"table": table, "purity": float(table.max(1).sum() / a.size), "ari": float(ari)}
+
+
+def pseudo_group_table(table, clusters):
+    """An EmbeddingTable over the SAME embedding storage (no copy) whose confounder is the cluster id, so that targets_group =
+    2 y + cluster: given as `train_table` to train_all_epochs / train_sweep with opt.robust it is group DRO without group labels.
+    Val and test keep their true groups, so model selection and the reported worst-group accuracy do not change.  The tables have
+    two places per class: cluster ids outside {0, 1} raise ValueError."""
+    c = np.asarray(clusters)
+    if c.shape != (len(table),) or not np.isin(c, (0, 1)).all():
+        raise ValueError(f"pseudo_group_table: cluster ids must be {len(table)} values in {{0, 1}} (n_places = {table.n_places})")
+    out = trainer.EmbeddingTable(table.embeddings, table.targets.cpu().numpy(), c.astype(np.int64), y_pred=None, filenames=table.filenames,
+                                 device=table.device)
+    out.y_pred = table.y_pred
+    return out

@@ -1445,6 +1445,83 @@ def sym_eig_topk(C, k, tol=1e-10, max_iter=256, check_every=8):
     return ws[2:2 + k], vectors, info
 
 
+KMEANS_MAX_K = 16                   # centres of the k-means kernels (csrc/kmeans.hip); more wants an MFMA tile kernel
+_KMEANS_STATUS = 256                # bytes of the status block at the head of the workspace (include/dbmm.h)
+
+
+def _kmeans_operands(what, x, centers):
+    require_cuda(x, centers)
+    _f32c(x)
+    _f32c(centers)
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise _lib.DbmmError(f"{what}: x must be [N, D] with N >= 1, got {tuple(x.shape)}")
+    N, D = x.shape
+    if centers.dim() != 2 or centers.shape[1] != D or centers.shape[0] < 1:
+        raise _lib.DbmmError(f"{what}: centers must be [K, {D}] with K >= 1, got {tuple(centers.shape)}")
+    if centers.device != x.device:
+        raise _lib.DbmmError(f"{what}: centers is on {centers.device}, x on {x.device}")
+    K = centers.shape[0]
+    if K > KMEANS_MAX_K or D % 4 or D > 4096:
+        raise DbmmUnsupported(f"{what}: K = {K}, D = {D}; the kernels serve K <= {KMEANS_MAX_K}, D % 4 == 0, D <= 4096")
+    return N, D, K
+
+
+def kmeans_assign(x, centers):
+    """(labels int32 [N], dmin fp32 [N]): the nearest of the centres fp32 [K, D] (K <= 16; the lowest index on an exact tie) and the
+    squared distance to it, for every row of x fp32 [N, D] (D % 4 == 0, D <= 4096), in one read of x (dbmm_kmeans_assign).  The
+    distances are sums of squared differences in fp32, and a row's result does not depend on the other rows: assigning a slice gives
+    the bits of the slice of the assignment."""
+    N, D, K = _kmeans_operands("kmeans_assign", x, centers)
+    labels = _empty((N,), device=x.device, dtype=torch.int32)
+    dmin = _empty((N,), device=x.device, dtype=torch.float32)
+    rc = _lib.lib().dbmm_kmeans_assign(x.data_ptr(), centers.data_ptr(), labels.data_ptr(), dmin.data_ptr(), N, D, K, stream())
+    if rc == _lib.E_UNSUPPORTED:
+        raise DbmmUnsupported(f"kmeans_assign: no kernel for N = {N}, D = {D}, K = {K}")
+    check(rc, "kmeans_assign")
+    return labels, dmin
+
+
+def kmeans_fit(x, centers0, max_iter=100, check_every=8):
+    """Lloyd's k-means of the rows x fp32 [N, D] from the start centres centers0 fp32 [K, D] (K <= 16, N >= K, D % 4 == 0,
+    D <= 4096) on the device (dbmm_kmeans_begin / dbmm_kmeans_iterate): per iteration one assignment, the per-cluster sums in a fixed
+    order and the float64 merge; a cluster that loses all its rows keeps its centre.  Returns (centers fp32 [K, D], labels int32
+    [N], info): device tensors, views of the call's workspace, and info = {'iterations', 'converged', 'inertia': the float64 sum of the
+    squared distances of the last assignment, 'counts': numpy int64 [K] of that assignment}.  Converged means that an assignment
+    changed no label; labels, inertia and counts then belong to the returned centres.
+
+    The loop enqueues min(check_every, remaining) iterations, reads the status block (one small copy to the host) and stops on
+    'converged' or max_iter; iterations enqueued after convergence are no-ops on the device, so the result does not depend on
+    check_every, and two calls give the same bits.  Non-convergence is reported, never raised."""
+    N, D, K = _kmeans_operands("kmeans_fit", x, centers0)
+    max_iter, check_every = int(max_iter), int(check_every)
+    if max_iter < 1 or check_every < 1:
+        raise _lib.DbmmError(f"kmeans_fit: max_iter = {max_iter}, check_every = {check_every}; both at least 1")
+    if N < K:
+        raise _lib.DbmmError(f"kmeans_fit: {N} rows for {K} centres")
+    L = _lib.lib()
+    nbytes = L.dbmm_workspace_bytes_kmeans(N, D, K)
+    if nbytes == 0:
+        raise DbmmUnsupported(f"kmeans_fit: no kernel for N = {N}, D = {D}, K = {K}")
+    ws = _empty((nbytes // 4,), device=x.device, dtype=torch.float32).view(torch.uint8)       # (the layout is in bytes, a multiple of 16)
+    check(L.dbmm_kmeans_begin(centers0.data_ptr(), N, D, K, ws.data_ptr(), nbytes, stream()), "kmeans_begin")
+    done = 0
+    while True:
+        n = min(check_every, max_iter - done)
+        check(L.dbmm_kmeans_iterate(x.data_ptr(), N, D, K, n, ws.data_ptr(), nbytes, stream()), "kmeans_iterate")
+        done += n
+        status = ws[:_KMEANS_STATUS].cpu().numpy()
+        words = status.view(np.int64)
+        if words[1] != 0 or done >= max_iter:
+            break
+    info = {"iterations": int(words[0]), "converged": bool(words[1] == 1), "inertia": float(status.view(np.float64)[3]),
+            "counts": words[4:4 + K].copy()}
+    c0 = _KMEANS_STATUS
+    l0 = c0 + K * D * 4
+    centers = ws[c0:c0 + K * D * 4].view(torch.float32).view(K, D)
+    labels = ws[l0:l0 + N * 4].view(torch.int32)
+    return centers, labels, info
+
+
 # ---- fp16 mode of the transformer towers (csrc/f16_ops.hip) -------------------------------------------------------
 
 def _f16c(t):

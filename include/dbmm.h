@@ -824,6 +824,48 @@ size_t dbmm_workspace_bytes_sym_eig(int64_t D);
 int dbmm_sym_eig_begin(const double* q0, int64_t D, int64_t k, double tol, void* workspace, size_t workspace_bytes, void* stream);
 int dbmm_sym_eig_iterate(const double* C, int64_t D, int64_t n_iter, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Lloyd's k-means of the rows x fp32 [N][D] (contiguous) into K <= 16 clusters WITHOUT leaving the device: the label-free groups of
+ * group DRO (Sohoni et al. 2020) and the question whether a representation separates the spurious attribute.  The reference has no
+ * counterpart.  x is read twice per iteration; nothing N x D or N x K is allocated.
+ *   dbmm_kmeans_begin    copies the start centres centers0 fp32 [K][D] into the workspace, sets every label to -1 and clears the status.
+ *                        One launch.
+ *   dbmm_kmeans_iterate  enqueues exactly n_iter iterations, three launches each:
+ *                          assign  label[i] = argmin_j d2_ij (the lowest j on an exact tie), dmin[i] = min_j d2_ij, with
+ *                                  d2_ij = sum_d (x_id - c_jd)^2 formed FROM THE DIFFERENCES in fp32 (one fmaf chain per (row, centre) in
+ *                                  column order, a fixed shuffle tree): a row's result depends on that row and the centres only.  The
+ *                                  rows whose label changed are counted with an integer atomic.
+ *                          sums    per-cluster column sums per (one of P row ranges, 256 columns), rows in order, in float64 from the
+ *                                  first add (there is no fp32 chain); P depends on (N, D) only.  Also the ranges' row counts and
+ *                                  float64 sums of dmin.
+ *                          merge   the partials added in a fixed order (range order within each quarter of the ranges, then the
+ *                                  quarters in order); c_j <- fp32(sum_j / n_j) in float64; a cluster without rows
+ *                                  keeps its centre (count 0).  When the assignment changed no label the state becomes `converged`
+ *                                  instead and the centres stay the ones that labels, dmin and inertia were computed against.
+ *                        Every kernel reads the state first and does nothing unless it is `running`: iterations enqueued after
+ *                        convergence are no-ops, and the result and the iteration count do not depend on how n_iter is cut into calls.
+ *                        Plain launches on `stream`; no memset, no floating-point atomics: two runs give the same bits.
+ *   dbmm_kmeans_assign   the assignment alone against given centres fp32 [K][D], into labels int32 [N] and dmin fp32 [N]: one launch,
+ *                        no workspace.  Places other rows (val, test) at fitted centres, so N may be below K here (N >= 1).  A slice
+ *                        of the rows gets the bits of the slice of the whole assignment.
+ * Workspace, in bytes (Python reads views of it); every part starts 16-byte aligned:
+ *   [0, 256)    the status, 8-byte words: [0] int64 iterations done; [1] int64 state: 0 running, 1 converged; [2] int64 rows whose
+ *               label changed in the last assignment; [3] double inertia = sum_i dmin[i] of the last assignment; [4..19] int64
+ *               counts[16], the clusters' rows in the last assignment; [20..31] internal words
+ *   [256, ..)   centres fp32 [K][D]
+ *   then        labels int32 [N], padded to 16 bytes; dmin fp32 [N], padded to 16 bytes
+ *   then        the partials: float64 [P][K][D] sums, int64 [P][16] counts, float64 [P] sums of dmin
+ * with P = min(ceil(2048 / ceil(D / 256)), ceil(N / 64)), at least 1.
+ * K < 1, N < K, D <= 0, D % 4 != 0, n_iter < 0: DBMM_E_SHAPE; K > 16 (that wants an MFMA tile kernel), D > 4096 or N >= 2^31:
+ * DBMM_E_UNSUPPORTED; then null pointers: DBMM_E_ARG; a short workspace: DBMM_E_WORKSPACE; x, the centres or the workspace not
+ * 16-byte aligned (labels, dmin of dbmm_kmeans_assign: 4-byte): DBMM_E_ALIGN.  Every check precedes the first launch.
+ * dbmm_workspace_bytes_kmeans is 0 for a shape that is not served. */
+size_t dbmm_workspace_bytes_kmeans(int64_t N, int64_t D, int64_t K);
+int dbmm_kmeans_begin(const float* centers0, int64_t N, int64_t D, int64_t K, void* workspace, size_t workspace_bytes, void* stream);
+int dbmm_kmeans_iterate(const float* x, int64_t N, int64_t D, int64_t K, int64_t n_iter, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int dbmm_kmeans_assign(const float* x, const float* centers, int32_t* labels, float* dmin, int64_t N, int64_t D, int64_t K,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
