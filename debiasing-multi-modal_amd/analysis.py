@@ -459,3 +459,133 @@ def pseudo_group_table(table, clusters):
                                  device=table.device)
     out.y_pred = table.y_pred
     return out
+
+
+# ---- silhouettes: how well a labelling is separated in a representation (Rousseeuw 1987) -----------------------------------------
+# Exact, O(N^2 D), and without the N x N matrix: ops.pairdist_row_group_sums gives every row its summed distance to every label in
+# one pass.  Per row, so it names the rows whose own group is not their nearest one; per labelling, so it needs no second partition
+# (cluster_agreement does) and exists before and after `transform`; and it is the criterion kmeans_select_k chooses k by.
+
+def silhouette_from_sums(R, dense_labels, counts):
+    """The host step of `silhouette`, numpy only.  R float64 [N, G]: R[i, g] = sum over j != i with label g of ||x_i - x_j||;
+    dense_labels int [N] in [0, G); counts [G]: the rows per label (they must be dense_labels' own counts).  The conventions:
+    a_i = R[i, g_i] / (n_{g_i} - 1); b_i = min over g != g_i with n_g > 0 of R[i, g] / n_g; s_i = (b_i - a_i) / max(a_i, b_i);
+    s_i = 0 (and a_i = 0) for a row alone in its label (Rousseeuw's and sklearn's convention) and where max(a_i, b_i) == 0 (all
+    rows identical); empty labels are ignored; fewer than two labels with rows raise ValueError.  Returns {'a', 'b', 'samples':
+    float64 [N], 'nearest': int64 [N], the label index that attains b_i, the lowest index on a tie}."""
+    R = np.asarray(R, dtype=np.float64)
+    g = np.asarray(dense_labels).astype(np.int64).ravel()
+    n = np.asarray(counts).astype(np.int64).ravel()
+    if R.ndim != 2 or g.shape != (R.shape[0],) or n.shape != (R.shape[1],):
+        raise ValueError(f"silhouette_from_sums: R {R.shape}, {g.shape[0]} labels, {n.shape[0]} counts")
+    N, G = R.shape
+    if N and (g.min() < 0 or g.max() >= G) or not np.array_equal(np.bincount(g, minlength=G), n):
+        raise ValueError("silhouette_from_sums: counts are not the counts of dense_labels")
+    present = n > 0
+    if present.sum() < 2:
+        raise ValueError(f"a silhouette needs at least two labels with rows, got {int(present.sum())}")
+    rows = np.arange(N)
+    own = n[g]
+    a = np.where(own > 1, R[rows, g] / np.maximum(own - 1, 1), 0.0)
+    M = R / np.where(present, n, 1).astype(np.float64)[None, :]
+    M[:, ~present] = np.inf
+    M[rows, g] = np.inf
+    nearest = M.argmin(axis=1)                                      # the first minimum: the lowest index on a tie
+    b = M[rows, nearest]
+    top = np.maximum(a, b)
+    s = np.where((own > 1) & (top > 0), (b - a) / np.where(top > 0, top, 1.0), 0.0)
+    return {"a": a, "b": b, "samples": s, "nearest": nearest.astype(np.int64)}
+
+
+def silhouette(embeddings, labels=None, transform=None):
+    """The exact silhouette of a labelling of a split's rows, Euclidean distances, on the device (ops.pairdist_row_group_sums: one
+    pass over the 256 x 256 tiles of the Gram matrix, nothing N x N is stored).
+
+    `embeddings`: an EmbeddingTable (its targets_group unless `labels` is given) or a device tensor [N, D] with `labels` [N] (any
+    integers; they go through np.unique, at most 16 of them: more raise DbmmUnsupported, fewer than two ValueError, both before
+    anything is launched).  `transform` (a callable emb -> emb, e.g. the stage-1 adapter) is applied batch by batch in eval mode
+    first, as in `kmeans`.  The rows are sorted by label with one gather, as group_stats sorts them by group (nearly every tile of
+    the kernel then holds one label), the centre is that copy's mean, and everything is returned in the INPUT's row order:
+    {'samples': float64 [N], 'score': their mean, 'per_label': {label: mean of its rows}, 'a', 'b': float64 [N] (the mean distance
+    to the row's own label and to the nearest other one), 'nearest': [N], the nearest other label of every row (a value of
+    `labels`), 'labels': the unique labels, 'counts'}.  The conventions are silhouette_from_sums'."""
+    x, l_np = _rows_and_groups(embeddings, labels)
+    uniq, dense, counts = np.unique(l_np, return_inverse=True, return_counts=True)
+    G, N = len(uniq), x.shape[0]
+    if G > ops.PAIRDIST_ROWS_MAX_G:
+        raise ops.DbmmUnsupported(f"silhouette: {G} labels; the distance kernel sums at most {ops.PAIRDIST_ROWS_MAX_G}")
+    if G < 2:
+        raise ValueError(f"a silhouette needs at least two labels with rows, got {G}")
+    x = x.float().contiguous()
+    if transform is not None:
+        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
+    dense = dense.reshape(-1)
+    order = np.argsort(dense, kind="stable")
+    xs = ops.gather_rows(x, torch.from_numpy(order).to(x.device))
+    center = torch.from_numpy((_column_sums(xs) / N).astype(np.float32)).to(x.device)
+    gs = torch.from_numpy(dense[order].astype(np.int64)).to(x.device)
+    sorted_sums = ops.pairdist_row_group_sums(xs, gs, G, center).cpu().numpy()
+    R = np.empty_like(sorted_sums)
+    R[order] = sorted_sums
+    out = silhouette_from_sums(R, dense, counts)
+    s = out["samples"]
+    return {"samples": s, "score": float(s.mean()), "per_label": {lab: float(s[dense == i].mean()) for i, lab in enumerate(uniq)},
+            "a": out["a"], "b": out["b"], "nearest": uniq[out["nearest"]], "labels": uniq, "counts": counts}
+
+
+def _device_rows(embeddings, transform):
+    x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+    x = x.float().contiguous()
+    return x if transform is None else _transformed_rows(x, transform, TRANSFORM_ROWS)
+
+
+def kmeans_select_k(embeddings, ks=(2, 3, 4, 5, 6, 7, 8), transform=None, **kmeans_kw):
+    """The number of clusters by the silhouette: one `kmeans` fit (its keywords in `kmeans_kw`) and one `silhouette` of that fit's
+    labels per k in `ks` (each in 2..16), on the same rows -- `transform` is applied once, before the first fit.  Returns {'k': the
+    k of the largest score, the smaller k on a tie, 'scores': {k: score}, 'fits': {k: `kmeans`' dict}}; a fit that left fewer than
+    two clusters with rows scores nan and is never chosen.  It REPORTS k: pseudo_group_table still takes two clusters per class,
+    the tables are not widened."""
+    ks = sorted({int(k) for k in ks})
+    if not ks or ks[0] < 2 or ks[-1] > ops.KMEANS_MAX_K:
+        raise ValueError(f"kmeans_select_k: ks = {ks}; values in 2..{ops.KMEANS_MAX_K}")
+    x = _device_rows(embeddings, transform)
+    scores, fits, best = {}, {}, None
+    for k in ks:
+        fit = kmeans(x, k, **kmeans_kw)
+        fits[k] = fit
+        scores[k] = silhouette(x, fit["labels"])["score"] if (fit["counts"] > 0).sum() >= 2 else float("nan")
+        if scores[k] == scores[k] and (best is None or scores[k] > scores[best]):
+            best = k
+    if best is None:
+        raise ValueError("kmeans_select_k: no fit has two clusters with rows")
+    return {"k": best, "scores": scores, "fits": fits}
+
+
+def _score_or_nan(x, labels):
+    if len(np.unique(labels)) < 2:
+        return {"score": float("nan"), "per_label": {}}
+    fit = silhouette(x, labels)
+    return {"score": fit["score"], "per_label": fit["per_label"]}
+
+
+def separation_report(train_table, val_table, test_table, transform=None):
+    """How separable the groups, and within each class the spurious attribute, are in a representation: {'train': r, 'val': r,
+    'test': r} with r = {'group': {'score', 'per_label'} of `silhouette` on targets_group, 'spurious_within_class': {class: the
+    silhouette score of the confounder among that class's rows}}.  A class in which only one place is present gets nan; nothing is
+    raised.  `transform` (a callable emb -> emb) is applied once per split, as in `kmeans`: run it once raw and once with the
+    stage-1 or stage-2 adapter, the within-class scores should fall when the debiasing works."""
+    out = {}
+    for split, table in (("train", train_table), ("val", val_table), ("test", test_table)):
+        x = _device_rows(table, transform)
+        y, c = table.targets.cpu().numpy(), table.targets_spurious.cpu().numpy()
+        within = {}
+        for cls in np.unique(y):
+            idx = np.flatnonzero(y == cls)
+            if len(np.unique(c[idx])) < 2:
+                within[int(cls)] = float("nan")
+                continue
+            within[int(cls)] = silhouette(ops.gather_rows(x, torch.from_numpy(idx).to(x.device)), c[idx])["score"]
+        out[split] = {"group": _score_or_nan(x, table.targets_group.cpu().numpy()), "spurious_within_class": within}
+    return out

@@ -288,3 +288,269 @@ extern "C" int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, c
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
 }
+
+// ---- per-row, per-group sums: R[i][g] = sum over j != i with group[j] == g of ||x_i - x_j||_2, float64 [N][G] (the silhouette's input) -------
+// The same planes, ring and distance arithmetic; the epilogue reduces ALONG THE COLUMNS of a tile per row instead of into (group, group)
+// buckets, so the kernel walks the full square of 256 x 256 blocks (the triangle's column sums would need an (other block) x N x G buffer to
+// fold deterministically).  A work unit is one row block and a run of consecutive column blocks (a "column chunk", C of them per row block,
+// chosen on the host); units are numbered chunk-major, so the workgroups of an XCD walk the same column blocks at about the same time.  A
+// workgroup handles its unit's column blocks in order and keeps one float64 running sum per (row, group) IN PLACE in the unit's [256][G]
+// block of part [C][N][G] (zeroed by a memset; thread t < 256 owns row t, nobody else touches the block): the ring leaves neither sixteen
+// registers per thread nor 32 KB of LDS for them.  pairdist_rows_fold_kernel adds the C partials in chunk order and rescales.
+// Order of a sum: a lane's two columns and the 32 fr lanes by a fixed fp32 tree (depth 6: 6 x 2^-24 relative, the terms are non-negative),
+// then float64: the four column waves in wave order, the unit's tiles in walk order, the chunks in chunk order.  No floating-point atomics.
+// A column takes its label from `groups` directly (RowInfo's NO_GROUP = 15 is a label here): labels outside [0, G) and columns >= N are in
+// no sum.  The fast path is a tile off the diagonal whose 256 columns all carry one label; every other tile takes the predicated path, once
+// per label present among its columns.
+namespace {
+
+constexpr int ROWS_MAX_G = 16;                                     // labels live in a byte; 16 = the k-means kernels' K
+constexpr int ROWS_NO_GROUP = 255;                                 // columns past N / labels outside [0, G): in no sum
+constexpr int ROWS_MAX_CHUNKS = 16;
+
+struct PairRowsP {
+    const u16* P; const RowInfo* info; const int64_t* groups; double* part;      // part [C][N][G]
+    long long ldp, p_total;                                        // halves per row of P (2 Dp), bytes of P
+    int N, T, nb, G, C, n_units;                                   // T = Dp / 64 K tiles per plane, nb = row blocks of 256, units = nb * C
+};
+
+// v[16 ii + r] (ii = 0 / 1, r < 16) of the 32 lanes with the same fh -> the sums over those lanes, one per lane: afterwards lane fr holds in
+// v[0] the sum of value number fr.  Step s pairs lane fr with fr ^ (16 >> s); the lane whose bit is set keeps the upper half of what is left.
+__device__ __forceinline__ void fold_fr_lanes(float (&v)[32], int fr) {
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        const int h = 16 >> s;
+        const bool up = (fr >> (4 - s)) & 1;
+#pragma unroll
+        for (int k = 0; k < h; ++k) {
+            const float lo = v[k], hi = v[k + h];
+            v[k] = (up ? hi : lo) + __shfl_xor(up ? lo : hi, 16 >> s, 64);
+        }
+    }
+}
+
+__global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const PairRowsP p) {
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[8 * PH_HALF];      // [buffer 2][Ah0, Bh0, Bh1, Ah1] = 128 KB
+    __shared__ float e_norm[512];                                  // epilogue: norms of the tile's 256 rows, then of its 256 columns
+    __shared__ unsigned char e_grp[256];                           // labels of the tile's columns
+    __shared__ unsigned e_mask;                                    // labels present among the columns; bit 16: a column in no group
+    __shared__ float e_rsum[2][4][256];                            // [parity][column wave][row]: a wave's sums over its 64 columns
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 2, wc = wid & 3;
+    const int fr = lane & 31, fh = lane >> 5;
+    const TileWalk walk = tile_walk(blockIdx.x, gridDim.x, p.n_units);
+    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.P, 0, 0, 0x00020000);
+    __amdgpu_buffer_rsrc_t rsA = rs0, rsW = rs0;
+    int m0 = 0, n0 = 0;
+    unsigned voff[4][2];                                           // the stager's lane offsets per half-tile kind (Ah0, Bh0, Bh1, Ah1); rows >= N masked
+    auto set_tile = [&](int t, int bi, int bj) {
+        m0 = bi * 256; n0 = bj * 256;
+        rsA = desc(p.P, p.p_total, (long long)m0 * p.ldp * 2);
+        rsW = desc(p.P, p.p_total, (long long)n0 * p.ldp * 2);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                int ra, rw;
+                unsigned cb;
+                ring_rows(t, i, h, ra, rw, cb);
+                voff[h ? 3 : 0][i] = m0 + ra < p.N ? (unsigned)ra * (unsigned)(p.ldp * 2) + cb : OOR;
+                voff[h ? 2 : 1][i] = n0 + rw < p.N ? (unsigned)rw * (unsigned)(p.ldp * 2) + cb : OOR;
+            }
+        }
+    };
+    // unit number k of this workgroup -> its row block, chunk and column blocks [lo, hi)
+    auto unit = [&](int k, int& bi, int& c, int& lo, int& hi) {
+        const int u = walk.first + k * walk.stride;
+        c = u / p.nb; bi = u - c * p.nb;
+        lo = (int)((long long)c * p.nb / p.C); hi = (int)((long long)(c + 1) * p.nb / p.C);
+    };
+    const int nT = 3 * p.T;                                          // K tiles of the three products: hi.hi, hi.lo, lo.hi
+    auto ring_src = [&](int kind, int t, __amdgpu_buffer_rsrc_t& rs, unsigned (&vo)[2], unsigned& so) {
+        const bool isA = kind == 0 || kind == 3, valid = t < nT;
+        rs = valid ? (isA ? rsA : rsW) : rs0;
+        const int kt = isA ? (t < p.T ? t : t - p.T) : (t < 2 * p.T ? t : t - 2 * p.T);
+        vo[0] = voff[kind][0]; vo[1] = voff[kind][1];
+        so = (unsigned)kt * 128u;
+    };
+#include "fp16_ring.inc"
+
+    const int wm0 = wr * 128, wn0 = wc * 64;
+    int k = 0, bi = 0, ch = 0, bj = 0, hi = 0, par = 0;
+    if (tid == 0) e_mask = 0u;
+    if (walk.n_whole > 0) { unit(0, bi, ch, bj, hi); set_tile(tid, bi, bj); ring_prologue(0); }
+    while (k < walk.n_whole) {
+        ring_item(0, nT, true, [](int) {});                           // (every item waits for all of its prologue and the epilogue's stores)
+        const int em0 = m0, en0 = n0, ech = ch;
+        // everything per-lane below is recomputed from an opaque copy of tid: hoisted out of the item loop it would live across the ring's
+        // phases, which leave two registers free, and be spilled
+        int te = tid;
+        asm volatile("" : "+v"(te));
+        const int fr = te & 31, fh = (te >> 5) & 1;
+        if (bj + 1 == hi) { if (++k < walk.n_whole) unit(k, bi, ch, bj, hi); } else ++bj;
+        if (k < walk.n_whole) { set_tile(te, bi, bj); ring_prologue(0); }    // in flight during the epilogue
+
+        // ---- epilogue: distances and per-row sums straight from the accumulators ------------------------------------------------
+        // lane (fr, fh) holds columns wn0 + 2 fr + j (blocks j = 0 / 1: the B halves are the even / odd columns) of rows
+        // wm0 + 32 i + (r & 3) + 8 (r >> 2) + 4 fh.
+        {
+            const int src = (te < 256 ? em0 : en0 - 256) + te;      // threads 0 .. 255: the tile's rows, 256 .. 511: its columns
+            e_norm[te] = src < p.N ? p.info[src].norm : 0.f;
+            if (te >= 256) {
+                int g = ROWS_NO_GROUP;
+                if (src < p.N) {
+                    const int64_t gv = p.groups[src];
+                    if (gv >= 0 && gv < p.G) g = (int)gv;
+                }
+                e_grp[te - 256] = (unsigned char)g;
+                atomicOr(&e_mask, g == ROWS_NO_GROUP ? 0x10000u : 1u << g);        // integer, order-free
+            }
+        }
+        __syncthreads();
+        const unsigned mB = e_mask;
+        const bool diag = em0 == en0;
+        const bool fast = !diag && __builtin_popcount(mB) == 1 && mB < 0x10000u;
+        const int c0 = wn0 + 2 * fr;
+        const float cn0 = e_norm[256 + c0], cn1 = e_norm[256 + c0 + 1];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float rn = e_norm[wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh];
+                acc[i][0][r] = __builtin_sqrtf(fmaxf(fmaf(-2.f, acc[i][0][r], rn + cn0), 0.f));
+                acc[i][1][r] = __builtin_sqrtf(fmaxf(fmaf(-2.f, acc[i][1][r], rn + cn1), 0.f));
+            }
+        if (diag) {                                                   // the pair (i, i) is in no sum: by index, whatever its value
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int lr = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    acc[i][0][r] = lr == c0 ? 0.f : acc[i][0][r];
+                    acc[i][1][r] = lr == c0 + 1 ? 0.f : acc[i][1][r];
+                }
+        }
+        const int gb0 = e_grp[c0], gb1 = e_grp[c0 + 1];
+        // after the fold of row blocks 2 hh, 2 hh + 1 lane fr holds value fr: i = 2 hh + (fr >> 4), r = fr & 15
+        const int out_row = wm0 + 32 * (fr >> 4) + (fr & 3) + 8 * ((fr & 15) >> 2) + 4 * fh;
+        // this tile's running sums: thread t < 256 owns row em0 + t of the unit's block of part, for every label (in place: sixteen float64
+        // sums per row held across the ring's phases do not fit its register budget, and [256][16] float64 does not fit beside the ring in LDS)
+        const bool owner = te < 256 && em0 + te < p.N;
+        auto fold_store = [&](float (&v)[32], int hh) {
+            fold_fr_lanes(v, fr);
+            e_rsum[par][wc][out_row + 64 * hh] = v[0];
+        };
+        auto add_label = [&](int g) {                                 // the four column waves in wave order, onto the running sum
+            __syncthreads();
+            if (owner)
+                p.part[((size_t)ech * p.N + em0 + te) * p.G + g] += (double)e_rsum[par][0][te] + (double)e_rsum[par][1][te] + (double)e_rsum[par][2][te] + (double)e_rsum[par][3][te];
+            par ^= 1;                                                 // the next label's sums go to the other half: one barrier per label
+        };
+        if (fast) {                                                   // one label, all 256 columns: no predicates
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                float v[32];
+#pragma unroll
+                for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) v[16 * ii + r] = acc[2 * hh + ii][0][r] + acc[2 * hh + ii][1][r];
+                fold_store(v, hh);
+            }
+            add_label(__builtin_ctz(mB));
+        } else {
+            for (unsigned mb = mB & 0xffffu; mb; mb &= mb - 1) {      // once per label present among the columns
+                const int g = __builtin_ctz(mb);
+                const bool in0 = gb0 == g, in1 = gb1 == g;
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    float v[32];
+#pragma unroll
+                    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) v[16 * ii + r] = (in0 ? acc[2 * hh + ii][0][r] : 0.f) + (in1 ? acc[2 * hh + ii][1][r] : 0.f);
+                    fold_store(v, hh);
+                }
+                add_label(g);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) e_mask = 0u;                                    // for the next tile: its atomics come after that tile's ring barriers
+    }
+}
+
+// chunk partials -> R [N][G], in chunk order; distances were taken in units of 2^-s
+__global__ __launch_bounds__(256) void pairdist_rows_fold_kernel(const double* __restrict__ part, int C, long long n_out, const unsigned* __restrict__ amax_bits,
+                                                                 double* __restrict__ R) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_out) return;
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += part[(size_t)c * n_out + i];
+    R[i] = ldexp(s, -scale_exp(__uint_as_float(*amax_bits)));
+}
+
+// Column chunks per row block: 1 .. min(16, nb), the count whose schedule is shortest -- rounds of the persistent grid times the tiles of the
+// longest unit --, the smaller count on a tie.  Few row blocks want many chunks to fill the grid; many row blocks still gain when
+// nb / MAX_WG is just above a whole number (636 row blocks: 3 rounds of 636 tiles with one chunk, 5 rounds of 318 with two).
+inline int rows_chunks(long long nb) {
+    long long best = 0;
+    int C = 1;
+    for (int c = 1; c <= ROWS_MAX_CHUNKS && c <= nb; ++c) {
+        const long long units = nb * c, grid = units < MAX_WG ? units : MAX_WG;
+        const long long cost = ((units + grid - 1) / grid) * ((nb + c - 1) / c);
+        if (c == 1 || cost < best) { best = cost; C = c; }
+    }
+    return C;
+}
+
+}  // namespace
+
+// see include/dbmm.h
+extern "C" size_t dbmm_workspace_bytes_pairdist_rows(int64_t N, int64_t D, int64_t G) {
+    if (N <= 0 || D <= 0 || G < 1 || G > ROWS_MAX_G) return 0;
+    const size_t Dp = (size_t)padded_dim(D);
+    // the partials are sized for 16 chunks whatever rows_chunks picks: the size then grows with N
+    return HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256) + align_up((size_t)N * 2 * Dp * 2, 256) +
+           (size_t)ROWS_MAX_CHUNKS * (size_t)N * (size_t)G * sizeof(double);
+}
+
+// see include/dbmm.h
+extern "C" int dbmm_pairdist_row_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N, int64_t D,
+                                            int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
+    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > ROWS_MAX_G) return DBMM_E_SHAPE;
+    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
+    if (!x || !groups || !center || !sums || !workspace) return DBMM_E_ARG;
+    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
+    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rows(N, D, G)) return DBMM_E_WORKSPACE;
+    const long long Dp = padded_dim(D);
+    char* ws = (char*)workspace;
+    unsigned* amax = (unsigned*)ws;
+    RowInfo* info = (RowInfo*)(ws + HEAD_BYTES);
+    u16* P = (u16*)(ws + HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256));
+    double* part = (double*)((char*)P + align_up((size_t)N * 2 * Dp * 2, 256));
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(amax, 0, HEAD_BYTES, s);
+    if (e != hipSuccess) return (int)e;
+    const long long n4 = N * D / 4;
+    const int g1 = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+    hipLaunchKernelGGL(pairdist_absmax_kernel, dim3(g1), dim3(256), 0, s, x, center, n4, (int)(D / 4), amax);
+    DBMM_CHECK_LAUNCH();
+    // (the split's own group column is not read here: the tile kernel takes the labels from `groups`)
+    hipLaunchKernelGGL(pairdist_split_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
+                       (int)G);
+    DBMM_CHECK_LAUNCH();
+    PairRowsP p{};
+    p.P = P; p.info = info; p.groups = groups; p.part = part;
+    p.ldp = 2 * Dp; p.p_total = (long long)N * 2 * Dp * 2;
+    p.N = (int)N; p.T = (int)(Dp / 64); p.nb = (int)((N + 255) / 256); p.G = (int)G;
+    p.C = rows_chunks(p.nb);
+    p.n_units = p.nb * p.C;
+    e = hipMemsetAsync(part, 0, (size_t)p.C * (size_t)N * (size_t)G * sizeof(double), s);    // the units' running sums start at zero
+    if (e != hipSuccess) return (int)e;
+    const int grid = p.n_units < MAX_WG ? p.n_units : MAX_WG;
+    hipLaunchKernelGGL(pairdist_rows_tile_kernel, dim3(grid), dim3(512), 0, s, p);
+    DBMM_CHECK_LAUNCH();
+    const long long n_out = N * G;
+    hipLaunchKernelGGL(pairdist_rows_fold_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, part, p.C, n_out, amax, sums);
+    DBMM_CHECK_LAUNCH();
+    return DBMM_OK;
+}

@@ -1342,6 +1342,44 @@ def pairdist_group_sums(x, groups, n_groups, center):
     return out
 
 
+PAIRDIST_ROWS_MAX_G = 16             # labels of the per-row distance sums (csrc/pairdist.hip); the value of KMEANS_MAX_K
+
+
+def pairdist_row_group_sums(x, groups, n_groups, center):
+    """R float64 [N, G]: R[i, g] = sum over j != i with groups[j] == g of ||x[i] - x[j]||_2, on the fused Gram-and-distance kernel
+    (dbmm_pairdist_row_group_sums): no N x N matrix, float64 sums in a fixed order, the same bits on every call.  x fp32 [N, D]
+    (D % 64 == 0, D <= 4096), groups int64 [N] (n_groups <= 16; a row with a label outside [0, n_groups) is in nobody's sums and
+    still gets its own), center fp32 [D]: a vector near the rows' mean (the split's mean vector), subtracted before the products
+    are formed.  The diagonal is left out by index: R[i, groups[i]] of a group's only row and the column of an empty group are
+    exactly 0.  Rows sorted by group take the kernel's fast path; any order gives the same sums to 1e-6."""
+    require_cuda(x, groups, center)
+    _f32c(x)
+    _f32c(center)
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise _lib.DbmmError(f"pairdist_row_group_sums: x must be [N, D] with N >= 1, got {tuple(x.shape)}")
+    N, D = x.shape
+    if groups.dtype != torch.int64 or not groups.is_contiguous() or groups.dim() != 1:
+        raise _lib.DbmmError("pairdist_row_group_sums: groups must be a contiguous int64 [N] tensor")
+    _sized("pairdist_row_group_sums: groups", groups, N)
+    _sized("pairdist_row_group_sums: center", center, D)
+    if groups.device != x.device or center.device != x.device:
+        raise _lib.DbmmError(f"pairdist_row_group_sums: groups is on {groups.device}, center on {center.device}, x on {x.device}")
+    if not 1 <= n_groups <= PAIRDIST_ROWS_MAX_G:
+        raise _lib.DbmmError(f"pairdist_row_group_sums: n_groups = {n_groups} outside 1..{PAIRDIST_ROWS_MAX_G}")
+    if D % 64 or D > 4096:
+        raise DbmmUnsupported(f"pairdist_row_group_sums: D = {D}; the kernel serves D % 64 == 0, D <= 4096")
+    L = _lib.lib()
+    nbytes = L.dbmm_workspace_bytes_pairdist_rows(N, D, n_groups)
+    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # planes and partials: sized by the call, not cached
+    out = _empty((N, n_groups), device=x.device, dtype=torch.float64)
+    rc = L.dbmm_pairdist_row_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), out.data_ptr(), N, D, n_groups, ws.data_ptr(),
+                                        ws.numel() * 4, stream())
+    if rc == _lib.E_UNSUPPORTED:
+        raise DbmmUnsupported(f"pairdist_row_group_sums: no kernel for N = {N}, D = {D}")
+    check(rc, "pairdist_row_group_sums")
+    return out
+
+
 def _pca_operands(what, x, center):
     require_cuda(x, center)
     _f32c(x)

@@ -772,6 +772,20 @@ size_t dbmm_workspace_bytes_pairdist(int64_t N, int64_t D);
 int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N,
                              int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Per-row, per-group sums of Euclidean distances without the N x N matrix (what a silhouette needs of the distances):
+ *   sums double [N][G]: sums[i][g] = sum over j != i with groups[j] == g of ||x[i] - x[j]||_2.
+ * Operands, centring, split and distance arithmetic of dbmm_pairdist_group_sums; the kernel walks the full square of 256 x 256
+ * tiles and reduces every tile along its columns.  A column j >= N or with a label outside [0, G) is in no sum; a row with such a
+ * label still gets its G sums.  The diagonal is excluded by index: a group's only row has exactly 0 for its own group, and an empty
+ * group's column is exactly 0.  fp32 over the 64 columns of a wave (a fixed tree of depth 6), float64 above that in a fixed order, no
+ * floating-point atomics: two calls on the same input give the same bits.  Four launches and two memsets on `stream`.
+ * D % 64 != 0 or D > 4096: DBMM_E_UNSUPPORTED; G outside 1..16, N outside 1..2^23: DBMM_E_SHAPE; x, center and the workspace
+ * 16-byte aligned.  The workspace holds the planes (about N * D * 4 bytes), 8 bytes per row and up to 16 partial [N][G] float64
+ * matrices (one per column chunk of the schedule), never N x N. */
+size_t dbmm_workspace_bytes_pairdist_rows(int64_t N, int64_t D, int64_t G);
+int dbmm_pairdist_row_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N,
+                                 int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream);
+
 /* PCA of an embedding split: the scatter matrix without a centred copy of the rows (the deterministic map that stands in for the
  * UMAP / MDS projection of plot_umap, demo/visualizer.py:311-408; classical MDS of the distances dbmm_pairdist_group_sums reports):
  *   scatter double [D][D]: scatter[a][b] = sum_i (x[i][a] - center[a]) (x[i][b] - center[b]), about the GIVEN center exactly.
