@@ -205,6 +205,14 @@ _SIGS = {
     "dbmm_linear_sweep_step": [_P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _I, _L, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_linear_sweep_eval": [_L, _L],
     "dbmm_linear_sweep_eval": [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_weighted_mean": [_P, _P, _P, _L, _P],
+    "dbmm_l2norm_sim_ce_bwd_rows": [_P, _P, _F, _I, _P, _P, _P, _P, _F, _F, _P, _L, _L, _L, _P],
+    "dbmm_adapter_train_step_weighted": [_P] * 26 + [_F, _P, _F, _F, _F, _F, _I, _P, _P, _P, _P, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_adapter_sweep_step_weighted": [_P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _F, _P, _F, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _I, _P, _L,
+                                         _L, _L, _L, _L, _L, _P, _Z, _P],
+    "dbmm_linear_train_step_weighted": [_P] * 6 + [_F, _F, _F, _I, _P, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
+    "dbmm_linear_sweep_step_weighted": [_P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _I, _P, _L, _L, _L, _L,
+                                        _L, _P, _Z, _P],
     "dbmm_workspace_bytes_preprocess": [_L, _L],
     "dbmm_resize_crop_normalize_u8": [_P, _L, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _Z, _P],
     "dbmm_resize_crop_normalize_u8_batch": [_P, _L, _L, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _Z, _P],

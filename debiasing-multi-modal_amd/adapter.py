@@ -41,11 +41,12 @@ class LinearClassifier(nn.Module):
         with torch.no_grad():
             return ops.linear_ce_fwd(features.detach().contiguous(), labels.contiguous(), self.fc.weight.detach(), self.fc.bias.detach())
 
-    def train_step(self, features, labels, optimizer, use_group=False):
+    def train_step(self, features, labels, optimizer, use_group=False, row_weights=None):
         """The step body of train_one_epoch (final_main.py:455-466) for the linear probe -- logits, mean CE, backward and the
         SGD-momentum update -- as ONE C call (one kernel launch up to the library's one-launch batch size).  Uses the optimiser's
         lr / momentum / weight_decay and its `momentum_buffer` state, so it mixes freely with `loss.backward(); optimizer.step()`.
-        Requires train mode.  Returns (mean CE, logits, per-row CE), all on the device."""
+        Requires train mode.  Returns (mean CE, logits, per-row CE), all on the device.  `row_weights` (float32 [B], taken as they
+        are): the step minimises and returns (1 / B) sum_b w_b CE_b, in the same launches; per-row CE stays unweighted."""
         if use_group:
             raise ValueError("LinearClassifier.forward takes no use_group (final_main.py:43-49)")
         if not self.training:
@@ -65,7 +66,8 @@ class LinearClassifier(nn.Module):
             bufs.append(st["momentum_buffer"])
         with torch.no_grad():
             return ops.linear_train_step(features.detach().contiguous(), labels.contiguous(), w.data, b.data, bufs[0], bufs[1],
-                                         group["lr"], group.get("momentum", 0.0), group.get("weight_decay", 0.0), first)
+                                         group["lr"], group.get("momentum", 0.0), group.get("weight_decay", 0.0), first,
+                                         row_weights=row_weights)
 
 
 class _LinearFn(torch.autograd.Function):
@@ -175,6 +177,35 @@ class _SimCEFn(torch.autograd.Function):
         # gloss is a 0-dim device tensor (1.0 for loss.backward()); fold it in on device
         dz = ops.l2norm_sim_ce_bwd(z, inv_norm, tn, T, logits=logits, labels=labels, blended=blended, ebd_weight=w)
         return dz * gloss, None, None, None, None, None
+
+
+class _SimCEWeightedFn(torch.autograd.Function):
+    """Fused logits + cross-entropy under fixed per-row weights: returns (L = (1 / B) sum_b w_b CE_b, logits, per-row CE).  The
+    launches of _SimCEFn (forward rows, mean; backward rows), each reading the weights; the one-call step's bits."""
+
+    @staticmethod
+    def forward(ctx, z, z_old, tn, temperature, ebd_weight, labels, row_w):
+        logits, loss_rows, _, _, inv_norm = ops.l2norm_sim_ce_fwd(z, tn, temperature, labels=labels, z_old=z_old, ebd_weight=ebd_weight,
+                                                                  want_mean=False)
+        loss = ops.weighted_mean(loss_rows, row_w)
+        ctx.save_for_backward(z, inv_norm, tn, logits, labels, row_w)
+        ctx.cfg = (temperature, ebd_weight, z_old is not None)
+        ctx.mark_non_differentiable(logits, loss_rows)
+        return loss, logits, loss_rows
+
+    @staticmethod
+    def backward(ctx, gloss, _gl, _gr):
+        z, inv_norm, tn, logits, labels, row_w = ctx.saved_tensors
+        T, w, blended = ctx.cfg
+        dz = ops.l2norm_sim_ce_bwd_rows(z, inv_norm, tn, T, logits, labels, row_w, blended=blended, ebd_weight=w)
+        return dz * gloss, None, None, None, None, None, None
+
+
+def _row_weight_operands(row_weights, robust, contrastive):
+    """a `row_weights=` argument beside the other heads' arguments: they do not combine (raised before anything is launched)"""
+    if robust is not None or contrastive is not None:
+        raise ops.DbmmUnsupported("row_weights= does not combine with robust= or contrastive=: those heads have no per-row weighted form")
+    return row_weights
 
 
 class GroupDRO:
@@ -416,12 +447,17 @@ class CustomCLIP(nn.Module):
         tn = self._text("spurious", features.device)
         return _SimFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5))
 
-    def loss(self, features, labels, use_group=False, spurious=False, robust=None, contrastive=None):
+    def loss(self, features, labels, use_group=False, spurious=False, robust=None, contrastive=None, row_weights=None):
         """fused step body: returns (mean CE, logits, per-row CE); `spurious`: against the spurious-attribute prompts
         (forward_spurious + criterion, final_main.py:764-766).  `robust` = (GroupDRO state, group ids of the batch): the loss is the
         group-DRO robust loss and the state's q is updated in place.  `contrastive` = (weight, temperature): returns (mixed loss,
         logits, per-row CE, L_con) with mixed = (1 - weight) * mean CE + weight * L_con, L_con the supervised-contrastive loss of the
-        trainable adapter's output under `labels`."""
+        trainable adapter's output under `labels`.  `row_weights` (float32 [B] on the device, taken as they
+        are): the loss is (1 / B) sum_b w_b CE_b; logits and per-row CE are the unweighted ones, and a row
+        of weight 0 still takes part in the train-mode BatchNorm statistics."""
+        if row_weights is not None:
+            row_weights = _row_weight_operands(row_weights, robust, contrastive)
+            ops._row_weights("loss", row_weights, features.device, features.shape[0])
         if contrastive is not None:
             contrastive = _contrastive_operands(contrastive, robust)
         z, z_old = self._features(features)
@@ -431,6 +467,8 @@ class CustomCLIP(nn.Module):
         if robust is not None:
             groups, q, eta = _robust_operands(robust, features.shape[0])
             return _SimCERobustFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5), labels, groups, q, eta)
+        if row_weights is not None:
+            return _SimCEWeightedFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5), labels.contiguous(), row_weights)
         return _SimCEFn.apply(z, z_old, tn, self.temperature, getattr(self, "ebd_weight", 0.5), labels)
 
     def _step_adapters(self):
@@ -497,7 +535,7 @@ class CustomCLIP(nn.Module):
             return ops.adapter_train_step_sets(features.detach().contiguous(), plan["args"], plan["H"], sets, scale, tau, group["lr"],
                                                group.get("momentum", 0.0), group.get("weight_decay", 0.0), first)
 
-    def train_step(self, features, labels, optimizer, use_group=False, robust=None, contrastive=None):
+    def train_step(self, features, labels, optimizer, use_group=False, robust=None, contrastive=None, row_weights=None):
         """The whole step body of final_main.py:455-466 / :610-623 -- forward, mean CE, backward and
         the SGD-momentum update -- as ONE C call (~20 launches back to back, no autograd graph, no
         host round trip).  Uses the optimiser's lr / momentum / weight_decay and its
@@ -505,7 +543,11 @@ class CustomCLIP(nn.Module):
         Requires train mode.  Returns (mean CE, logits, per-row CE), all on the device.  `robust` = (GroupDRO state, group ids of
         the batch): the group-DRO step (two launches more) -- the state's q is updated in place, the returned loss is the robust
         loss.  `contrastive` = (weight, temperature): the step with the supervised-contrastive head (three launches more); returns
-        (mixed loss, logits, per-row CE, L_con)."""
+        (mixed loss, logits, per-row CE, L_con).  `row_weights` (float32 [B] on the device, taken as they are): the step minimises
+        and returns (1 / B) sum_b w_b CE_b in ERM's launches; the bits of `loss(..., row_weights=)`, backward, `optimizer.step()`."""
+        if row_weights is not None:
+            row_weights = _row_weight_operands(row_weights, robust, contrastive)
+            ops._row_weights("train_step", row_weights, features.device, features.shape[0])
         if contrastive is not None:
             contrastive = _contrastive_operands(contrastive, robust)
         plan, first = self._plan(optimizer, "train_step")
@@ -516,7 +558,7 @@ class CustomCLIP(nn.Module):
                 features.detach().contiguous(), labels.contiguous(), plan["args"], plan["H"], plan["with_old"],
                 getattr(self, "ebd_weight", 0.5), tn, self.temperature, group["lr"], group.get("momentum", 0.0),
                 group.get("weight_decay", 0.0), first, robust=None if robust is None else _robust_operands(robust, features.shape[0]),
-                contrastive=contrastive)
+                contrastive=contrastive, row_weights=row_weights)
 
 
 class MultipleAdapter(CustomCLIP):
@@ -714,15 +756,18 @@ class SweepAdapters:
             self._args[key] = a
         return a
 
-    def step(self, table, idx, labels, groups, which, lrs, momentum, weight_decay, counts, loss_sum, counted=True, robust=None):
+    def step(self, table, idx, labels, groups, which, lrs, momentum, weight_decay, counts, loss_sum, counted=True, robust=None, row_weights=None):
         """one training step of every replica on rows idx[r] of `table` against the `which` prompts.  Returns (mean CE [R], logits
         [R, B, C], per-row CE [R, B]).  `robust`: a GroupDRO state with q [R, G] over the groups of `groups` -- the group-DRO step of
-        every replica; q is updated in place and the robust losses take the means' place"""
+        every replica; q is updated in place and the robust losses take the means' place.  `row_weights` (float32 [N] / [1, N] shared,
+        or [R, N], over the TABLE's rows): every replica's step under per-row loss weights; the counters stay unweighted"""
         if robust is not None and (not isinstance(robust, GroupDRO) or robust.q.dim() != 2):
             raise TypeError("SweepAdapters.step: robust must be a GroupDRO state built with replicas=R")
+        if row_weights is not None:
+            _row_weight_operands(row_weights, robust, None)
         out = ops.adapter_sweep_step(table, idx, labels, groups, self._call_args(), self.ebd_weight, self.text(which), self.temperature, lrs,
                                      momentum, weight_decay, self.first_step, counts, loss_sum, counted,
-                                     robust=None if robust is None else (robust.q, robust.step_size))
+                                     robust=None if robust is None else (robust.q, robust.step_size), row_weights=row_weights)
         self.first_step = False
         return out
 
@@ -789,10 +834,11 @@ class SweepLinear:
             m.fc.bias.copy_(b[r])
         return m.to(self.device).eval()
 
-    def step(self, table, idx, labels, groups, lrs, momentum, weight_decay, counts, loss_sum, counted=True):
-        """one training step of every replica on rows idx[r] of `table`.  Returns (mean CE [R], logits [R, B, C], per-row CE [R, B])"""
+    def step(self, table, idx, labels, groups, lrs, momentum, weight_decay, counts, loss_sum, counted=True, row_weights=None):
+        """one training step of every replica on rows idx[r] of `table`.  Returns (mean CE [R], logits [R, B, C], per-row CE [R, B]).
+        `row_weights` (float32 [N] / [1, N] shared, or [R, N], over the TABLE's rows): the step under per-row loss weights"""
         out = ops.linear_sweep_step(table, idx, labels, groups, self.w, self.b, self.mom_w, self.mom_b, lrs, momentum, weight_decay,
-                                    self.first_step, counts, loss_sum, counted)
+                                    self.first_step, counts, loss_sum, counted, row_weights=row_weights)
         self.first_step = False
         return out
 

@@ -311,6 +311,20 @@ __device__ __forceinline__ void bwd2_body(const dim3 bi, const dim3 gd, const fl
     }
 }
 
+// per-row loss weights: one workgroup writes L = (1 / B) sum_b loss_rows[b] * row_w[row(b)] -- mean_reduce_kernel's statements (and
+// those of bwd2_body's spare block) over the weighted terms, so all-ones weights give the ERM mean's bits.  row(b) = b, or with `idx`
+// the table row idx[b] clamped into a table of n_tab rows (the sweep's weights are per table row).  `red`: 4 floats of LDS
+__device__ __forceinline__ void weighted_mean_body(const float* __restrict__ loss_rows, const float* __restrict__ row_w, const long long* __restrict__ idx,
+                                                   long long n_tab, int B, float* red, float* __restrict__ loss_mean) {
+#pragma clang fp contract(off)                                           // the rounded terms loss_rows[b] * w, in every kernel that calls this
+    float s = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) s += loss_rows[i] * row_w[idx ? table_row(idx, i, n_tab) : (long long)i];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) *loss_mean = ((red[0] + red[1]) + (red[2] + red[3])) / (float)B;
+}
+
 // train-mode BatchNorm backward, 4 columns x 64 row-lanes per workgroup:
 // dr = sum_ks drpart; dhn = dr * (gamma xhat + beta > 0); dbeta = sum_b dhn; dgamma = sum_b dhn xhat;
 // dh = gamma invstd (dhn - dbeta / B - xhat dgamma / B)

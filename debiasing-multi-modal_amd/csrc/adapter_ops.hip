@@ -229,6 +229,40 @@ __global__ __launch_bounds__(256) void l2norm_sim_ce_fwdbwd_kernel(
     ce_bwd_row<CMAX>(z, inv, w_new, tn, lg, labels, nullptr, invT, gscale, dz, row, lane, D4, C, row);
 }
 
+// ---- per-row loss weights: L = (1 / B) sum_b row_w[b] CE_b (fixed weights: no batch reduction, so ERM's launch count) -------------
+// The siblings of the three kernels above and of mean_reduce_kernel; the only new arithmetic is gscale * row_w[row] and
+// loss_rows[b] * row_w[b], so all-ones weights give the unweighted kernels' bits.  logits / loss_rows stay unweighted.
+template <int CMAX>
+__global__ __launch_bounds__(256) void l2norm_sim_ce_bwd_rows_kernel(
+    const float* __restrict__ z, const float* __restrict__ inv_norm, float w_new, const float* __restrict__ tn,
+    const float* __restrict__ logits, const long long* __restrict__ labels, const float* __restrict__ row_w, float invT, float gscale,
+    float* __restrict__ dz, int B, int D4, int C) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B) return;
+    float lgv[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) lgv[c] = (c < C) ? logits[(long long)row * C + c] : -INFINITY;
+    ce_bwd_row<CMAX>(z, inv_norm[row], w_new, tn, lgv, labels, nullptr, invT, gscale * row_w[row], dz, row, lane, D4, C, row);
+}
+
+template <int CMAX>
+__global__ __launch_bounds__(256) void l2norm_sim_ce_fwdbwd_rows_kernel(
+    const float* __restrict__ z, const float* __restrict__ z_old, float w_old, float w_new, const float* __restrict__ tn,
+    const long long* __restrict__ labels, const float* __restrict__ row_w, float invT, float gscale, float* __restrict__ logits,
+    float* __restrict__ loss_rows, float* __restrict__ dz, int B, int D4, int C) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B) return;
+    float lg[CMAX], inv;
+    ce_fwd_row<CMAX>(z, z_old, w_old, tn, labels, invT, logits, loss_rows, nullptr, nullptr, row, lane, D4, C, lg, inv, row);
+    ce_bwd_row<CMAX>(z, inv, w_new, tn, lg, labels, nullptr, invT, gscale * row_w[row], dz, row, lane, D4, C, row);
+}
+
+__global__ __launch_bounds__(256) void mean_reduce_rows_kernel(const float* __restrict__ x, const float* __restrict__ row_w, int n,
+                                                               float* __restrict__ out) {
+    __shared__ float red[4];
+    weighted_mean_body(x, row_w, nullptr, 0, n, red, out);
+}
+
 // ---- multi-tensor SGD with momentum ---------------------------------------------------------
 struct SgdArgs {
     float* p[16];
@@ -497,6 +531,32 @@ extern "C" int dbmm_l2norm_sim_ce_bwd_weighted(const float* z, const float* inv_
     return DBMM_OK;
 }
 
+extern "C" int dbmm_weighted_mean(const float* x, const float* row_w, float* out, int64_t n, void* stream) {
+    if (!x || !row_w || !out) return DBMM_E_ARG;
+    if (n <= 0 || n > INT32_MAX) return DBMM_E_SHAPE;
+    hipLaunchKernelGGL(mean_reduce_rows_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, row_w, (int)n, out);
+    DBMM_CHECK_LAUNCH();
+    return DBMM_OK;
+}
+
+extern "C" int dbmm_l2norm_sim_ce_bwd_rows(const float* z, const float* inv_norm, float ebd_weight, int blended, const float* tn,
+                                           const float* logits, const int64_t* labels, const float* row_w, float temperature, float grad_scale,
+                                           float* dz, int64_t B, int64_t D, int64_t C, void* stream) {
+    if (!z || !inv_norm || !tn || !dz || !logits || !labels || !row_w) return DBMM_E_ARG;
+    if (B <= 0 || D <= 0 || (D & 3) || C <= 0 || C > 8 || B > INT32_MAX) return DBMM_E_SHAPE;
+    if (!dbmm_aligned16(z) || !dbmm_aligned16(tn) || !dbmm_aligned16(dz)) return DBMM_E_ALIGN;
+    const float w_new = blended ? (1.f - ebd_weight) : 1.f;
+    const float gs = grad_scale / (float)B;
+    const dim3 grid((unsigned)((B + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+    dbmm_with_cmax(C, [&](auto cm) {
+        hipLaunchKernelGGL(l2norm_sim_ce_bwd_rows_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, z, inv_norm, w_new, tn, logits,
+                           (const long long*)labels, row_w, 1.f / temperature, gs, dz, (int)B, (int)(D / 4), (int)C);
+    });
+    DBMM_CHECK_LAUNCH();
+    return DBMM_OK;
+}
+
 static int sgd_impl(int64_t n, float* const* params, const float* const* grads, float* const* bufs, const int64_t* sizes, const int* nsplit,
                     float lr, float momentum, float weight_decay, int first_step, void* stream) {
     if (!params || !grads || !bufs || !sizes) return DBMM_E_ARG;
@@ -643,6 +703,30 @@ int head_ce(const HeadIo& io, float* loss_mean, bool* spare) {
                                   io.dz, io.B, io.D, io.C, io.stream);
 }
 
+// CE under fixed per-row weights `row_w` [B]: head_ce's launches with the row's gradient scale (1 / B) row_w[b] and the mean of
+// loss_rows[b] row_w[b] (fast: by the backward's spare block, which then reads the weights too -- *spare).  logits and loss_rows
+// are ERM's; a row of weight 0 still takes part in the BatchNorm statistics, which ran before the head
+int head_ce_weighted(const HeadIo& io, const float* row_w, float* loss_mean, bool* spare) {
+    *spare = io.fast;
+    const float w_new = io.oz ? (1.f - io.ebd_weight) : 1.f;
+    if (io.fast) {
+        dbmm_with_cmax(io.C, [&](auto cm) {
+            hipLaunchKernelGGL(l2norm_sim_ce_fwdbwd_rows_kernel<decltype(cm)::value>, dim3((unsigned)((io.B + 3) / 4)), dim3(256), 0,
+                               (hipStream_t)io.stream, io.z, io.oz, io.ebd_weight, w_new, io.tn, (const long long*)io.labels, row_w,
+                               1.f / io.temperature, 1.f / (float)io.B, io.logits, io.loss_rows, io.dz, (int)io.B, (int)(io.D / 4), (int)io.C);
+        });
+        DBMM_CHECK_LAUNCH();
+        return DBMM_OK;
+    }
+    int rc = dbmm_l2norm_sim_ce_fwd(io.z, io.oz, io.ebd_weight, io.tn, io.labels, io.temperature, io.logits, io.loss_rows, nullptr, nullptr,
+                                    io.inv_norm, io.B, io.D, io.C, io.stream);
+    if (rc) return rc;
+    rc = dbmm_weighted_mean(io.loss_rows, row_w, loss_mean, io.B, io.stream);
+    if (rc) return rc;
+    return dbmm_l2norm_sim_ce_bwd_rows(io.z, io.inv_norm, io.ebd_weight, io.oz != nullptr, io.tn, io.logits, io.labels, row_w, io.temperature, 1.f,
+                                       io.dz, io.B, io.D, io.C, io.stream);
+}
+
 // group DRO: a row's weight needs the whole batch's losses, so the head is three launches -- forward rows, the group reduction + q
 // update (one workgroup), weighted backward rows; the robust loss is written by the second.  The [3][G] statistics live in `stats`
 // (the start of the backward scratch, unused until then).
@@ -680,8 +764,9 @@ int head_sets(const float* z, float* dz, float scale, float tau, float* loss, fl
 
 // the tail of every step: adapter backward from dz, then SGD.  fast: the batch-split dW1 / db1 partial sums stay in the backward's
 // scratch and are summed inside the SGD launch, and `loss_mean` given has the backward's spare block write the mean of loss_rows
+// (of loss_rows[b] row_w[b] with `row_w`)
 int bwd_sgd(const float* x, const AdapterParams& p, const AdapterMomentum& m, const SgdScalars& sc, float* f, const StepWs& L, bool fast,
-            const float* loss_rows, float* loss_mean, int64_t B, int64_t D, int64_t H, void* stream) {
+            const float* loss_rows, float* loss_mean, int64_t B, int64_t D, int64_t H, void* stream, const float* row_w = nullptr) {
     float* ps[6] = {p.w1, p.b1, p.gamma, p.beta, p.w2, p.b2};
     float* ms[6] = {m.w1, m.b1, m.gamma, m.beta, m.w2, m.b2};
     float* gs[6];
@@ -697,7 +782,7 @@ int bwd_sgd(const float* x, const AdapterParams& p, const AdapterMomentum& m, co
     const BwdScratch S = dbmm_adapter_bwd_scratch(B, D);
     float* scratch = bws + 2 * B * H;
     const int rc = dbmm_adapter_bwd_fast(x, dz, h, mean, invstd, r, p.gamma, p.beta, p.w2, gs[0], gs[1], gs[2], gs[3], gs[4], gs[5], bws + B * H,
-                                         scratch, B, D, (hipStream_t)stream, false, loss_rows, loss_mean);
+                                         scratch, B, D, (hipStream_t)stream, false, loss_rows, loss_mean, row_w);
     if (rc) return rc;
     gs[0] = scratch + S.dw1part;
     gs[1] = scratch + S.db1part;
@@ -706,11 +791,12 @@ int bwd_sgd(const float* x, const AdapterParams& p, const AdapterMomentum& m, co
 }
 
 // `gdro.groups` given: the group-DRO step (q [G] updated in place, loss_mean = the robust loss); `con.loss` given: the ERM step with the
-// supervised-contrastive head on top (loss_mean = the mixed loss); else the ERM step.  `old`: the frozen adapter, or none (w1 null)
+// supervised-contrastive head on top (loss_mean = the mixed loss); `row_w` given: the step under fixed per-row loss weights (loss_mean =
+// (1 / B) sum_b row_w[b] CE_b); else the ERM step.  `old`: the frozen adapter, or none (w1 null)
 int train_step_impl(const float* x, const int64_t* labels, const AdapterParams& p, const AdapterMomentum& m, const FrozenAdapter& old,
                     float ebd_weight, const float* tn, float temperature, const SgdScalars& sc, float* logits, float* loss_rows, float* loss_mean,
                     const GdroHead& gdro, const SupconHead& con, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
-                    void* stream) {
+                    void* stream, const float* row_w = nullptr) {
     if (!x || !labels || !complete(p.forward_only()) || !complete(m) || !tn || !logits || !loss_rows || !loss_mean || !workspace)
         return DBMM_E_ARG;
     const bool with_old = old.w1 != nullptr, with_con = con.loss != nullptr;
@@ -738,9 +824,10 @@ int train_step_impl(const float* x, const int64_t* labels, const AdapterParams& 
     bool spare = false;                      // the loss mean is still to be written, by the backward's spare block
     if (gdro.groups) rc = head_gdro(io, gdro, f + L.bws, loss_mean);
     else if (with_con) rc = head_ce_supcon(io, con, loss_mean, (char*)workspace + step_bytes, cbytes);
+    else if (row_w) rc = head_ce_weighted(io, row_w, loss_mean, &spare);
     else rc = head_ce(io, loss_mean, &spare);
     if (rc) return rc;
-    return bwd_sgd(x, p, m, sc, f, L, fast, spare ? loss_rows : nullptr, spare ? loss_mean : nullptr, B, D, H, stream);
+    return bwd_sgd(x, p, m, sc, f, L, fast, spare ? loss_rows : nullptr, spare ? loss_mean : nullptr, B, D, H, stream, spare ? row_w : nullptr);
 }
 
 }  // namespace
@@ -763,6 +850,25 @@ extern "C" int dbmm_adapter_train_step(const float* x, const int64_t* labels, fl
                            {o_w1, o_b1, o_gamma, o_beta, o_rmean, o_rvar, (long long*)o_nbt, o_w2, o_b2}, ebd_weight, tn, temperature,
                            {lr, momentum, weight_decay, first_step}, logits, loss_rows, loss_mean, {}, {}, B, D, H, C, workspace,
                            workspace_bytes, stream);
+}
+
+// the ERM step under per-row loss weights row_w [B] (fp32, taken as they are): L = (1 / B) sum_b row_w[b] CE_b.  Same workspace and
+// launch count as dbmm_adapter_train_step; logits / loss_rows are the unweighted ones; all-ones weights give that step's bits
+extern "C" int dbmm_adapter_train_step_weighted(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
+                                                float* beta, float* rmean, float* rvar, int64_t* nbt, float* w2, float* b2,
+                                                float* m_w1, float* m_b1, float* m_gamma, float* m_beta, float* m_w2,
+                                                float* m_b2, const float* o_w1, const float* o_b1, const float* o_gamma,
+                                                const float* o_beta, float* o_rmean, float* o_rvar, int64_t* o_nbt,
+                                                const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
+                                                float temperature, float lr, float momentum, float weight_decay,
+                                                int first_step, float* logits, float* loss_rows, float* loss_mean,
+                                                const float* row_w, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
+                                                size_t workspace_bytes, void* stream) {
+    if (!row_w) return DBMM_E_ARG;
+    return train_step_impl(x, labels, {w1, b1, gamma, beta, rmean, rvar, (long long*)nbt, w2, b2}, {m_w1, m_b1, m_gamma, m_beta, m_w2, m_b2},
+                           {o_w1, o_b1, o_gamma, o_beta, o_rmean, o_rvar, (long long*)o_nbt, o_w2, o_b2}, ebd_weight, tn, temperature,
+                           {lr, momentum, weight_decay, first_step}, logits, loss_rows, loss_mean, {}, {}, B, D, H, C, workspace,
+                           workspace_bytes, stream, row_w);
 }
 
 extern "C" int dbmm_adapter_train_step_gdro(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,

@@ -63,7 +63,9 @@ int dbmm_adapter_fwd_fast(const float* x, const float* w1, const float* b1, cons
                           float* z, int64_t B, int64_t D, int train, float eps, float momentum, hipStream_t s);
 // backward: dW2, db2, dgamma, dbeta, dh (left in `dh`) and, with `sum_dw1`, dW1, db1; `scratch` = dbmm_adapter_bwd_scratch(B, D).total floats.
 // !sum_dw1: the batch splits of dW1 / db1 stay in the scratch and the caller (the one-call step) sums them inside its SGD launch, in the
-// same order.  `loss_mean` given: a spare block of the first launch writes the mean of loss_rows [B] to it.
+// same order.  `loss_mean` given: a spare block of the first launch writes the mean of loss_rows [B] to it; with `row_w` [B] (per-row
+// loss weights) that block writes (1 / B) sum_b loss_rows[b] row_w[b] instead.
 int dbmm_adapter_bwd_fast(const float* x, const float* dz, const float* h, const float* mean, const float* invstd, const float* r, const float* gamma,
                           const float* beta, const float* w2, float* dw1, float* db1, float* dgamma, float* dbeta, float* dw2, float* db2,
-                          float* dh, float* scratch, int64_t B, int64_t D, hipStream_t s, bool sum_dw1, const float* loss_rows, float* loss_mean);
+                          float* dh, float* scratch, int64_t B, int64_t D, hipStream_t s, bool sum_dw1, const float* loss_rows, float* loss_mean,
+                          const float* row_w = nullptr);

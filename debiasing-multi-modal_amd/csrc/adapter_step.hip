@@ -59,6 +59,19 @@ __global__ __launch_bounds__(256) void bwd2_kernel(const float* __restrict__ dz,
     bwd2_body(blockIdx, gridDim, dz, r, w2, dw2part, db2part, drpart, B, D, NS, RB, loss_rows, loss_mean);
 }
 
+// the weighted step's first backward launch: bwd2_kernel's blocks, and the spare block writes the WEIGHTED mean of loss_rows
+__global__ __launch_bounds__(256) void bwd2_rows_kernel(const float* __restrict__ dz, const float* __restrict__ r, const float* __restrict__ w2,
+                                                        float* __restrict__ dw2part, float* __restrict__ db2part, float* __restrict__ drpart, int B, int D,
+                                                        int NS, int RB, const float* __restrict__ loss_rows, const float* __restrict__ row_w,
+                                                        float* __restrict__ loss_mean) {
+    __shared__ float red[4];
+    if (blockIdx.x == gridDim.x - 1) {
+        weighted_mean_body(loss_rows, row_w, nullptr, 0, B, red, loss_mean);
+        return;
+    }
+    bwd2_body(blockIdx, gridDim, dz, r, w2, dw2part, db2part, drpart, B, D, NS, RB, nullptr, nullptr);
+}
+
 __global__ __launch_bounds__(256) void bn_bwd_kernel(const float* __restrict__ drpart, int KS, const float* __restrict__ h, const float* __restrict__ mean,
                                                      const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dh, int B,
@@ -104,14 +117,19 @@ int dbmm_adapter_fwd_fast(const float* x, const float* w1, const float* b1, cons
 
 int dbmm_adapter_bwd_fast(const float* x, const float* dz, const float* h, const float* mean, const float* invstd, const float* r, const float* gamma,
                           const float* beta, const float* w2, float* dw1, float* db1, float* dgamma, float* dbeta, float* dw2, float* db2,
-                          float* dh, float* scratch, int64_t B, int64_t D, hipStream_t s, bool sum_dw1, const float* loss_rows, float* loss_mean) {
+                          float* dh, float* scratch, int64_t B, int64_t D, hipStream_t s, bool sum_dw1, const float* loss_rows, float* loss_mean,
+                          const float* row_w) {
     const int KS = (int)(D / 128), nb = (int)((B + TB - 1) / TB);
     const BwdScratch L = dbmm_adapter_bwd_scratch(B, D);
     const int NS = L.NS, RB = L.RB;
     float *drpart = scratch + L.drpart, *dw2part = scratch + L.dw2part, *db2part = scratch + L.db2part, *dw1part = scratch + L.dw1part,
           *db1part = scratch + L.db1part;
-    hipLaunchKernelGGL(bwd2_kernel, dim3((unsigned)(D / 32 * NS + nb * KS + (loss_mean ? 1 : 0))), dim3(256), 0, s, dz, r, w2, dw2part, db2part, drpart,
-                       (int)B, (int)D, NS, RB, loss_rows, loss_mean);
+    if (row_w && loss_mean)
+        hipLaunchKernelGGL(bwd2_rows_kernel, dim3((unsigned)(D / 32 * NS + nb * KS + 1)), dim3(256), 0, s, dz, r, w2, dw2part, db2part, drpart, (int)B,
+                           (int)D, NS, RB, loss_rows, row_w, loss_mean);
+    else
+        hipLaunchKernelGGL(bwd2_kernel, dim3((unsigned)(D / 32 * NS + nb * KS + (loss_mean ? 1 : 0))), dim3(256), 0, s, dz, r, w2, dw2part, db2part, drpart,
+                           (int)B, (int)D, NS, RB, loss_rows, loss_mean);
     DBMM_CHECK_LAUNCH();
     const long long nw4 = D * 128 / 4, nb4 = D / 4;
     hipLaunchKernelGGL(bn_bwd_kernel, dim3((unsigned)(32 + (nw4 + nb4 + 255) / 256)), dim3(256), 0, s, (const float*)drpart, KS, h, mean, invstd, gamma,

@@ -12,7 +12,8 @@
 //   * the per-replica learning rates reach the SGD launch by value.
 // Launches of a step: fc1 partials, BN statistics, fc2 [the same three for a frozen old adapter], CE forward + backward, bwd2,
 // BN backward, bwd1, SGD = 8 (11), whatever R is; the group-DRO step (dbmm_adapter_sweep_step_gdro) has CE forward, group weights +
-// q update, weighted CE backward in place of the one CE launch = 10 (13).  Evaluation: fc1 partials, reduce, fc2 [x 2], CE forward, loss sum = 5 (8).
+// q update, weighted CE backward in place of the one CE launch = 10 (13); the step under per-row loss weights
+// (dbmm_adapter_sweep_step_weighted) has the ERM step's 8 (11).  Evaluation: fc1 partials, reduce, fc2 [x 2], CE forward, loss sum = 5 (8).
 // No float atomics, no order that depends on timing.
 #include "adapter_step.h"
 
@@ -101,6 +102,38 @@ __global__ __launch_bounds__(256) void sweep_ce_fwdbwd_kernel(float* __restrict_
         ce_fwd_row<CMAX>(w + zoff, ozoff >= 0 ? w + ozoff : nullptr, w_old, tn, labels, invT, logits + (long long)r * B * C, loss_rows + (long long)r * B,
                          nullptr, nullptr, row, lane, D4, C, lg, inv, lrow);
         ce_bwd_row<CMAX>(w + zoff, inv, w_new, tn, lg, labels, nullptr, invT, gscale, w + dzoff, row, lane, D4, C, lrow);
+        if (counts && lane == 0) count_row<CMAX>(lg, C, labels[lrow], groups[lrow], G, sc);
+    }
+    if (counts) {
+        __syncthreads();
+        flush_counts(sc, counts + (long long)r * G * 2, G);
+    }
+}
+
+// per-row loss weights: sweep_ce_fwdbwd_kernel with the gradient scale of row b of replica r times row_w[r * w_stride + table row of b]
+// (l2norm_sim_ce_fwdbwd_rows_kernel's two calls); w_stride = 0: one weight vector shared by the replicas, else the table's rows
+template <int CMAX>
+__global__ __launch_bounds__(256) void sweep_ce_fwdbwd_rows_kernel(float* __restrict__ ws, long long ws_stride, long long zoff, long long ozoff,
+                                                                   long long dzoff, float w_old, float w_new, const float* __restrict__ tn,
+                                                                   const long long* __restrict__ labels, const long long* __restrict__ groups,
+                                                                   const long long* __restrict__ idx, long long n_tab, const float* __restrict__ row_w,
+                                                                   long long w_stride, float invT, float gscale, float* __restrict__ logits,
+                                                                   float* __restrict__ loss_rows, unsigned long long* __restrict__ counts, int G, int B,
+                                                                   int D4, int C) {
+    __shared__ unsigned int sc[64][2];
+    const int r = blockIdx.y;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (counts) {
+        if (threadIdx.x < 64) { sc[threadIdx.x][0] = 0; sc[threadIdx.x][1] = 0; }
+        __syncthreads();
+    }
+    if (row < B) {
+        float* w = ws + r * ws_stride;
+        const long long lrow = table_row(idx + (long long)r * B, row, n_tab);
+        float lg[CMAX], inv;
+        ce_fwd_row<CMAX>(w + zoff, ozoff >= 0 ? w + ozoff : nullptr, w_old, tn, labels, invT, logits + (long long)r * B * C, loss_rows + (long long)r * B,
+                         nullptr, nullptr, row, lane, D4, C, lg, inv, lrow);
+        ce_bwd_row<CMAX>(w + zoff, inv, w_new, tn, lg, labels, nullptr, invT, gscale * row_w[r * w_stride + lrow], w + dzoff, row, lane, D4, C, lrow);
         if (counts && lane == 0) count_row<CMAX>(lg, C, labels[lrow], groups[lrow], G, sc);
     }
     if (counts) {
@@ -222,6 +255,25 @@ __global__ __launch_bounds__(256) void sweep_bwd2_kernel(float* __restrict__ ws,
     if (loss_sum && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) loss_sum[r] += (double)loss_mean[r] * (double)B;
 }
 
+// per-row loss weights: sweep_bwd2_kernel whose spare block writes replica r's WEIGHTED loss mean (bwd2_rows_kernel's statements, the
+// weight of batch row b read at its table row) and counts it as sweep_bwd2_kernel counts the mean
+__global__ __launch_bounds__(256) void sweep_bwd2_rows_kernel(float* __restrict__ ws, long long ws_stride, long long dzoff, long long roff,
+                                                              const float* __restrict__ w2, long long dw2p, long long db2p, long long drp, int B, int D,
+                                                              int NS, int RB, const float* __restrict__ loss_rows, const float* __restrict__ row_w,
+                                                              long long w_stride, const long long* __restrict__ idx, long long n_tab,
+                                                              float* __restrict__ loss_mean, double* __restrict__ loss_sum) {
+    __shared__ float red[4];
+    const int r = blockIdx.y;
+    if (blockIdx.x == gridDim.x - 1) {
+        weighted_mean_body(loss_rows + (long long)r * B, row_w + r * w_stride, idx + (long long)r * B, n_tab, B, red, loss_mean + r);
+        if (loss_sum && threadIdx.x == 0) loss_sum[r] += (double)loss_mean[r] * (double)B;
+        return;
+    }
+    float* w = ws + r * ws_stride;
+    bwd2_body(dim3(blockIdx.x, 0, 0), dim3(gridDim.x, 1, 1), w + dzoff, w + roff, w2 + (long long)r * D * 128, w + dw2p, w + db2p, w + drp, B, D, NS, RB,
+              nullptr, nullptr);
+}
+
 __global__ __launch_bounds__(256) void sweep_bn_bwd_kernel(float* __restrict__ ws, long long ws_stride, long long drp, int KS, long long hoff,
                                                            long long moff, long long ioff, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, long long dgoff, long long dboff, long long dhoff, int B,
@@ -330,13 +382,14 @@ extern "C" size_t dbmm_workspace_bytes_adapter_sweep_eval(int64_t R, int64_t B, 
     return (size_t)R * (size_t)eval_layout(B, D, with_old).total * sizeof(float);
 }
 
-// `q` given: the group-DRO step of every replica (q [R][G] updated in place, loss_mean = the robust losses); else the ERM step
+// `q` given: the group-DRO step of every replica (q [R][G] updated in place, loss_mean = the robust losses); `row_w` given: the step
+// under per-row loss weights [Rw][n_rows] over the table's rows, Rw = 1 (shared) or R; else the ERM step
 static int sweep_step_impl(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B, const int64_t* labels,
                            const int64_t* groups, void* const* params, float* const* bufs, void* const* old, float ebd_weight,
                            const float* tn, float temperature, const float* lr, float momentum, float weight_decay, int first_step,
                            float* logits, float* loss_rows, float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted,
                            float* q, float eta, int64_t R, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace, size_t workspace_bytes,
-                           void* stream) {
+                           void* stream, const float* row_w = nullptr, int64_t Rw = 0) {
     if (!table || !idx || !labels || !groups || !tn || !lr || !logits || !loss_rows || !loss_mean || !counts || !loss_sum || !workspace || !bufs)
         return DBMM_E_ARG;
     if (!stack_ok(params) || (old && !stack_ok(old))) return DBMM_E_ARG;
@@ -345,6 +398,8 @@ static int sweep_step_impl(const float* table, int64_t n_rows, const int64_t* id
     int rc = sweep_shape(R, B, D, H, C, G, n_rows, 2);               // B < 2: train-mode BatchNorm1d has no statistics, as in the single step
     if (rc) return rc;
     if (idx_R != R || idx_B != B) return DBMM_E_SHAPE;
+    if (row_w && Rw != 1 && Rw != R) return DBMM_E_SHAPE;
+    const long long w_stride = (row_w && Rw != 1) ? (long long)n_rows : 0;
     const int with_old = old != nullptr;
     if (workspace_bytes < dbmm_workspace_bytes_adapter_sweep_step(R, B, D, H, with_old)) return DBMM_E_WORKSPACE;
     if (!dbmm_aligned16(workspace) || !dbmm_aligned16(table) || !dbmm_aligned16(tn) || !stack_aligned(params) || (old && !stack_aligned(old)))
@@ -397,6 +452,13 @@ static int sweep_step_impl(const float* table, int64_t n_rows, const int64_t* id
                                (const float*)logits, lab, grp, idxl, (long long)n_rows, (int)G, invT, iB, (int)(D / 4), (int)C);
         });
         DBMM_CHECK_LAUNCH();
+    } else if (row_w) {
+        dbmm_with_cmax(C, [&](auto cm) {
+            hipLaunchKernelGGL(sweep_ce_fwdbwd_rows_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, L.dz, ebd_weight, w_new, tn,
+                               lab, grp, idxl, (long long)n_rows, row_w, w_stride, invT, 1.f / (float)B, logits, loss_rows, cnt, (int)G, iB, (int)(D / 4),
+                               (int)C);
+        });
+        DBMM_CHECK_LAUNCH();
     } else {
         dbmm_with_cmax(C, [&](auto cm) {
             hipLaunchKernelGGL(sweep_ce_fwdbwd_kernel<decltype(cm)::value>, grid, dim3(256), 0, s, ws, wst, L.z, L.oz, L.dz, ebd_weight, w_new, tn, lab,
@@ -411,8 +473,14 @@ static int sweep_step_impl(const float* table, int64_t n_rows, const int64_t* id
                     db1p = L.scratch + S.db1part;
     const int nbT = (int)((B + TB - 1) / TB);
     // (group DRO: the robust loss is already written and counted, so the spare loss-mean block is not launched)
-    hipLaunchKernelGGL(sweep_bwd2_kernel, dim3((unsigned)(D / 32 * NS + nbT * KS + (q ? 0 : 1)), iR), dim3(256), 0, s, ws, wst, L.dz, L.r, (const float*)P.w2,
-                       dw2p, db2p, drp, iB, iD, NS, RB, (const float*)loss_rows, q ? nullptr : loss_mean, (counted && !q) ? loss_sum : nullptr);
+    if (row_w)
+        hipLaunchKernelGGL(sweep_bwd2_rows_kernel, dim3((unsigned)(D / 32 * NS + nbT * KS + 1), iR), dim3(256), 0, s, ws, wst, L.dz, L.r, (const float*)P.w2,
+                           dw2p, db2p, drp, iB, iD, NS, RB, (const float*)loss_rows, row_w, w_stride, idxl, (long long)n_rows, loss_mean,
+                           counted ? loss_sum : nullptr);
+    else
+        hipLaunchKernelGGL(sweep_bwd2_kernel, dim3((unsigned)(D / 32 * NS + nbT * KS + (q ? 0 : 1)), iR), dim3(256), 0, s, ws, wst, L.dz, L.r,
+                           (const float*)P.w2, dw2p, db2p, drp, iB, iD, NS, RB, (const float*)loss_rows, q ? nullptr : loss_mean,
+                           (counted && !q) ? loss_sum : nullptr);
     DBMM_CHECK_LAUNCH();
     const long long nw4 = D * 128 / 4, nb4 = D / 4;
     hipLaunchKernelGGL(sweep_bn_bwd_kernel, dim3((unsigned)(32 + (nw4 + nb4 + 255) / 256), iR), dim3(256), 0, s, ws, wst, drp, KS, L.h, L.mean, L.invstd,
@@ -446,6 +514,22 @@ extern "C" int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const
     return sweep_step_impl(table, n_rows, idx, idx_R, idx_B, labels, groups, params, bufs, old, ebd_weight, tn, temperature, lr, momentum, weight_decay,
                            first_step, logits, loss_rows, loss_mean, counts, loss_sum, G, counted, nullptr, 0.f, R, B, D, H, C, workspace, workspace_bytes,
                            stream);
+}
+
+// the ERM step of every replica under per-row loss weights row_w [Rw][n_rows] (fp32, over the TABLE's rows; Rw = 1: shared by the
+// replicas, Rw = R: one vector each): batch row b of replica r weighs row_w[(Rw == 1 ? 0 : r) * n_rows + idx[r][b] clamped].  The
+// workspace and launches of dbmm_adapter_sweep_step; the counters stay unweighted, the counted loss sum adds L * B
+extern "C" int dbmm_adapter_sweep_step_weighted(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B,
+                                                const int64_t* labels, const int64_t* groups, void* const* params, float* const* bufs,
+                                                void* const* old, float ebd_weight, const float* tn, float temperature, const float* lr,
+                                                float momentum, float weight_decay, int first_step, float* logits, float* loss_rows,
+                                                float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted, const float* row_w,
+                                                int64_t Rw, int64_t R, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
+                                                size_t workspace_bytes, void* stream) {
+    if (!row_w) return DBMM_E_ARG;
+    return sweep_step_impl(table, n_rows, idx, idx_R, idx_B, labels, groups, params, bufs, old, ebd_weight, tn, temperature, lr, momentum, weight_decay,
+                           first_step, logits, loss_rows, loss_mean, counts, loss_sum, G, counted, nullptr, 0.f, R, B, D, H, C, workspace, workspace_bytes,
+                           stream, row_w, Rw);
 }
 
 extern "C" int dbmm_adapter_sweep_step_gdro(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B, const int64_t* labels,

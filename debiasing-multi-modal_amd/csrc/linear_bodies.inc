@@ -12,6 +12,9 @@
 //     MODE_STEP     at most 16 slabs; the last block to arrive sums the slabs in slab order and applies the update (one launch)
 //     MODE_PARTIAL  up to 128 slabs, no update: linear_reduce_sgd_body does it, gridded over the C x D quads (two launches)
 //     MODE_EVAL     no gradient: the slab is the block's loss sum, the last arriver writes the mean
+//   WEIGHTED (MODE_STEP / MODE_PARTIAL): per-row loss weights a.row_w, indexed like the labels (batch row, or table row in a sweep): the
+//   softmax-minus-one-hot term is scaled by invB * w where the unweighted form has invB, the loss sums take ce * w; logits and
+//   loss_rows stay unweighted.  All-ones weights give the unweighted bits; the unweighted instantiation has no new operation.
 //   SWEEP adds what a lock-step sweep needs and changes no float operation: batch row b is row idx[b] of a shared table (clamped
 //   into it), read in place, with labels[idx[b]] / groups[idx[b]]; the (n, correct) group counters of the block's rows go to LDS and
 //   from there to the replica's int64 counters (integer atomics: order-free); the thread that writes the loss mean adds
@@ -29,6 +32,7 @@ struct LinArgs {
     float* logits; float* loss_rows; float* loss_mean;
     float* slabs; unsigned* counter;
     int B, D, C, RB;
+    const float* row_w;                   // WEIGHTED: the weights of the rows `labels` indexes; else unused (null)
 };
 
 // what SWEEP adds, per replica: idx == nullptr: batch row b is row b of x / labels / groups (already offset to the first row)
@@ -99,7 +103,7 @@ __device__ __forceinline__ bool arrive_last(unsigned* counter, int* flag, int nb
 
 // lds: W [C][D] while rows run; afterwards the block's dW [C][D] | db [8] | loss, pad (MODE_EVAL: the four wave loss sums)
 //      (CM * NQ * 256 + 16 floats, 16-B aligned); sc: the block's group counters (SWEEP); red: 256 doubles (SWEEP, MODE_EVAL)
-template <int NQ, int CM, int MODE, bool SWEEP>
+template <int NQ, int CM, int MODE, bool SWEEP, bool WEIGHTED = false>
 __device__ __forceinline__ void linear_rows_body(const LinArgs& a, const LinSweepRows& sw, const int bid, const int nblk, float* lds, int* flag,
                                                  unsigned int (*sc)[2], double* red) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -171,7 +175,13 @@ __device__ __forceinline__ void linear_rows_body(const LinArgs& a, const LinSwee
         }
         const float se = 1.f + so;
         const float ce = (m - ly) + log1pf(so);
-        lsum += ce;
+        const float rw = WEIGHTED ? a.row_w[row] : 1.f;
+        if (WEIGHTED) {
+#pragma clang fp contract(off)
+            lsum += ce * rw;                                             // the rounded term ce * w, in every instantiation
+        } else {
+            lsum += ce;
+        }
         if (lane == 0) a.loss_rows[r] = ce;
         float lo = l[0];
 #pragma unroll
@@ -189,16 +199,38 @@ __device__ __forceinline__ void linear_rows_body(const LinArgs& a, const LinSwee
         }
         if (MODE != MODE_EVAL) {
             const float inv = 1.f / se;
+            if (WEIGHTED) {
+                // The unweighted statements (the else branch) with invB * w for invB, written as the operations the compiler makes
+                // of them -- e * inv - onehot is ONE fma, db += t * invB is ONE fma, d itself is the rounded product -- and with
+                // contraction off, so that this instantiation cannot be contracted (or packed) into other roundings: all-ones
+                // weights give the unweighted step's bits, which tests/test_gpu_row_weights.py holds on both launch paths.
+#pragma clang fp contract(off)
+                const float gs = invB * rw;
 #pragma unroll
-            for (int c = 0; c < CM; ++c) {
-                const float d = (e[c] * inv - (c == y ? 1.f : 0.f)) * invB;
-                db[c] += d;
+                for (int c = 0; c < CM; ++c) {
+                    const float t = fmaf(e[c], inv, -(c == y ? 1.f : 0.f));
+                    const float d = t * gs;
+                    db[c] = fmaf(t, gs, db[c]);
 #pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    dw[c][q][0] = fmaf(d, xv[q][0], dw[c][q][0]);
-                    dw[c][q][1] = fmaf(d, xv[q][1], dw[c][q][1]);
-                    dw[c][q][2] = fmaf(d, xv[q][2], dw[c][q][2]);
-                    dw[c][q][3] = fmaf(d, xv[q][3], dw[c][q][3]);
+                    for (int q = 0; q < NQ; ++q) {
+                        dw[c][q][0] = fmaf(d, xv[q][0], dw[c][q][0]);
+                        dw[c][q][1] = fmaf(d, xv[q][1], dw[c][q][1]);
+                        dw[c][q][2] = fmaf(d, xv[q][2], dw[c][q][2]);
+                        dw[c][q][3] = fmaf(d, xv[q][3], dw[c][q][3]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < CM; ++c) {
+                    const float d = (e[c] * inv - (c == y ? 1.f : 0.f)) * invB;
+                    db[c] += d;
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        dw[c][q][0] = fmaf(d, xv[q][0], dw[c][q][0]);
+                        dw[c][q][1] = fmaf(d, xv[q][1], dw[c][q][1]);
+                        dw[c][q][2] = fmaf(d, xv[q][2], dw[c][q][2]);
+                        dw[c][q][3] = fmaf(d, xv[q][3], dw[c][q][3]);
+                    }
                 }
             }
         }

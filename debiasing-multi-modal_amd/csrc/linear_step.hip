@@ -25,23 +25,23 @@ namespace {
 
 #include "linear_bodies.inc"
 
-template <int NQ, int CM, int MODE>
+template <int NQ, int CM, int MODE, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void linear_rows_kernel(const LinArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[CM * NQ * 256 + 16];
     __shared__ int flag;
-    linear_rows_body<NQ, CM, MODE, false>(a, LinSweepRows{}, blockIdx.x, gridDim.x, lds, &flag, nullptr, nullptr);
+    linear_rows_body<NQ, CM, MODE, false, WEIGHTED>(a, LinSweepRows{}, blockIdx.x, gridDim.x, lds, &flag, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(256) void linear_reduce_sgd_kernel(const LinArgs a, int NS) {
     linear_reduce_sgd_body<false>(a, nullptr, NS, blockIdx.x);
 }
 
-template <int MODE>
+template <int MODE, bool WEIGHTED = false>
 int launch_rows(const LinArgs& a, int NS, hipStream_t s) {
     const int NQ = (a.D / 4 + 63) / 64, CM = a.C <= 2 ? 2 : a.C <= 4 ? 4 : 8;
 #define DBMM_LIN_CASE(nq, cm)                                                                                    \
     if (NQ == nq && CM == cm) {                                                                                  \
-        hipLaunchKernelGGL((linear_rows_kernel<nq, cm, MODE>), dim3((unsigned)NS), dim3(256), 0, s, a);         \
+        hipLaunchKernelGGL((linear_rows_kernel<nq, cm, MODE, WEIGHTED>), dim3((unsigned)NS), dim3(256), 0, s, a); \
         DBMM_CHECK_LAUNCH();                                                                                     \
         return DBMM_OK;                                                                                          \
     }
@@ -69,30 +69,49 @@ extern "C" size_t dbmm_workspace_bytes_linear_ce_fwd(int64_t B) {
     return 16 + (size_t)ns * sizeof(float);
 }
 
-extern "C" int dbmm_linear_train_step(const float* x, const int64_t* labels, float* w, float* b, float* m_w, float* m_b, float lr,
-                                      float momentum, float weight_decay, int first_step, float* logits, float* loss_rows, float* loss_mean,
-                                      int64_t B, int64_t D, int64_t C, void* workspace, size_t workspace_bytes, void* stream) {
+// `row_w` given: the step under per-row loss weights [B] (the WEIGHTED kernels), else the ERM step
+static int linear_step_impl(const float* x, const int64_t* labels, float* w, float* b, float* m_w, float* m_b, float lr, float momentum,
+                            float weight_decay, int first_step, float* logits, float* loss_rows, float* loss_mean, const float* row_w, int64_t B,
+                            int64_t D, int64_t C, void* workspace, size_t workspace_bytes, void* stream) {
     if (!x || !labels || !w || !b || !m_w || !m_b || !logits || !loss_rows || !loss_mean || !workspace) return DBMM_E_ARG;
     if (!lin_shape_ok(B, D, C)) return DBMM_E_SHAPE;
     if (!dbmm_aligned16(x) || !dbmm_aligned16(w) || !dbmm_aligned16(m_w) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
     if (workspace_bytes < dbmm_workspace_bytes_linear_train_step(B, D, C)) return DBMM_E_WORKSPACE;
     const hipStream_t s = (hipStream_t)stream;
     LinArgs a{x, (const long long*)labels, w, b, m_w, m_b, lr, momentum, weight_decay, first_step, logits, loss_rows, loss_mean,
-              (float*)((char*)workspace + 16), (unsigned*)workspace, (int)B, (int)D, (int)C, 0};
+              (float*)((char*)workspace + 16), (unsigned*)workspace, (int)B, (int)D, (int)C, 0, row_w};
     int NS;
     if (B <= dbmm_opt(OPT_LINEAR_STEP_ONE_LAUNCH_MAX_B)) {
         split_step1(B, &NS, &a.RB);
         const hipError_t e = hipMemsetAsync(workspace, 0, sizeof(unsigned), s);       // the ticket counter, per call, ahead of the launch
         if (e != hipSuccess) return (int)e;
-        return launch_rows<MODE_STEP>(a, NS, s);
+        return row_w ? launch_rows<MODE_STEP, true>(a, NS, s) : launch_rows<MODE_STEP>(a, NS, s);
     }
     split_step2(B, &NS, &a.RB);
-    const int rc = launch_rows<MODE_PARTIAL>(a, NS, s);
+    const int rc = row_w ? launch_rows<MODE_PARTIAL, true>(a, NS, s) : launch_rows<MODE_PARTIAL>(a, NS, s);
     if (rc != DBMM_OK) return rc;
     const int items = (int)(C * D / 4) + 1;
     hipLaunchKernelGGL(linear_reduce_sgd_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a, NS);
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
+}
+
+extern "C" int dbmm_linear_train_step(const float* x, const int64_t* labels, float* w, float* b, float* m_w, float* m_b, float lr,
+                                      float momentum, float weight_decay, int first_step, float* logits, float* loss_rows, float* loss_mean,
+                                      int64_t B, int64_t D, int64_t C, void* workspace, size_t workspace_bytes, void* stream) {
+    return linear_step_impl(x, labels, w, b, m_w, m_b, lr, momentum, weight_decay, first_step, logits, loss_rows, loss_mean, nullptr, B, D, C,
+                            workspace, workspace_bytes, stream);
+}
+
+// the step under per-row loss weights row_w [B] (fp32, taken as they are): L = (1 / B) sum_b row_w[b] CE_b.  Same workspace and launches
+// as dbmm_linear_train_step; logits / loss_rows are the unweighted ones; all-ones weights give that step's bits
+extern "C" int dbmm_linear_train_step_weighted(const float* x, const int64_t* labels, float* w, float* b, float* m_w, float* m_b, float lr,
+                                               float momentum, float weight_decay, int first_step, float* logits, float* loss_rows,
+                                               float* loss_mean, const float* row_w, int64_t B, int64_t D, int64_t C, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    if (!row_w) return DBMM_E_ARG;
+    return linear_step_impl(x, labels, w, b, m_w, m_b, lr, momentum, weight_decay, first_step, logits, loss_rows, loss_mean, row_w, B, D, C,
+                            workspace, workspace_bytes, stream);
 }
 
 extern "C" int dbmm_linear_ce_fwd(const float* x, const float* w, const float* b, const int64_t* labels, float* logits, float* loss_rows,

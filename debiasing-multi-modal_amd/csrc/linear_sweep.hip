@@ -40,6 +40,7 @@ struct LinSweepArgs {
     unsigned* counter;                    // R ticket counters
     unsigned long long* counts; double* loss_sum; int G;
     int B, D, C, RB;
+    const float* row_w; long long w_stride;   // per-row loss weights over the table's rows (null: none); replica r's at row_w + r * w_stride
 };
 
 __device__ __forceinline__ LinArgs replica_args(const LinSweepArgs& s, int r) {
@@ -51,21 +52,22 @@ __device__ __forceinline__ LinArgs replica_args(const LinSweepArgs& s, int r) {
     return LinArgs{s.x, s.labels, s.w + r * CD, s.b + r * s.C, s.mw ? s.mw + r * CD : nullptr, s.mb ? s.mb + r * s.C : nullptr,
                    lr, s.mu, s.wd, s.first,
                    s.logits + (long long)r * s.B * s.C, s.loss_rows + (long long)r * s.B, s.loss_mean ? s.loss_mean + r : nullptr,
-                   s.slabs ? s.slabs + r * s.slab_stride : nullptr, s.counter + r, s.B, s.D, s.C, s.RB};
+                   s.slabs ? s.slabs + r * s.slab_stride : nullptr, s.counter + r, s.B, s.D, s.C, s.RB,
+                   s.row_w ? s.row_w + r * s.w_stride : nullptr};
 }
 __device__ __forceinline__ LinSweepRows replica_rows(const LinSweepArgs& s, int r) {
     return LinSweepRows{s.idx ? s.idx + r * s.idx_stride : nullptr, s.n_tab, s.groups,
                         s.counts ? s.counts + (long long)r * s.G * 2 : nullptr, s.G, s.loss_sum ? s.loss_sum + r : nullptr};
 }
 
-template <int NQ, int CM, int MODE>
+template <int NQ, int CM, int MODE, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void linear_sweep_rows_kernel(const LinSweepArgs s) {
     __shared__ __attribute__((aligned(16))) float lds[CM * NQ * 256 + 16];
     __shared__ int flag;
     __shared__ unsigned int sc[64][2];
     __shared__ double red[MODE == MODE_EVAL ? 256 : 1];
     const int r = blockIdx.y;
-    linear_rows_body<NQ, CM, MODE, true>(replica_args(s, r), replica_rows(s, r), blockIdx.x, gridDim.x, lds, &flag, sc, red);
+    linear_rows_body<NQ, CM, MODE, true, WEIGHTED>(replica_args(s, r), replica_rows(s, r), blockIdx.x, gridDim.x, lds, &flag, sc, red);
 }
 
 __global__ __launch_bounds__(256) void linear_sweep_reduce_sgd_kernel(const LinSweepArgs s, int NS) {
@@ -73,12 +75,12 @@ __global__ __launch_bounds__(256) void linear_sweep_reduce_sgd_kernel(const LinS
     linear_reduce_sgd_body<true>(replica_args(s, r), s.loss_sum ? s.loss_sum + r : nullptr, NS, blockIdx.x);
 }
 
-template <int MODE>
+template <int MODE, bool WEIGHTED = false>
 int launch_sweep_rows(const LinSweepArgs& a, int NS, int R, hipStream_t s) {
     const int NQ = (a.D / 4 + 63) / 64, CM = a.C <= 2 ? 2 : a.C <= 4 ? 4 : 8;
 #define DBMM_LIN_CASE(nq, cm)                                                                                               \
     if (NQ == nq && CM == cm) {                                                                                             \
-        hipLaunchKernelGGL((linear_sweep_rows_kernel<nq, cm, MODE>), dim3((unsigned)NS, (unsigned)R), dim3(256), 0, s, a); \
+        hipLaunchKernelGGL((linear_sweep_rows_kernel<nq, cm, MODE, WEIGHTED>), dim3((unsigned)NS, (unsigned)R), dim3(256), 0, s, a); \
         DBMM_CHECK_LAUNCH();                                                                                                \
         return DBMM_OK;                                                                                                     \
     }
@@ -114,17 +116,19 @@ extern "C" size_t dbmm_workspace_bytes_linear_sweep_eval(int64_t R, int64_t B) {
     return (size_t)R * 16;
 }
 
-extern "C" int dbmm_linear_sweep_step(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B, const int64_t* labels,
-                                      const int64_t* groups, float* w, float* b, float* m_w, float* m_b, const float* lr, float momentum,
-                                      float weight_decay, int first_step, float* logits, float* loss_rows, float* loss_mean, int64_t* counts,
-                                      double* loss_sum, int64_t G, int counted, int64_t R, int64_t B, int64_t D, int64_t C, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
+// `row_w` given: the step under per-row loss weights [Rw][n_rows] over the table's rows, Rw = 1 (shared) or R; else the ERM step
+static int linear_sweep_step_impl(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B, const int64_t* labels,
+                                  const int64_t* groups, float* w, float* b, float* m_w, float* m_b, const float* lr, float momentum,
+                                  float weight_decay, int first_step, float* logits, float* loss_rows, float* loss_mean, int64_t* counts,
+                                  double* loss_sum, int64_t G, int counted, const float* row_w, int64_t Rw, int64_t R, int64_t B, int64_t D,
+                                  int64_t C, void* workspace, size_t workspace_bytes, void* stream) {
     if (!table || !idx || !labels || !groups || !w || !b || !m_w || !m_b || !lr || !logits || !loss_rows || !loss_mean || !counts || !loss_sum ||
         !workspace)
         return DBMM_E_ARG;
     const int rc = sweep_shape(R, B, D, C, G, n_rows);
     if (rc) return rc;
     if (idx_R != R || idx_B != B) return DBMM_E_SHAPE;
+    if (row_w && Rw != 1 && Rw != R) return DBMM_E_SHAPE;
     if (!dbmm_aligned16(table) || !dbmm_aligned16(w) || !dbmm_aligned16(m_w) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
     if (workspace_bytes < dbmm_workspace_bytes_linear_sweep_step(R, B, D, C)) return DBMM_E_WORKSPACE;
     const hipStream_t s = (hipStream_t)stream;
@@ -139,20 +143,44 @@ extern "C" int dbmm_linear_sweep_step(const float* table, int64_t n_rows, const 
     a.counter = (unsigned*)workspace;
     a.counts = counted ? (unsigned long long*)counts : nullptr; a.loss_sum = counted ? loss_sum : nullptr; a.G = (int)G;
     a.B = (int)B; a.D = (int)D; a.C = (int)C;
+    a.row_w = row_w; a.w_stride = (row_w && Rw != 1) ? (long long)n_rows : 0;
     int NS;
     if (B <= dbmm_opt(OPT_LINEAR_STEP_ONE_LAUNCH_MAX_B)) {
         split_step1(B, &NS, &a.RB);
         const hipError_t e = hipMemsetAsync(workspace, 0, (size_t)R * sizeof(unsigned), s);      // the R ticket counters, per call
         if (e != hipSuccess) return (int)e;
-        return launch_sweep_rows<MODE_STEP>(a, NS, (int)R, s);
+        return row_w ? launch_sweep_rows<MODE_STEP, true>(a, NS, (int)R, s) : launch_sweep_rows<MODE_STEP>(a, NS, (int)R, s);
     }
     split_step2(B, &NS, &a.RB);
-    const int rc2 = launch_sweep_rows<MODE_PARTIAL>(a, NS, (int)R, s);
+    const int rc2 = row_w ? launch_sweep_rows<MODE_PARTIAL, true>(a, NS, (int)R, s) : launch_sweep_rows<MODE_PARTIAL>(a, NS, (int)R, s);
     if (rc2 != DBMM_OK) return rc2;
     const int items = (int)(C * D / 4) + 1;
     hipLaunchKernelGGL(linear_sweep_reduce_sgd_kernel, dim3((unsigned)((items + 255) / 256), (unsigned)R), dim3(256), 0, s, a, NS);
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
+}
+
+extern "C" int dbmm_linear_sweep_step(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B, const int64_t* labels,
+                                      const int64_t* groups, float* w, float* b, float* m_w, float* m_b, const float* lr, float momentum,
+                                      float weight_decay, int first_step, float* logits, float* loss_rows, float* loss_mean, int64_t* counts,
+                                      double* loss_sum, int64_t G, int counted, int64_t R, int64_t B, int64_t D, int64_t C, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    return linear_sweep_step_impl(table, n_rows, idx, idx_R, idx_B, labels, groups, w, b, m_w, m_b, lr, momentum, weight_decay, first_step, logits,
+                                  loss_rows, loss_mean, counts, loss_sum, G, counted, nullptr, 0, R, B, D, C, workspace, workspace_bytes, stream);
+}
+
+// every replica's step under per-row loss weights row_w [Rw][n_rows] (fp32, over the TABLE's rows; Rw = 1: shared, Rw = R: one vector
+// each), indexed like the labels: batch row b of replica r weighs row_w[(Rw == 1 ? 0 : r) * n_rows + idx[r][b] clamped].  The workspace
+// and launches of dbmm_linear_sweep_step; the counters stay unweighted, the counted loss sum adds L * B
+extern "C" int dbmm_linear_sweep_step_weighted(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B,
+                                               const int64_t* labels, const int64_t* groups, float* w, float* b, float* m_w, float* m_b,
+                                               const float* lr, float momentum, float weight_decay, int first_step, float* logits,
+                                               float* loss_rows, float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted,
+                                               const float* row_w, int64_t Rw, int64_t R, int64_t B, int64_t D, int64_t C, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    if (!row_w) return DBMM_E_ARG;
+    return linear_sweep_step_impl(table, n_rows, idx, idx_R, idx_B, labels, groups, w, b, m_w, m_b, lr, momentum, weight_decay, first_step, logits,
+                                  loss_rows, loss_mean, counts, loss_sum, G, counted, row_w, Rw, R, B, D, C, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dbmm_linear_sweep_eval(const float* table, int64_t n_rows, const int64_t* idx, int64_t row0, const int64_t* labels,

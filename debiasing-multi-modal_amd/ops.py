@@ -726,6 +726,55 @@ def l2norm_sim_ce_bwd_weighted(z, inv_norm, tn, temperature, logits, labels, gro
     return dz
 
 
+def _row_weights(what, w, dev, n, R=None):
+    """per-row loss weights as the library will index them: float32, contiguous, on the rows' device; `n` elements for a single
+    step, or with `R` (a sweep) [n] / [1, n] (shared by the replicas) or [R, n] over the table's rows.  Returns Rw (1 or R).  No sync."""
+    if not isinstance(w, torch.Tensor):
+        raise _lib.DbmmError(f"{what}: row_weights must be a float32 tensor on the device, got {type(w).__name__}")
+    require_cuda(w)
+    if w.device != dev:
+        raise _lib.DbmmError(f"{what}: row_weights are on {w.device}, the rows on {dev}")
+    _f32c(w)
+    if R is None:
+        if w.dim() != 1:
+            raise _lib.DbmmError(f"{what}: row_weights must be [B], got {tuple(w.shape)}")
+        _sized(f"{what} row_weights", w, n)
+        return 1
+    if w.dim() == 1:
+        _sized(f"{what} row_weights", w, n)
+        return 1
+    if w.dim() != 2 or w.shape[1] != n or w.shape[0] not in (1, R):
+        raise _lib.DbmmError(f"{what}: row_weights must be [{n}], [1, {n}] or [{R}, {n}] over the table's rows, got {tuple(w.shape)}")
+    return w.shape[0]
+
+
+def weighted_mean(x, row_w):
+    """(sum_i x[i] row_w[i]) / n in the order of l2norm_sim_ce_fwd's loss mean (dbmm_weighted_mean); 0-dim"""
+    require_cuda(x)
+    _f32c(x)
+    _row_weights("weighted_mean", row_w, x.device, x.numel())
+    out = _empty((), device=x.device, dtype=torch.float32)
+    check(_lib.lib().dbmm_weighted_mean(ptr(x), ptr(row_w), ptr(out), x.numel(), stream()), "weighted_mean")
+    return out
+
+
+def l2norm_sim_ce_bwd_rows(z, inv_norm, tn, temperature, logits, labels, row_w, blended=False, ebd_weight=0.5, grad_scale=1.0):
+    """dz of (1 / B) sum_b row_w[b] CE_b (dbmm_l2norm_sim_ce_bwd_rows): l2norm_sim_ce_bwd's fused path under per-row weights [B]"""
+    require_cuda(z, inv_norm, tn, logits, labels)
+    _f32c(z)
+    B, D = z.shape
+    C = tn.shape[0]
+    _sized("l2norm_sim_ce_bwd_rows inv_norm", inv_norm, B)
+    _sized("l2norm_sim_ce_bwd_rows logits", logits, B * C)
+    _sized("l2norm_sim_ce_bwd_rows labels", labels, B)
+    _row_weights("l2norm_sim_ce_bwd_rows", row_w, z.device, B)
+    dz = _empty(tuple(z.shape), device=z.device, dtype=z.dtype)
+    check(_lib.lib().dbmm_l2norm_sim_ce_bwd_rows(ptr(z), ptr(inv_norm), float(ebd_weight), int(blended), ptr(tn), ptr(logits), ptr(labels),
+                                                 ptr(row_w), float(temperature), float(grad_scale), ptr(dz), B, D, C, stream()),
+          "l2norm_sim_ce_bwd_rows")
+    return dz
+
+
 SUPCON_MAX_B = 2048
 
 
@@ -939,15 +988,19 @@ def group_loss_sum(loss_rows, g, sums):
     return sums
 
 
-def adapter_step_launches(B, D, H, with_old=False, robust=False, contrastive=False):
+def adapter_step_launches(B, D, H, with_old=False, robust=False, contrastive=False, weighted=False):
     """kernel launches of one dbmm_adapter_train_step call on the purpose-built kernels (csrc/adapter_step.hip): forward 3
     (K-split fc1, BatchNorm statistics, BatchNorm + ReLU + fc2; 3 more for a frozen old adapter), cosine logits + CE forward
     and backward in one, backward 3 (dW2 / dr + the loss mean, BatchNorm backward + dW2 sums, dW1), SGD (+ dW1 sums); None for
     shapes that take the general GEMM kernel (H != 128 or D % 128 != 0).  `robust` (dbmm_adapter_train_step_gdro): 2 more -- the
     head is forward rows, group reduction + q update, weighted backward rows, and the loss needs no launch of the backward.
-    `contrastive` (dbmm_adapter_train_step_supcon): 3 more -- Gram tiles, the reduction + the mixed loss, the contrastive backward"""
+    `contrastive` (dbmm_adapter_train_step_supcon): 3 more -- Gram tiles, the reduction + the mixed loss, the contrastive backward.
+    `weighted` (dbmm_adapter_train_step_weighted): none more -- fixed per-row weights need no batch reduction, the head and the
+    backward's spare block read them in the launches ERM has"""
     if H != 128 or D % 128 or not get_option("adapter_step_fused"):
         return None
+    if weighted and (robust or contrastive):
+        raise DbmmUnsupported("adapter_step_launches: per-row weights do not combine with group DRO or the contrastive head")
     return 8 + (3 if with_old else 0) + (2 if robust else 0) + (3 if contrastive else 0)
 
 
@@ -960,11 +1013,12 @@ def adapter_step_args(new, bufs, old):
 
 
 def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature, lr, momentum, weight_decay, first_step, robust=None,
-                       contrastive=None):
+                       contrastive=None, row_weights=None):
     """one fused training-step body (dbmm_adapter_train_step); `args` from adapter_step_args().  `robust` = (groups int64 [B], q
     float32 [G], eta): the group-DRO step (dbmm_adapter_train_step_gdro) -- q is updated in place, the returned loss is the robust
     loss.  `contrastive` = (weight, tau): the step with the supervised-contrastive head (dbmm_adapter_train_step_supcon); returns
-    (mixed loss, logits, per-row CE, L_con)."""
+    (mixed loss, logits, per-row CE, L_con).  `row_weights` float32 [B]: the step under per-row loss weights
+    (dbmm_adapter_train_step_weighted) -- the returned loss is (1 / B) sum_b w_b CE_b, logits and per-row CE are the unweighted ones."""
     if not (x.is_cuda and labels.is_cuda and tn.is_cuda):
         require_cuda(x, labels, tn)
     _f32c(x)
@@ -976,6 +1030,10 @@ def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature
             raise DbmmUnsupported("adapter_train_step: the contrastive head and group DRO do not combine")
         if B > SUPCON_MAX_B:
             raise DbmmUnsupported(f"adapter_train_step: B = {B}; the contrastive head serves 2 <= B <= {SUPCON_MAX_B}")
+    if row_weights is not None:
+        if robust is not None or contrastive is not None:
+            raise DbmmUnsupported("adapter_train_step: per-row weights do not combine with group DRO or the contrastive head")
+        _row_weights("adapter_train_step", row_weights, dev, B)
     L = _lib.lib()
     ws = _cached_ws(_step_ws, 8, (dev.index, B, D, H, with_old, contrastive is not None), dev, _step_ws_bytes)
     logits = _empty((B, C), device=dev, dtype=torch.float32)
@@ -989,6 +1047,8 @@ def adapter_train_step(x, labels, args, H, with_old, ebd_weight, tn, temperature
         groups, q, eta = robust
         step, name = L.dbmm_adapter_train_step_gdro, "adapter_train_step_gdro"
         head = (groups.data_ptr(), q.data_ptr(), float(eta), _gdro_operands(groups, q, B))
+    elif row_weights is not None:
+        step, name, head = L.dbmm_adapter_train_step_weighted, "adapter_train_step_weighted", (row_weights.data_ptr(),)
     else:
         step, name, head = L.dbmm_adapter_train_step, "adapter_train_step", ()
     # the 36 arguments every head shares, the head's own, the shape and the workspace
@@ -1072,12 +1132,14 @@ def _sweep_metrics(counts, loss_sum, R):
 
 
 def adapter_sweep_step(table, idx, labels, groups, args, ebd_weight, tn, temperature, lrs, momentum, weight_decay, first_step, counts, loss_sum,
-                       counted=True, robust=None):
+                       counted=True, robust=None, row_weights=None):
     """one training step of R replicas in the launches of one (dbmm_adapter_sweep_step): replica r trains on rows idx[r] of `table`
     ([N, D] fp32; labels / groups int64 [N]); `args` from adapter_sweep_args(); `lrs` R host floats; counts int64 [R, G, 2] and
     loss_sum float64 [R] are accumulated in place when `counted`.  Returns (mean CE [R], logits [R, B, C], per-row CE [R, B]).
     `robust` = (q float32 [R, G], eta): the group-DRO step of every replica (dbmm_adapter_sweep_step_gdro) over the groups of
-    `groups` (G = counts.shape[1] <= 8) -- q is updated in place, the robust losses take the means' place."""
+    `groups` (G = counts.shape[1] <= 8) -- q is updated in place, the robust losses take the means' place.  `row_weights` float32
+    [N] / [1, N] (shared) or [R, N] over the TABLE's rows: the step under per-row loss weights (dbmm_adapter_sweep_step_weighted) --
+    the losses returned and counted are (1 / B) sum_b w CE_b, the counters and per-row CE stay unweighted."""
     R, D, H = args["R"], args["D"], args["H"]
     if args["Bf"] is None:
         raise _lib.DbmmError("adapter sweep step: adapter_sweep_args() was built without momentum buffers")
@@ -1105,6 +1167,11 @@ def adapter_sweep_step(table, idx, labels, groups, args, ebd_weight, tn, tempera
         if _gdro_operands(groups, q, None, R) != G:
             raise _lib.DbmmError(f"adapter sweep step: q {tuple(q.shape)} for counters of {G} groups")
         step, name, head = L.dbmm_adapter_sweep_step_gdro, "adapter_sweep_step_gdro", (q.data_ptr(), float(eta))
+    if row_weights is not None:
+        if robust is not None:
+            raise DbmmUnsupported("adapter sweep step: per-row weights do not combine with group DRO")
+        Rw = _row_weights("adapter sweep step", row_weights, dev, table.shape[0], R)
+        step, name, head = L.dbmm_adapter_sweep_step_weighted, "adapter_sweep_step_weighted", (row_weights.data_ptr(), Rw)
     rc = step(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(), args["P"], args["Bf"], args["O"],
               float(ebd_weight), tn.data_ptr(), float(temperature), LR, float(momentum), float(weight_decay), int(first_step), logits.data_ptr(),
               loss.data_ptr(), loss.data_ptr() + 4 * R * B, counts.data_ptr(), loss_sum.data_ptr(), G, int(counted), *head, R, B, D, H, C,
@@ -1178,22 +1245,27 @@ def _linear_operands(x, labels, w, b, extra=()):
     return B, D, C
 
 
-def linear_train_step(x, labels, w, b, m_w, m_b, lr, momentum, weight_decay, first_step):
+def linear_train_step(x, labels, w, b, m_w, m_b, lr, momentum, weight_decay, first_step, row_weights=None):
     """one fused linear-probe training step (dbmm_linear_train_step): w, b, m_w, m_b updated in place.
-    Returns (mean CE 0-dim, logits [B, C], per-row CE [B]), all on the device."""
+    Returns (mean CE 0-dim, logits [B, C], per-row CE [B]), all on the device.  `row_weights` float32 [B]: the step under per-row
+    loss weights (dbmm_linear_train_step_weighted) -- the loss is (1 / B) sum_b w_b CE_b, logits and per-row CE stay unweighted."""
     B, D, C = _linear_operands(x, labels, w, b, (m_w, m_b))
     if m_w.shape != w.shape or m_b.shape != b.shape:
         raise _lib.DbmmError(f"linear probe: momentum buffers {tuple(m_w.shape)}, {tuple(m_b.shape)} for w {tuple(w.shape)}, b {tuple(b.shape)}")
     dev = x.device
     L = _lib.lib()
+    step, name, head = L.dbmm_linear_train_step, "linear_train_step", ()
+    if row_weights is not None:
+        _row_weights("linear_train_step", row_weights, dev, B)
+        step, name, head = L.dbmm_linear_train_step_weighted, "linear_train_step_weighted", (row_weights.data_ptr(),)
     ws = _linear_workspace(dev, L.dbmm_workspace_bytes_linear_train_step(B, D, C))
     logits = _empty((B, C), device=dev, dtype=torch.float32)
     loss = _empty((B + 1,), device=dev, dtype=torch.float32)        # per-row losses, then their mean: one allocation
-    rc = L.dbmm_linear_train_step(x.data_ptr(), labels.data_ptr(), w.data_ptr(), b.data_ptr(), m_w.data_ptr(), m_b.data_ptr(),
-                                  float(lr), float(momentum), float(weight_decay), int(first_step), logits.data_ptr(),
-                                  loss.data_ptr(), loss.data_ptr() + 4 * B, B, D, C, ws.data_ptr(), ws.numel() * 4, stream())
+    rc = step(x.data_ptr(), labels.data_ptr(), w.data_ptr(), b.data_ptr(), m_w.data_ptr(), m_b.data_ptr(),
+              float(lr), float(momentum), float(weight_decay), int(first_step), logits.data_ptr(),
+              loss.data_ptr(), loss.data_ptr() + 4 * B, *head, B, D, C, ws.data_ptr(), ws.numel() * 4, stream())
     if rc:
-        check(rc, "linear_train_step")
+        check(rc, name)
     return loss[B], logits, loss[:B]
 
 
@@ -1235,11 +1307,13 @@ def _linear_sweep_operands(table, labels, groups, w, b, extra=()):
     return R, C, D
 
 
-def linear_sweep_step(table, idx, labels, groups, w, b, m_w, m_b, lrs, momentum, weight_decay, first_step, counts, loss_sum, counted=True):
+def linear_sweep_step(table, idx, labels, groups, w, b, m_w, m_b, lrs, momentum, weight_decay, first_step, counts, loss_sum, counted=True,
+                      row_weights=None):
     """one training step of R linear probes in the launches of one (dbmm_linear_sweep_step): replica r trains on rows idx[r] of
     `table` ([N, D] fp32; labels / groups int64 [N]); w / m_w [R, C, D] and b / m_b [R, C] are updated in place; `lrs` R host floats;
     counts int64 [R, G, 2] and loss_sum float64 [R] are accumulated in place when `counted`.  Returns (mean CE [R], logits
-    [R, B, C], per-row CE [R, B])."""
+    [R, B, C], per-row CE [R, B]).  `row_weights` float32 [N] / [1, N] (shared) or [R, N] over the TABLE's rows: the step under
+    per-row loss weights (dbmm_linear_sweep_step_weighted)."""
     R, C, D = _linear_sweep_operands(table, labels, groups, w, b, (m_w, m_b))
     if m_w.shape != w.shape or m_b.shape != b.shape:
         raise _lib.DbmmError(f"linear sweep: momentum buffers {tuple(m_w.shape)}, {tuple(m_b.shape)} for w {tuple(w.shape)}, b {tuple(b.shape)}")
@@ -1258,12 +1332,16 @@ def linear_sweep_step(table, idx, labels, groups, w, b, m_w, m_b, lrs, momentum,
     logits = _empty((R, B, C), device=dev, dtype=torch.float32)
     loss = _empty((R * (B + 1),), device=dev, dtype=torch.float32)      # the R x B per-row losses, then the R means: one allocation
     LR = (ctypes.c_float * R)(*[float(v) for v in lrs])
-    rc = L.dbmm_linear_sweep_step(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(),
-                                  w.data_ptr(), b.data_ptr(), m_w.data_ptr(), m_b.data_ptr(), LR, float(momentum), float(weight_decay),
-                                  int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * R * B, counts.data_ptr(),
-                                  loss_sum.data_ptr(), G, int(counted), R, B, D, C, ws.data_ptr(), ws.numel() * 4, stream())
+    step, name, head = L.dbmm_linear_sweep_step, "linear_sweep_step", ()
+    if row_weights is not None:
+        Rw = _row_weights("linear sweep step", row_weights, dev, table.shape[0], R)
+        step, name, head = L.dbmm_linear_sweep_step_weighted, "linear_sweep_step_weighted", (row_weights.data_ptr(), Rw)
+    rc = step(table.data_ptr(), table.shape[0], idx.data_ptr(), idx.shape[0], B, labels.data_ptr(), groups.data_ptr(),
+              w.data_ptr(), b.data_ptr(), m_w.data_ptr(), m_b.data_ptr(), LR, float(momentum), float(weight_decay),
+              int(first_step), logits.data_ptr(), loss.data_ptr(), loss.data_ptr() + 4 * R * B, counts.data_ptr(),
+              loss_sum.data_ptr(), G, int(counted), *head, R, B, D, C, ws.data_ptr(), ws.numel() * 4, stream())
     if rc:
-        check(rc, "linear_sweep_step")
+        check(rc, name)
     return loss[R * B:], logits, loss[:R * B].view(R, B)
 
 

@@ -73,6 +73,123 @@ def _loader_base_seed():
     torch.empty((), dtype=torch.int64).random_()
 
 
+def weighted_sampler_order(weights):
+    """Index order of one `DataLoader(dataset, sampler=WeightedRandomSampler(weights, len(weights), replacement=True))` epoch, drawn
+    from the global torch RNG like torch.utils.data does: the iterator's base seed, then torch.multinomial over the float64 weights
+    (WeightedRandomSampler.__iter__ with no generator of its own)."""
+    w = torch.as_tensor(np.asarray(weights, dtype=np.float64), dtype=torch.double)
+    _loader_base_seed()
+    return torch.multinomial(w, len(w), True)
+
+
+def failure_weights(y, wrong, correct_class_bias=True, reweighting_by_class=False):
+    """The reference's GetResampledWeightsCE (demo/visualizer_supcon.py:1642-1703) restated: float64 [N] sampling weights that
+    up-sample, per class, the rows predicted wrong (`wrong` bool [N]; its "negatives") to the number predicted right (its
+    "positives") -- weight n_right / n_wrong on the wrong rows of a class unless it has more wrong than right rows --, then correct
+    the class imbalance the up-sampling introduced: with imbal = n_major / n_minor and reweighted = right_major / right_minor, the
+    minority class's rows are multiplied by reweighted / imbal when imbal < reweighted (`correct_class_bias`), or by reweighted itself
+    (`reweighting_by_class`, whatever the comparison says).  The defaults are what final_main.py:870-871 sets.  Two departures, where
+    the reference divides by zero: a class without wrong rows keeps weight 1, and the correction is skipped when a class has no
+    right rows.  Binary labels {0, 1} with both classes present, else ValueError."""
+    y = np.asarray(y).astype(np.int64).ravel()
+    wrong = np.asarray(wrong).astype(bool).ravel()
+    if y.shape != wrong.shape:
+        raise ValueError(f"failure_weights: {y.shape[0]} labels for {wrong.shape[0]} flags")
+    if not np.array_equal(np.unique(y), [0, 1]):
+        raise ValueError(f"failure_weights covers two classes (labels 0 and 1, both present), got {np.unique(y).tolist()}")
+    weights = np.ones(len(y))
+    num_cls, num_pos = {}, {}
+    for c in (0, 1):
+        n_pos, n_neg = int((~wrong & (y == c)).sum()), int((wrong & (y == c)).sum())
+        num_cls[c], num_pos[c] = n_pos + n_neg, n_pos
+        if n_neg and n_pos >= n_neg:
+            weights[wrong & (y == c)] = n_pos / n_neg
+    if (correct_class_bias or reweighting_by_class) and num_pos[0] and num_pos[1]:
+        major, minor = (1, 0) if num_cls[0] < num_cls[1] else (0, 1)
+        imbal = num_cls[major] / num_cls[minor]
+        reweighted = num_pos[major] / num_pos[minor]
+        if reweighting_by_class:
+            weights[y == minor] = weights[y == minor] * (reweighted / 1)
+        elif imbal < reweighted:
+            weights[y == minor] = weights[y == minor] * (reweighted / imbal)
+    return weights
+
+
+def jtt_weights(wrong, lambda_up):
+    """JTT's second-stage weights (Liu et al. 2021): `lambda_up` on the rows of the error set, 1 elsewhere; float64 [N]"""
+    return np.where(np.asarray(wrong).astype(bool).ravel(), float(lambda_up), 1.0)
+
+
+def zero_shot_failures(table, text_embedding_dir, temperature):
+    """bool [N] (numpy): the rows of `table` CLIP's zero-shot prediction gets wrong -- `table.y_pred != targets` when the table
+    carries y_pred, else the argmax of the fused kernel's logits of the raw embeddings against the class prompts"""
+    if table.y_pred is not None:
+        return (table.y_pred != table.targets).cpu().numpy()
+    tn = ops.text_colnorm(adapter.get_text_embedding(text_embedding_dir).to(table.device).float().contiguous())
+    pred = ops.l2norm_sim_ce_fwd(table.embeddings, tn, temperature, want_loss=False, want_pred=True)[3]
+    return (pred != table.targets).cpu().numpy()
+
+
+def normalise_row_weights(weights, n_rows, replicas=1):
+    """given per-row weights -> float64 [Rw, n_rows] of mean 1 per row of weights (w * N / sum(w), on the host), Rw = 1 or `replicas`.
+    Non-finite, negative, all-zero weights or a wrong shape raise ValueError."""
+    w = np.asarray(weights, dtype=np.float64)
+    if w.ndim == 1:
+        w = w[None]
+    if w.ndim != 2 or w.shape[1] != n_rows or w.shape[0] not in (1, replicas):
+        want = f"[{n_rows}]" if replicas == 1 else f"[{n_rows}] or [{replicas}, {n_rows}]"
+        raise ValueError(f"row_weights: {want} weights over the train table expected, got shape {np.shape(weights)}")
+    if not np.isfinite(w).all():
+        raise ValueError("row_weights: non-finite weights")
+    if (w < 0).any():
+        raise ValueError("row_weights: negative weights")
+    tot = w.sum(axis=1, keepdims=True)
+    if (tot <= 0).any():
+        raise ValueError("row_weights: all weights are zero")
+    return w * n_rows / tot
+
+
+class _RowWeights:
+    """the schedule's per-row weights over the train table: `mode` "loss" / "sample", `host` float64 [Rw, N] of mean 1, and -- once
+    `upload`ed, in "loss" mode -- `dev` float32 [Rw, N] on the table's device"""
+
+    def __init__(self, mode, host):
+        self.mode, self.host, self.dev = mode, host, None
+
+    def upload(self, device):
+        if self.mode == "loss":
+            self.dev = torch.from_numpy(self.host.astype(np.float32)).contiguous().to(device)
+        return self
+
+    def of(self, r):
+        """replica r's float64 weights"""
+        return self.host[r if self.host.shape[0] > 1 else 0]
+
+
+def _row_weight_option(opt, n_train, replicas=1, zs_failures=None):
+    """opt.row_weights / opt.row_weight_mode (read with getattr) as a _RowWeights over a train table of `n_train` rows, or None when
+    off.  Runs on the host: `zs_failures()` -> (y, wrong) is only called for the string "zs_failures".  Raises DbmmUnsupported beside
+    opt.robust / opt.contrastive_weight and ValueError for a bad mode or bad weights; opt.resample_ce plays no part (a no-op, as in
+    the reference)."""
+    given = getattr(opt, "row_weights", None)
+    if given is None:
+        return None
+    mode = getattr(opt, "row_weight_mode", "loss") or "loss"
+    if mode not in ("loss", "sample"):
+        raise ValueError(f"row_weight_mode must be 'loss' or 'sample', got {mode!r}")
+    if bool(getattr(opt, "robust", False)):
+        raise ops.DbmmUnsupported("opt.row_weights and opt.robust do not combine: the group-DRO head has no per-row weighted form")
+    if _contrastive_option(opt) is not None:
+        raise ops.DbmmUnsupported("opt.row_weights and opt.contrastive_weight do not combine: the contrastive head has no per-row weighted form")
+    if isinstance(given, str):
+        if given != "zs_failures":
+            raise ValueError(f"row_weights must be None, 'zs_failures' or an array over the train table, got {given!r}")
+        if zs_failures is None:
+            raise ValueError("row_weights='zs_failures' needs the train table")
+        given = failure_weights(*zs_failures())
+    return _RowWeights(mode, normalise_row_weights(given, n_train, replicas))
+
+
 def _epoch_order(n, shuffle, indices):
     """row order of one loader pass over `indices` (n of them; None: rows 0 .. n-1), int64"""
     if shuffle:
@@ -110,7 +227,8 @@ def _scores(table, c, loss_sum, n, ratio=None):
 
 # One loader pass of an epoch, as the schedule describes it to an executor.  `rows`: per replica the row subset of `table` the pass
 # runs over (None: the whole table); `counted`: the pass adds to the epoch's loss sum and group counters.
-_Pass = namedtuple("_Pass", "table rows shuffle batch_size use_group counted")
+# `weights`: a _RowWeights over `table` (train-table passes of a schedule with opt.row_weights), else None.
+_Pass = namedtuple("_Pass", "table rows shuffle batch_size use_group counted weights", defaults=(None,))
 
 
 def _pass_rows(p, r=0):
@@ -130,7 +248,9 @@ def _train_passes(classifier, optimizer, target, passes, lr_hook, robust=None, q
     epoch's row order).  `robust` (an adapter.GroupDRO state): every step is a group-DRO step over the table's group ids -- also on
     the group-prompt passes --, the loss summed is the robust loss; `q_log` (a list) receives q after each pass.  `contrastive` = (weight,
     temperature): every step is the mixed step (CustomCLIP.train_step(contrastive=)) under the labels its CE uses, the loss summed is
-    the mixed loss; `con_log` (a list) receives the sum of L_con x rows over the counted passes."""
+    the mixed loss; `con_log` (a list) receives the sum of L_con x rows over the counted passes.  A pass with `weights` (whole-table
+    passes only): in "loss" mode every step is the weighted step under the weights of its rows and the loss summed is L * B; in
+    "sample" mode the row order is weighted_sampler_order's draw and the steps are plain."""
     classifier.train()
     dev = passes[0].table.device
     counts = torch.zeros((passes[0].table.n_groups, 2), dtype=torch.int64, device=dev)
@@ -138,7 +258,14 @@ def _train_passes(classifier, optimizer, target, passes, lr_hook, robust=None, q
     con_sum = torch.zeros((), dtype=torch.float64, device=dev) if contrastive is not None else None
     order, qs = [], []
     for p in passes:
-        batches = _epoch_batches(_pass_rows(p), p.batch_size, p.shuffle, None if p.rows is None else p.rows[0])
+        wdev = None
+        if p.weights is not None and p.weights.mode == "sample":
+            drawn = weighted_sampler_order(p.weights.of(0))
+            batches = [drawn[i:i + p.batch_size] for i in range(0, len(drawn), p.batch_size)]
+        else:
+            batches = _epoch_batches(_pass_rows(p), p.batch_size, p.shuffle, None if p.rows is None else p.rows[0])
+            if p.weights is not None:
+                wdev = p.weights.dev[0]
         for step, idx in enumerate(batches):
             idx = idx.to(dev, non_blocking=True)
             emb, labels, groups = p.table.batch(idx, target)
@@ -152,6 +279,8 @@ def _train_passes(classifier, optimizer, target, passes, lr_hook, robust=None, q
                 loss, logits, _, con = classifier.train_step(emb, labels, optimizer, p.use_group, contrastive=contrastive)
                 if p.counted:
                     con_sum += con.double() * idx.numel()
+            elif wdev is not None:
+                loss, logits, _ = classifier.train_step(emb, labels, optimizer, p.use_group, row_weights=wdev[idx])
             else:
                 loss, logits, _ = classifier.train_step(emb, labels, optimizer, p.use_group)
             if p.counted:
@@ -280,6 +409,15 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
           supervised-contrastive loss of the trainable adapter's output under the labels the pass's CE uses (group ids on a
           group-prompt pass); a pass counts the mixed loss; the train records carry `con`, the row-weighted
           average of L_con; linear_probing, a sweep and opt.robust raise.
+      opt.row_weights (a build-side addition; read with getattr, default None = off): per-row weights over the TRAIN table -- an
+          array [N] (a sweep also takes [R, N]) or the string "zs_failures" = failure_weights of zero_shot_failures of the train
+          table, the reference's dead --resample_ce weights (:868-884).  Rescaled once, on the host in float64, to mean 1 over the
+          table, then cast to fp32.  opt.row_weight_mode "loss" (default): every step of a train-table pass minimises (1 / B) sum_b
+          w_b CE_b, a pass counts L * B, the group counters stay unweighted; "sample": every train-table pass
+          draws weighted_sampler_order (a WeightedRandomSampler loader) in place of the shuffle and takes plain steps.  The reg
+          passes on the val half (adapter_reg, stage 2 of the seq methods) stay unweighted.  All methods, single runs and sweeps;
+          with opt.robust or opt.contrastive_weight it raises DbmmUnsupported, bad weights raise ValueError, both before a model is
+          built.  opt.resample_ce alone stays the no-op it is in the reference.
 
     Random streams are consumed like the reference does (global torch RNG: parameter initialisation and DataLoader orders; global
     numpy RNG: balance_val) through ex.streams.run(r, ...), so the same seeds give the same initial weights and batches.  Returns per
@@ -304,6 +442,10 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
         ex.contrastive = contrastive
     streams = ex.streams
     dev = train_table.device
+    row_w = _row_weight_option(opt, len(train_table), R, lambda: (train_table.targets.cpu().numpy(),
+                                                                   zero_shot_failures(train_table, opt.text_embedding_dir, opt.zs_temperature)))
+    if row_w is not None:
+        row_w.upload(dev)
     D = input_dim or train_table.embeddings.shape[1]
     reg_idx = val_idx = None
     if has_reg:                                                           # load_*_embeddings: stratified 50/50 split of the val split
@@ -360,7 +502,7 @@ def _run_schedule(ex, opts, train_table, val_table, test_table, input_dim=None, 
         hook = lambda i, n: each(lambda r: warmup(opts[r], warm_epoch, i, n, lrs[r]))     # restarts with each loader of the epoch
         passes, extra = [], {}
         if not stage2:
-            passes.append(_Pass(train_table, None, True, opt.batch_size, False, True))
+            passes.append(_Pass(train_table, None, True, opt.batch_size, False, True, row_w))
         if stage2 or method == "adapter_reg":
             use_group = (epoch % 2) == 0 if method == "adapter_reg_seq_alter" else not opt.use_cls_prompt_in_reg
             if balanced is not None:                                     # DataLoader(balanced_subset, shuffle=False, batch_size=adjusted)
@@ -593,6 +735,71 @@ def train_all_epochs(opt, train_table, val_table, test_table, input_dim=None, lo
     return out[0]
 
 
+def train_jtt(opt, train_table, val_table, test_table, log=None):
+    """Just Train Twice (Liu et al. 2021), the label-free baseline, as one run: an identification model of the method's own kind
+    (`linear_probing`: LinearClassifier; the adapter methods: CustomCLIP(Adapter)) takes opt.jtt_epochs (T, default 1) plain
+    train_epochs on the train table under the schedule's learning-rate rule (adjust_learning_rate per epoch, warm-up per step); its
+    eval-mode predictions on the whole train table give the error set (no random draw); then train_all_epochs runs on a copy of `opt`
+    with row_weights = jtt_weights(error set, opt.jtt_lambda (default 5)) -- in opt.row_weight_mode, "loss" by default.  The global
+    random streams are consumed in that order (identification model's initialisation, its T loader orders, then the second stage's
+    own draws), so a seed fixes the run.  opt.row_weights must be unset; opt.robust / opt.contrastive_weight raise as in the
+    schedule, before a model is built.  Single runs only (a JTT sweep: train_sweep with [R, N] weights).
+
+    Returns train_all_epochs' result plus the error set (bool [N] numpy): ((best train, best val, best test), (zero-shot class,
+    zero-shot spurious), wrong).  `log` (a list) receives the identification model's records first (`init`, one `jtt_identify` per
+    epoch, then `jtt_errors` with `wrong`, `n_wrong` and `rng_state` = the (torch, numpy) stream states the second stage starts
+    from), then train_all_epochs' records."""
+    if opt.tl_method not in _METHODS:
+        raise ValueError(f"train_jtt covers linear_probing and the adapter methods, not tl_method={opt.tl_method!r}")
+    if getattr(opt, "row_weights", None) is not None:
+        raise ValueError("train_jtt sets opt.row_weights itself (jtt_weights of the error set); leave it unset")
+    T, lam = int(getattr(opt, "jtt_epochs", 1)), float(getattr(opt, "jtt_lambda", 5.0))
+    if T < 1 or not np.isfinite(lam) or lam <= 0:
+        raise ValueError(f"train_jtt: jtt_epochs >= 1 and a finite jtt_lambda > 0 expected, got {T}, {lam}")
+    probe = copy(opt)
+    probe.row_weights = np.ones(len(train_table))
+    _row_weight_option(probe, len(train_table))                            # the schedule's refusals, before a model is built
+    rec = (lambda **k: log.append(k)) if log is not None else (lambda **k: None)
+    dev = train_table.device
+    D = train_table.embeddings.shape[1]
+    linear = opt.tl_method == "linear_probing"
+    if linear:
+        model = adapter.LinearClassifier(D, opt.n_cls)
+    else:
+        model = adapter.CustomCLIP(adapter.Adapter(D, opt.adapter_feat_dim), opt.text_embedding_dir, opt.text_spurious_embedding_dir,
+                                   opt.text_group_embedding_dir, temperature=opt.zs_temperature)
+    rec(kind="init", state={k: v.clone() for k, v in (model if linear else model.adapter).state_dict().items()})
+    model = model.to(dev)
+    optimizer = O.set_optimizer(opt, model)
+    for epoch in range(1, T + 1):
+        O.adjust_learning_rate(opt, optimizer, epoch)
+        st = {}
+        loss, acc, gacc = train_epoch(train_table, model, optimizer, opt.batch_size, target=opt.train_target,
+                                      lr_hook=lambda i, n: O.warmup_learning_rate(opt, epoch, i, n, optimizer), stats=st)
+        rec(kind="jtt_identify", epoch=epoch, loss=loss, acc=acc, group_acc=gacc, counts=st["counts"], order=st["order"])
+    wrong = prediction_errors(train_table, model, target=opt.train_target)
+    rec(kind="jtt_errors", wrong=wrong, n_wrong=int(wrong.sum()), rng_state=(torch.get_rng_state(), np.random.get_state()))
+    second = copy(opt)
+    second.row_weights = jtt_weights(wrong, lam)
+    out = train_all_epochs(second, train_table, val_table, test_table, log=log)
+    return out + (wrong,)
+
+
+@torch.no_grad()
+def prediction_errors(table, classifier, target="class", batch_size=4096):
+    """bool [N] (numpy): the rows of `table` whose eval-mode prediction (argmax of the logits, the first maximum) differs from the
+    `target` label; in-order batches, no random draw.  Leaves the classifier in eval mode."""
+    classifier.eval()
+    labels = table.labels(target)
+    wrong = []
+    for i in range(0, len(table), batch_size):
+        idx = torch.arange(i, min(i + batch_size, len(table)), device=table.device)
+        emb, y, _ = table.batch(idx, target)
+        logits = classifier.loss(emb, y)[1]
+        wrong.append(logits.argmax(1) != y)
+    return torch.cat(wrong).cpu().numpy()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # seed sweeps (run_multiple/final_main_iteration_wb.py, final_main_iteration_ca.py): R runs in lock-step, one launch for all
 # ---------------------------------------------------------------------------------------------------------------------
@@ -619,6 +826,20 @@ class ReplicaStreams:
             self.states[r] = (torch.get_rng_state(), np.random.get_state())
 
 
+def _with_replica_weights(opts, n_replicas, first):
+    """`opts`, the namespaces of replicas first, first + 1, ... of a sweep of `n_replicas`, with per-replica weights cut to their own
+    rows: opt.row_weights of shape [n_replicas, N] becomes rows first : first + len(opts) on copies of the namespaces (one row,
+    [N], for a replica that runs alone).  Anything else -- unset, "zs_failures", [N], [1, N] -- is shared: `opts` as they are."""
+    given = getattr(opts[0], "row_weights", None)
+    if given is None or isinstance(given, str) or np.ndim(given) != 2 or n_replicas < 2 or np.shape(given)[0] != n_replicas:
+        return list(opts)
+    rows = np.asarray(given)[first:first + len(opts)]
+    out = [copy(o) for o in opts]
+    for o in out:
+        o.row_weights = rows[0] if len(opts) == 1 else rows
+    return out
+
+
 def _sweep_replicas(opt, seeds, learning_rates):
     """(opt of the replica, seed) pairs, learning-rate-major like final_main_iteration_ca.py's loops"""
     if learning_rates is None:
@@ -643,13 +864,14 @@ class _Lr:
 
 
 def _sweep_train_pass(streams, sweep, table, orders_fn, batch_size, target, use_group, lr_fn, momentum, weight_decay, counted=True, acc=None,
-                      sync=True, robust=None):
+                      sync=True, robust=None, row_weights=None):
     """one loader pass of every replica: `orders_fn(r)` draws replica r's row order (under its own streams), all orders go to the
     device in ONE upload, then n_steps batched steps; lr_fn(step, n_steps) -> the R learning rates.  `sweep`: SweepAdapters (scored on
     the group prompts when `use_group`, else the class prompts) or SweepLinear.  `counted`: the pass adds to the loss sums and group
     counters; `acc` = (counts, loss sums) device tensors of an epoch made of several passes (fresh ones if None).  Returns (counts
     [R, G, 2] numpy, loss sums [R] numpy, orders, acc) after the pass's one host sync; the two arrays are None without `sync`.
-    `robust`: an adapter.GroupDRO state with q [R, G] -- every step is a group-DRO step over the table's group ids."""
+    `robust`: an adapter.GroupDRO state with q [R, G] -- every step is a group-DRO step over the table's group ids.  `row_weights`:
+    float32 [Rw, N] on the device over the table's rows -- every step is the weighted step."""
     R, dev = sweep.R, table.device
     linear = isinstance(sweep, adapter.SweepLinear)
     orders = [streams.run(r, orders_fn, r) for r in range(R)]
@@ -672,6 +894,8 @@ def _sweep_train_pass(streams, sweep, table, orders_fn, batch_size, target, use_
     labels = table.targets_group if use_group else table.labels(target)
     prompts = () if linear else ("group" if use_group else "class",)
     extra = {} if robust is None else {"robust": robust}
+    if row_weights is not None:
+        extra["row_weights"] = row_weights
     for i, b in enumerate(steps):
         sweep.step(table.embeddings, b, labels, table.targets_group, *prompts, lr_fn(i, len(steps)), momentum, weight_decay, counts, loss_sum,
                    counted=counted, **extra)
@@ -741,8 +965,14 @@ class _LockStep:
         acc, orders, qs = None, [], []
         for k, p in enumerate(passes):                                   # the passes of an epoch share the accumulators: one host sync
             order_fn = lambda r, p=p: _epoch_order(_pass_rows(p, r), p.shuffle, None if p.rows is None else p.rows[r])
+            wdev = None
+            if p.weights is not None and p.weights.mode == "sample":     # the replica's own WeightedRandomSampler loader, under its streams
+                order_fn = lambda r, p=p: weighted_sampler_order(p.weights.of(r))
+            elif p.weights is not None:
+                wdev = p.weights.dev
             c, ls, o, acc = _sweep_train_pass(self.streams, self.sweep, p.table, order_fn, p.batch_size, opt.train_target, p.use_group, lr_fn,
-                                              opt.momentum, opt.weight_decay, counted=p.counted, acc=acc, sync=k == len(passes) - 1, robust=self.dro)
+                                              opt.momentum, opt.weight_decay, counted=p.counted, acc=acc, sync=k == len(passes) - 1, robust=self.dro,
+                                              row_weights=wdev)
             orders.append(o)
             if self.dro is not None:
                 qs.append(self.dro.q.clone())
@@ -817,15 +1047,16 @@ def train_sweep(opt, train_table, val_table, test_table, seeds, learning_rates=N
         batched = len(replicas) >= 2 and opt.adapter_feat_dim == 128 and D % 128 == 0 and bool(ops.get_option("adapter_step_fused"))
     out = []
     if not batched:
-        for o, s in replicas:
+        for k, (o, s) in enumerate(replicas):
             O.set_seed(s)
             lg = [] if log is not None else None
-            out.append(train_all_epochs(o, train_table, val_table, test_table, log=lg))
+            out.append(train_all_epochs(_with_replica_weights([o], len(replicas), k)[0], train_table, val_table, test_table, log=lg))
             if log is not None:
                 log.append(lg)
         return out
     for i in range(0, len(replicas), 16):
         opts, group_seeds = zip(*replicas[i:i + 16])
+        opts = _with_replica_weights(opts, len(replicas), i)
         out += _run_schedule(_LockStep(opts, group_seeds), opts, train_table, val_table, test_table, log=log)
     return out
 

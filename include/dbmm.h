@@ -744,6 +744,53 @@ int dbmm_linear_sweep_eval(const float* table, int64_t n_rows, const int64_t* id
                            int64_t* counts, double* loss_sum, int64_t G, int64_t R, int64_t B, int64_t D, int64_t C,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-row loss weights: L = (1 / B) sum_b row_w[b] CE_b -------------------------------------------------------------------
+ * row_w is fp32 and taken as it is (no normalisation; the schedule rescales to mean 1 once, on the host).  Every entry is its
+ * unweighted sibling with the row's gradient scale (1 / B) row_w[b] where that one has 1 / B and the mean taken over the terms
+ * loss_rows[b] * row_w[b] in the sibling's order: the same launch count, workspace, shape / alignment rules and error codes, and
+ * all-ones weights give the sibling's bits (parameters, momenta, running statistics, logits, loss_rows, loss).  logits and loss_rows
+ * are the UNWEIGHTED ones; a row of weight 0 still takes part in train-mode BatchNorm statistics.  No float atomics; same bits on
+ * every call.
+ *   dbmm_weighted_mean               out = (sum_i x[i] row_w[i]) / n, one workgroup (the order of dbmm_l2norm_sim_ce_fwd's loss_mean)
+ *   dbmm_l2norm_sim_ce_bwd_rows      dbmm_l2norm_sim_ce_bwd's fused path (logits + labels given) with row_w [B]
+ *   dbmm_adapter_train_step_weighted dbmm_adapter_train_step with row_w [B]; workspace = dbmm_workspace_bytes_adapter_train_step
+ *   dbmm_linear_train_step_weighted  dbmm_linear_train_step with row_w [B], on both of its launch paths
+ *   dbmm_adapter_sweep_step_weighted, dbmm_linear_sweep_step_weighted
+ *       the sweep steps with row_w [Rw][n_rows] over the TABLE's rows, Rw = 1 (shared by the replicas) or R (else DBMM_E_SHAPE):
+ *       batch row b of replica r weighs row_w[(Rw == 1 ? 0 : r) * n_rows + idx[r][b] clamped into the table], the clamp the labels
+ *       use.  The group counters stay unweighted; counted != 0 adds (double)L[r] * B to loss_sum[r]. */
+int dbmm_weighted_mean(const float* x, const float* row_w, float* out, int64_t n, void* stream);
+int dbmm_l2norm_sim_ce_bwd_rows(const float* z, const float* inv_norm, float ebd_weight, int blended, const float* tn,
+                                const float* logits, const int64_t* labels, const float* row_w, float temperature,
+                                float grad_scale, float* dz, int64_t B, int64_t D, int64_t C, void* stream);
+int dbmm_adapter_train_step_weighted(const float* x, const int64_t* labels, float* w1, float* b1, float* gamma,
+                                     float* beta, float* rmean, float* rvar, int64_t* nbt, float* w2, float* b2,
+                                     float* m_w1, float* m_b1, float* m_gamma, float* m_beta, float* m_w2,
+                                     float* m_b2, const float* o_w1, const float* o_b1, const float* o_gamma,
+                                     const float* o_beta, float* o_rmean, float* o_rvar, int64_t* o_nbt,
+                                     const float* o_w2, const float* o_b2, float ebd_weight, const float* tn,
+                                     float temperature, float lr, float momentum, float weight_decay,
+                                     int first_step, float* logits, float* loss_rows, float* loss_mean,
+                                     const float* row_w, int64_t B, int64_t D, int64_t H, int64_t C, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int dbmm_adapter_sweep_step_weighted(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B,
+                                     const int64_t* labels, const int64_t* groups, void* const* params, float* const* bufs,
+                                     void* const* old, float ebd_weight, const float* tn, float temperature, const float* lr,
+                                     float momentum, float weight_decay, int first_step, float* logits, float* loss_rows,
+                                     float* loss_mean, int64_t* counts, double* loss_sum, int64_t G, int counted,
+                                     const float* row_w, int64_t Rw, int64_t R, int64_t B, int64_t D, int64_t H, int64_t C,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int dbmm_linear_train_step_weighted(const float* x, const int64_t* labels, float* w, float* b, float* m_w, float* m_b,
+                                    float lr, float momentum, float weight_decay, int first_step, float* logits,
+                                    float* loss_rows, float* loss_mean, const float* row_w, int64_t B, int64_t D, int64_t C,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int dbmm_linear_sweep_step_weighted(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B,
+                                    const int64_t* labels, const int64_t* groups, float* w, float* b, float* m_w, float* m_b,
+                                    const float* lr, float momentum, float weight_decay, int first_step, float* logits,
+                                    float* loss_rows, float* loss_mean, int64_t* counts, double* loss_sum, int64_t G,
+                                    int counted, const float* row_w, int64_t Rw, int64_t R, int64_t B, int64_t D, int64_t C,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* out[i][:] = table[idx[i]][:] -- batch assembly from a device-resident embedding table
  * (replaces the DataLoader + per-item DataFrame lookups of data/ *_embeddings*.py) */
 int dbmm_gather_rows(const float* table, const int64_t* idx, float* out, int64_t n_rows,
