@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void group_count_kernel(const float* __restric
     if (b < B) {
         int am = 0; float mx = logits[(long long)b * C];
         for (int c = 1; c < C; ++c) { const float v = logits[(long long)b * C + c]; if (v > mx) { mx = v; am = c; } }
-        const int gi = (int)g[b];
+        const long long gi = g[b];                 // compared as 64 bits: an id of 2^32 + 1 is outside [0, G), not group 1
         if (gi >= 0 && gi < G) {
             atomicAdd(&sc[gi][0], 1u);
             if ((long long)am == y[b]) atomicAdd(&sc[gi][1], 1u);
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(256) void group_loss_sum_kernel(const float* __rest
     __shared__ float red[256];
     for (int gi = 0; gi < G; ++gi) {
         float s = 0.f;
-        for (int b = threadIdx.x; b < B; b += 256) if ((int)g[b] == gi) s += loss[b];
+        for (int b = threadIdx.x; b < B; b += 256) if (g[b] == (long long)gi) s += loss[b];
         red[threadIdx.x] = s;
         __syncthreads();
         for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }

@@ -140,10 +140,35 @@ def _sized(name, t, n):
         raise RuntimeError(f"{name}: {t.numel()} elements where the kernels will index {n}")
 
 
-def _f32c(t):
+def _f32c(t, name=None):
     if t.dtype != torch.float32 or not t.is_contiguous():
-        raise _lib.DbmmError(f"expected a contiguous float32 tensor, got {t.dtype} contiguous={t.is_contiguous()}")
+        what = f"{name} {tuple(t.shape)}: " if name else ""
+        raise _lib.DbmmError(f"{what}expected a contiguous float32 tensor, got {t.dtype} contiguous={t.is_contiguous()}")
     return t
+
+
+def _operand(name, t, dtype, shape):
+    """an operand the library only sees as a pointer: on the device, contiguous, of the dtype the kernel reads and of exactly the
+    shape (a tuple) or element count (an int) it will index -- an int32 tensor read as int64, or a short one, is a stray read,
+    not an error the library can see"""
+    require_cuda(t)
+    fits = t.numel() == shape if isinstance(shape, int) else tuple(t.shape) == tuple(shape)
+    if t.dtype != dtype or not t.is_contiguous() or not fits:
+        want = f"{shape} elements" if isinstance(shape, int) else f"shape {tuple(shape)}"
+        raise _lib.DbmmError(f"{name}: expected a contiguous {dtype} tensor of {want}, got {t.dtype} {tuple(t.shape)} "
+                             f"contiguous={t.is_contiguous()}")
+    return t
+
+
+def _patch_image_check(name, x, P, Kp=None):
+    # the library gets B, R, P and a pointer and reads B * 3 * R * R elements: another channel count or a non-square image
+    # fails here like the reference's conv1 / `x + self.positional_embedding` (clip/model.py:224-229), not as a read past the batch
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or P <= 0 or x.shape[2] % P:
+        raise RuntimeError(f"{name}: image batch of shape {tuple(x.shape)} where the patch kernel reads [B, 3, R, R] with R a multiple "
+                           f"of the patch size {P}")
+    if Kp is not None and (Kp < 3 * P * P or Kp % 8):
+        raise RuntimeError(f"{name}: padded patch length Kp = {Kp} for images of shape {tuple(x.shape)}: it must be a multiple of 8 "
+                           f"(aligned vector stores) and at least 3 * {P} * {P} = {3 * P * P}")
 
 
 def split_planes(w):
@@ -563,11 +588,18 @@ def mha_core(qkv, B, L, E, heads, causal, qkv_absmax=None):
     return out
 
 
-def embed_gather(tokens, table, pos):
-    require_cuda(tokens, table)
+def _embed_gather_check(name, tokens, table, pos):
+    require_cuda(tokens, table, pos)
+    _f32c(table, f"{name} table"); _f32c(pos, f"{name} pos")
+    if tokens.dim() != 2 or table.dim() != 2:
+        raise RuntimeError(f"{name}: tokens {tuple(tokens.shape)} and table {tuple(table.shape)} where [n, L] ids and a [vocab, W] table are expected")
     if tokens.dtype != torch.int32:
         tokens = tokens.to(torch.int32)
-    tokens = tokens.contiguous()
+    return tokens.contiguous()
+
+
+def embed_gather(tokens, table, pos):
+    tokens = _embed_gather_check("embed_gather", tokens, table, pos)
     n, L = tokens.shape
     W = table.shape[1]
     if tuple(pos.shape) != (L, W):          # (clip/model.py:346: `x + self.positional_embedding` needs context_length tokens)
@@ -580,8 +612,11 @@ def embed_gather(tokens, table, pos):
 
 def im2col_patch(x_nchw, P, out_absmax=None):
     """[B,3,R,R] -> patch rows [B*g*g, 3*P*P]; out_absmax (1-element device tensor, zeroed by the caller) receives max|x|"""
-    require_cuda(x_nchw)
-    _f32c(x_nchw)
+    require_cuda(x_nchw, out_absmax)
+    _f32c(x_nchw, "im2col_patch image batch")
+    _patch_image_check("im2col_patch", x_nchw, P)
+    if out_absmax is not None and (out_absmax.dtype != torch.float32 or out_absmax.numel() != 1):
+        raise RuntimeError(f"im2col_patch out_absmax: one float32 element expected, got {out_absmax.dtype} {tuple(out_absmax.shape)}")
     B, C, R, _ = x_nchw.shape
     g = R // P
     out = _empty((B * g * g, 3 * P * P), device=x_nchw.device, dtype=torch.float32)
@@ -589,24 +624,40 @@ def im2col_patch(x_nchw, P, out_absmax=None):
     return out
 
 
-def _vit_tokens_check(patches, cls, pos, B):
+def _vit_tokens_check(patches, cls, pos, B, patch_dtype=torch.float32):
     # raw pointers below: a patch count other than the positional table's (another input resolution) fails like the reference's
     # `x + self.positional_embedding` (clip/model.py:229), not as a stray read
+    require_cuda(patches, cls, pos)
+    if pos.dim() != 2:
+        raise RuntimeError(f"vit_tokens: positional embedding of shape {tuple(pos.shape)} where [L, W] is expected")
     L, W = pos.shape
     if patches.numel() != B * (L - 1) * W or cls.numel() != W:
         raise RuntimeError(f"vit_tokens: {patches.numel() // max(1, B * W)} patches of width {W} per image do not match a positional embedding of "
                            f"{L} rows: the input resolution differs from the one the model was built for")
+    _f32c(cls, "vit_tokens cls"); _f32c(pos, "vit_tokens pos")
+    if patches.dtype != patch_dtype or not patches.is_contiguous():
+        raise _lib.DbmmError(f"vit_tokens patches {tuple(patches.shape)}: expected a contiguous {patch_dtype} tensor, got {patches.dtype} "
+                             f"contiguous={patches.is_contiguous()}")
 
 
 def vit_tokens(patches, cls, pos, B):
-    L, W = pos.shape
     _vit_tokens_check(patches, cls, pos, B)
+    L, W = pos.shape
     out = _empty((B, L, W), device=patches.device, dtype=torch.float32)
     check(_lib.lib().dbmm_vit_tokens(ptr(patches), ptr(cls), ptr(pos), ptr(out), B, L, W, stream()), "vit_tokens")
     return out
 
 
+def _gather_eot_check(name, tokens_i32, x, dtype):
+    require_cuda(tokens_i32, x)
+    if x.dim() != 3 or x.dtype != dtype or not x.is_contiguous():
+        raise _lib.DbmmError(f"{name} x: expected a contiguous {dtype} tensor [n, L, W], got {x.dtype} {tuple(x.shape)} "
+                             f"contiguous={x.is_contiguous()}")
+    _operand(f"{name} tokens", tokens_i32, torch.int32, x.shape[:2])
+
+
 def gather_eot(tokens_i32, x):
+    _gather_eot_check("gather_eot", tokens_i32, x, torch.float32)
     n, L, W = x.shape
     out = _empty((n, W), device=x.device, dtype=torch.float32)
     check(_lib.lib().dbmm_gather_eot(ptr(tokens_i32), ptr(x), ptr(out), n, L, W, stream()), "gather_eot")
@@ -975,16 +1026,29 @@ def sgd_momentum(params, grads, bufs, lr, momentum, weight_decay, first_step):
 
 def group_count(logits, y, g, counts):
     """counts int64 [G,2] accumulated in place: (n, correct) per group."""
-    require_cuda(logits, y, g, counts)
+    require_cuda(logits)
+    _f32c(logits, "group_count logits")
+    if logits.dim() != 2 or counts.dim() != 2 or counts.shape[0] > 64:
+        raise RuntimeError(f"group_count: logits {tuple(logits.shape)} and counts {tuple(counts.shape)} where [B, C] and [G, 2] with "
+                           f"G <= 64 are expected")
     B, C = logits.shape
+    _operand("group_count y", y, torch.int64, B)
+    _operand("group_count g", g, torch.int64, B)
+    _operand("group_count counts", counts, torch.int64, (counts.shape[0], 2))
     check(_lib.lib().dbmm_group_count(ptr(logits), ptr(y), ptr(g), ptr(counts), B, C, counts.shape[0], stream()),
           "group_count")
     return counts
 
 
 def group_loss_sum(loss_rows, g, sums):
-    check(_lib.lib().dbmm_group_loss_sum(ptr(loss_rows), ptr(g), ptr(sums), loss_rows.shape[0], sums.shape[0], stream()),
-          "group_loss_sum")
+    """sums float32 [G] accumulated in place: the sum of loss_rows over the rows of each group."""
+    require_cuda(loss_rows, sums)
+    _f32c(loss_rows, "group_loss_sum loss_rows"); _f32c(sums, "group_loss_sum sums")
+    B, G = loss_rows.numel(), sums.numel()
+    if G > 64:
+        raise RuntimeError(f"group_loss_sum sums {tuple(sums.shape)}: the kernel takes at most 64 groups")
+    _operand("group_loss_sum g", g, torch.int64, B)
+    check(_lib.lib().dbmm_group_loss_sum(ptr(loss_rows), ptr(g), ptr(sums), B, G, stream()), "group_loss_sum")
     return sums
 
 
@@ -1706,7 +1770,9 @@ def layernorm_f16(x, gamma, beta, rows=None, ldx=None, eps=1e-5):
 def im2col_patch_f16(x_nchw, P, Kp):
     require_cuda(x_nchw)
     if x_nchw.dtype not in (torch.float16, torch.float32) or not x_nchw.is_contiguous():
-        raise _lib.DbmmError("im2col_patch_f16 needs a contiguous float16 / float32 image batch")
+        raise _lib.DbmmError(f"im2col_patch_f16 needs a contiguous float16 / float32 image batch, got {x_nchw.dtype} {tuple(x_nchw.shape)} "
+                             f"contiguous={x_nchw.is_contiguous()}")
+    _patch_image_check("im2col_patch_f16", x_nchw, P, Kp)
     B, C, R, _ = x_nchw.shape
     g = R // P
     out = _empty((B * g * g, Kp), device=x_nchw.device, dtype=torch.float16)
@@ -1716,18 +1782,15 @@ def im2col_patch_f16(x_nchw, P, Kp):
 
 
 def vit_tokens_f16(patches, cls, pos, B):
+    _vit_tokens_check(patches, cls, pos, B, torch.float16)
     L, W = pos.shape
-    _vit_tokens_check(patches, cls, pos, B)
     out = _empty((B, L, W), device=patches.device, dtype=torch.float16)
     check(_lib.lib().dbmm_vit_tokens_f16(ptr(patches), ptr(cls), ptr(pos), ptr(out), B, L, W, stream()), "vit_tokens_f16")
     return out
 
 
 def embed_gather_f16(tokens, table, pos):
-    require_cuda(tokens, table)
-    if tokens.dtype != torch.int32:
-        tokens = tokens.to(torch.int32)
-    tokens = tokens.contiguous()
+    tokens = _embed_gather_check("embed_gather_f16", tokens, table, pos)
     n, L = tokens.shape
     W = table.shape[1]
     if tuple(pos.shape) != (L, W):
@@ -1739,6 +1802,7 @@ def embed_gather_f16(tokens, table, pos):
 
 
 def gather_eot_f16(tokens_i32, x):
+    _gather_eot_check("gather_eot_f16", tokens_i32, x, torch.float16)
     n, L, W = x.shape
     out = _empty((n, W), device=x.device, dtype=torch.float16)
     check(_lib.lib().dbmm_gather_eot_f16(ptr(tokens_i32), ptr(x), ptr(out), n, L, W, stream()), "gather_eot_f16")

@@ -797,7 +797,9 @@ int dbmm_gather_rows(const float* table, const int64_t* idx, float* out, int64_t
                      int64_t n_idx, int64_t D, void* stream);
 
 /* update_dict (final_main.py:383-391) on device: counts[g][0] += 1, counts[g][1] += (argmax
- * logits == y) for every row; counts is int64 [G][2], accumulated (not cleared). */
+ * logits == y, first index on ties) for every row; counts is int64 [G][2], accumulated (not
+ * cleared).  G <= 64.  Rows whose id is outside [0, G) -- compared as 64-bit values -- count
+ * for no group, here and in dbmm_group_loss_sum. */
 int dbmm_group_count(const float* logits, const int64_t* y, const int64_t* g, int64_t* counts,
                      int64_t B, int64_t C, int64_t G, void* stream);
 
