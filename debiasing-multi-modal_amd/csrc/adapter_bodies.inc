@@ -486,8 +486,9 @@ __device__ __forceinline__ void ce_fwd_row(const float* __restrict__ z, const fl
             float se = 0.f;
 #pragma unroll
             for (int c = 0; c < CMAX; ++c) if (c < C) se += expf(lg[c] - mx);
-            const int y = (int)labels[lrow];
-            float ly = 0.f;
+            const long long yl = labels[lrow];
+            const int y = (yl >= 0 && yl < (long long)C) ? (int)yl : -1;     // the int64 label is compared: 2^32 + 1 is no class
+            float ly = __builtin_nanf("");                                   // a label outside [0, C) scores NaN
 #pragma unroll
             for (int c = 0; c < CMAX; ++c) if (c == y) ly = lg[c];
             loss_rows[row] = (mx + logf(se)) - ly;
@@ -511,7 +512,8 @@ __device__ __forceinline__ void ce_bwd_row(const float* __restrict__ z, float in
         float se = 0.f;
 #pragma unroll
         for (int c = 0; c < CMAX; ++c) { dl[c] = (c < C) ? expf(dl[c] - mx) : 0.f; se += dl[c]; }
-        const int y = (int)labels[lrow];
+        const long long yl = labels[lrow];
+        const int y = (yl >= 0 && yl < (long long)C) ? (int)yl : -1;         // as ce_fwd_row: no one-hot for a label outside [0, C)
         const float k = gscale * invT * w_new;   // d loss / d (feat . tn[c]) incl. blend weight
 #pragma unroll
         for (int c = 0; c < CMAX; ++c) dl[c] = (dl[c] / se - (c == y ? 1.f : 0.f)) * k;

@@ -67,10 +67,9 @@ __device__ __forceinline__ void count_row(const float (&lg)[CMAX], int C, long l
 #pragma unroll
     for (int c = 1; c < CMAX; ++c)
         if (c < C && lg[c] > mx) { mx = lg[c]; am = c; }
-    const int gi = (int)g;
-    if (gi >= 0 && gi < G) {
-        atomicAdd(&sc[gi][0], 1u);
-        if ((long long)am == y) atomicAdd(&sc[gi][1], 1u);
+    if (g >= 0 && g < (long long)G) {                    // the int64 id is compared: 2^32 + k is no group
+        atomicAdd(&sc[g][0], 1u);
+        if ((long long)am == y) atomicAdd(&sc[g][1], 1u);
     }
 }
 __device__ __forceinline__ void flush_counts(unsigned int (*sc)[2], unsigned long long* __restrict__ counts, int G) {

@@ -142,7 +142,7 @@ __device__ __forceinline__ void linear_rows_body(const LinArgs& a, const LinSwee
         }
         const long long row = SWEEP ? srow : (long long)r;
         const long long yl = a.labels[row];
-        const int y = (int)yl;
+        const int y = (yl >= 0 && yl < (long long)C) ? (int)yl : -1;     // the int64 label is compared: 2^32 + 1 is no class
         float l[CM];
 #pragma unroll
         for (int c = 0; c < CM; ++c) {
@@ -190,10 +190,10 @@ __device__ __forceinline__ void linear_rows_body(const LinArgs& a, const LinSwee
         if (SWEEP) {
             // update_dict of the row: cm is group_count_kernel's argmax (the first maximum), compared with the int64 label
             if (count && lane == 0) {
-                const int gi = (int)sw.groups[row];
-                if (gi >= 0 && gi < sw.G) {
-                    atomicAdd(&sc[gi][0], 1u);
-                    if ((long long)cm == yl) atomicAdd(&sc[gi][1], 1u);
+                const long long gl = sw.groups[row];              // the int64 id is compared: 2^32 + k is no group
+                if (gl >= 0 && gl < (long long)sw.G) {
+                    atomicAdd(&sc[gl][0], 1u);
+                    if ((long long)cm == yl) atomicAdd(&sc[gl][1], 1u);
                 }
             }
         }

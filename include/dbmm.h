@@ -505,7 +505,16 @@ int dbmm_text_colnorm(const float* text, float* tn, int64_t D, int64_t C, void* 
  *   logits[b][c] = feat . tn[c] / T;   loss_rows[b] = CE(logits[b], labels[b]);
  *   pred[b] = argmax_c logits[b][c].
  * inv_norm[B] (1/||z||) is saved for the backward.  labels/loss_rows/pred/inv_norm may be
- * NULL.  C <= 8.  loss_mean (1 float, may be NULL) = mean of loss_rows. */
+ * NULL.  C <= 8.  loss_mean (1 float, may be NULL) = mean of loss_rows.
+ * Ids (every head, step and sweep entry of this header follows these rules; an id is compared as the 64-bit value it is, so
+ * 2^32 + 1 is neither class 1 nor group 1):
+ *   label outside [0, C): loss_rows[b] is NaN (and so is every mean or sum that takes it in); the row's logits and pred are
+ *     unaffected; the backward subtracts no one-hot for it (dz and the parameters stay finite); a sweep counts the row in its
+ *     group's n and never as correct.  Label -100 is such a label and nothing more: there is no ignore_index.
+ *   group id outside [0, G): the row is in no counter, neither n nor correct; under group DRO it has weight 0 and is in no n_g or L_g.
+ *   row index outside [0, n_rows) in a sweep's idx: clamped to 0 or n_rows - 1 at every use -- the embedding row, its label, its
+ *     group and its row weight.
+ * pred is the FIRST maximum of the row (the lower class on a tie), and so is the argmax behind the sweeps' counters. */
 int dbmm_l2norm_sim_ce_fwd(const float* z, const float* z_old, float ebd_weight, const float* tn,
                            const int64_t* labels, float temperature, float* logits,
                            float* loss_rows, float* loss_mean, int64_t* pred, float* inv_norm,
@@ -516,7 +525,8 @@ int dbmm_l2norm_sim_ce_fwd(const float* z, const float* z_old, float ebd_weight,
  *                    and `labels` (fused training path).
  *   dlogits != NULL: dLoss/dlogits [B][C] is given by the caller (autograd of an external
  *                    criterion, e.g. nn.CrossEntropyLoss at final_main.py:456); logits, labels
- *                    and grad_scale are ignored. */
+ *                    and grad_scale are ignored.
+ * A label outside [0, C) (64-bit compare) gets softmax * scale with no one-hot subtracted; see dbmm_l2norm_sim_ce_fwd. */
 int dbmm_l2norm_sim_ce_bwd(const float* z, const float* inv_norm, float ebd_weight, int blended,
                            const float* tn, const float* logits, const int64_t* labels,
                            const float* dlogits, float temperature, float grad_scale, float* dz,
@@ -557,7 +567,8 @@ int dbmm_group_dro_weights(const float* loss_rows, const int64_t* groups, const 
                            float* robust_loss, int64_t B, int64_t G, float eta, void* stream);
 
 /* dbmm_l2norm_sim_ce_bwd's fused training path with a weight per row: loss = sum_b weights[groups[b]] CE_b (row 0 of
- * dbmm_group_dro_weights' output; weight 0 for a group id outside [0, G)). */
+ * dbmm_group_dro_weights' output; weight 0 for a group id outside [0, G): that row's dz is exactly 0).  Labels as in
+ * dbmm_l2norm_sim_ce_bwd.  G outside 1..8 or B < 2: DBMM_E_SHAPE, as dbmm_group_dro_weights. */
 int dbmm_l2norm_sim_ce_bwd_weighted(const float* z, const float* inv_norm, float ebd_weight, int blended, const float* tn,
                                     const float* logits, const int64_t* labels, const int64_t* groups,
                                     const float* weights, int64_t G, float temperature, float* dz, int64_t B, int64_t D,
@@ -660,12 +671,16 @@ int dbmm_adapter_train_step_sets(const float* x, float* w1, float* b1, float* ga
  * the launches of ONE dbmm_adapter_train_step (8, or 11 with a frozen old adapter), the replica being a grid dimension.  Fast shape
  * only (H == 128, D % 128 == 0; else DBMM_E_UNSUPPORTED); replica r's results are the bits dbmm_adapter_train_step gives for r alone.
  *   table [n_rows][D], labels / groups [n_rows]: one shared embedding table; idx [idx_R][idx_B] (= [R][B], else DBMM_E_SHAPE): replica
- *     r trains on rows idx[r][:], read in place (indices are clamped into the table; repeats are legal)
+ *     r trains on rows idx[r][:], read in place (indices are clamped into the table -- to row 0 or n_rows - 1, as 64-bit values,
+ *     for the embedding row, its label and its group alike; repeats are legal)
  *   params: 9 device pointers to stacked [R, ...] tensors (w1, b1, gamma, beta, running_mean, running_var, nbt int64 [R], w2, b2);
  *     bufs: the 6 stacked momentum buffers (w1, b1, gamma, beta, w2, b2); old: 9 pointers of the frozen adapters, or NULL.  The
  *     three arrays and lr [R] are HOST arrays, read during the call (the learning rates travel as kernel arguments)
  *   logits [R][B][C], loss_rows [R][B], loss_mean [R]: outputs.  counted != 0: counts int64 [R][G][2] += (n, correct) per group and
- *     loss_sum double [R] += (double)loss_mean * B, by the step's own launches.  B < 2: DBMM_E_SHAPE (train-mode BatchNorm1d). */
+ *     loss_sum double [R] += (double)loss_mean * B, by the step's own launches.  B < 2: DBMM_E_SHAPE (train-mode BatchNorm1d).
+ *     G outside 1..64: DBMM_E_SHAPE.  A row whose group id is outside [0, G) (64-bit compare) is in no counter; a row whose label
+ *     is outside [0, C) has loss_rows NaN, is counted in its group's n, never as correct, and gets no one-hot in the backward
+ *     (the id rules at dbmm_l2norm_sim_ce_fwd). */
 size_t dbmm_workspace_bytes_adapter_sweep_step(int64_t R, int64_t B, int64_t D, int64_t H, int with_old);
 int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B,
                             const int64_t* labels, const int64_t* groups, void* const* params, float* const* bufs,
@@ -677,7 +692,9 @@ int dbmm_adapter_sweep_step(const float* table, int64_t n_rows, const int64_t* i
 
 /* dbmm_adapter_sweep_step under group DRO: replica r takes the step dbmm_adapter_train_step_gdro takes for r alone (same bits).
  * The groups of the robust loss are `groups` (G <= 8 here), q fp32 [R][G] is updated in place, robust_loss [R] takes loss_mean's
- * place and is what loss_sum accumulates (times B).  Same workspace; two launches more than dbmm_adapter_sweep_step. */
+ * place and is what loss_sum accumulates (times B).  Same workspace; two launches more than dbmm_adapter_sweep_step.  A row whose
+ * group id is outside [0, G) (64-bit compare) has weight 0, is in no n_g or L_g and in no counter; labels and indices as in
+ * dbmm_adapter_sweep_step. */
 int dbmm_adapter_sweep_step_gdro(const float* table, int64_t n_rows, const int64_t* idx, int64_t idx_R, int64_t idx_B,
                                  const int64_t* labels, const int64_t* groups, void* const* params, float* const* bufs,
                                  void* const* old, float ebd_weight, const float* tn, float temperature, const float* lr,
@@ -688,7 +705,9 @@ int dbmm_adapter_sweep_step_gdro(const float* table, int64_t n_rows, const int64
 
 /* Replica-batched evaluation forward: eval-mode adapters (running statistics; old + new blend when `old`), cosine logits, per-row
  * CE, group counters and the float64 loss sum (loss_sum[r] += sum_b (double)loss_rows[r][b], fixed order) of R replicas over the
- * SAME B rows: idx [B] rows of the table, or idx == NULL: rows row0 .. row0 + B - 1.  5 launches (8 with `old`). */
+ * SAME B rows: idx [B] rows of the table (clamped into it as in dbmm_adapter_sweep_step), or idx == NULL: rows row0 .. row0 + B - 1
+ * (row0 < 0 or row0 + B > n_rows: DBMM_E_SHAPE).  5 launches (8 with `old`).  Out-of-range labels and group ids as in
+ * dbmm_adapter_sweep_step. */
 size_t dbmm_workspace_bytes_adapter_sweep_eval(int64_t R, int64_t B, int64_t D, int64_t H, int with_old);
 int dbmm_adapter_sweep_eval(const float* table, int64_t n_rows, const int64_t* idx, int64_t row0, const int64_t* labels,
                             const int64_t* groups, void* const* params, void* const* old, float ebd_weight,
@@ -700,6 +719,8 @@ int dbmm_adapter_sweep_eval(const float* table, int64_t n_rows, const int64_t* i
  * logits = x W^T + b, per-row CE and its mean, dlogits = (softmax - onehot) / B, dW = dlogits^T x, db = colsum dlogits, then
  * dbmm_sgd_momentum's update of w, b and their momentum buffers m_w, m_b in place.  x [B][D], labels int64 [B] in [0, C),
  * w / m_w [C][D], b / m_b [C]; outputs logits [B][C], loss_rows [B], loss_mean [1].  C <= 8, D % 4 == 0, D <= 1024, any B >= 1.
+ * A label outside [0, C), compared as a 64-bit value (-100 included: no ignore_index): loss_rows[b] and loss_mean are NaN, the row's
+ * logits are unaffected and no one-hot is subtracted, so w, b and the momenta stay finite.
  * Every sum runs in a fixed order: identical inputs give identical bits.  One kernel launch (after a 4-byte memset of the
  * workspace's ticket counter) up to the batch size of the option linear_step_one_launch_max_b, two launches above it.
  * x, w, m_w and the workspace 16-byte aligned; workspace = dbmm_workspace_bytes_linear_train_step(B, D, C) bytes (0: bad shape). */
@@ -721,10 +742,13 @@ int dbmm_linear_ce_fwd(const float* x, const float* w, const float* b, const int
  * linear_step_one_launch_max_b, two kernels above it), the replica being a grid dimension.  Replica r's logits, loss_rows, loss_mean,
  * w, b, m_w, m_b are the bits dbmm_linear_train_step gives for r alone on table[idx[r]].
  *   table [n_rows][D], labels / groups [n_rows]: one shared embedding table; idx [idx_R][idx_B] (= [R][B], else DBMM_E_SHAPE): replica
- *     r trains on rows idx[r][:], read in place (indices are clamped into the table; repeats are legal)
+ *     r trains on rows idx[r][:], read in place (indices are clamped into the table -- to row 0 or n_rows - 1, as 64-bit values,
+ *     for the embedding row, its label, its group and its row weight alike; repeats are legal)
  *   w / m_w [R][C][D], b / m_b [R][C]: stacked; lr [R] is a HOST array, read during the call (the rates travel as kernel arguments)
  *   logits [R][B][C], loss_rows [R][B], loss_mean [R]: outputs.  counted != 0: counts int64 [R][G][2] += (n, correct) per group and
- *     loss_sum double [R] += (double)loss_mean[r] * B, by the step's own launches.
+ *     loss_sum double [R] += (double)loss_mean[r] * B, by the step's own launches.  A row whose group id is outside [0, G) (64-bit
+ *     compare) is in no counter; a row whose label is outside [0, C) scores NaN (dbmm_linear_train_step), is counted in its
+ *     group's n and never as correct.
  * R outside 1..16, C outside 1..8, D % 4 != 0, D > 1024, G outside 1..64: DBMM_E_SHAPE.  table, w, m_w and the workspace 16-byte
  * aligned; workspace = dbmm_workspace_bytes_linear_sweep_step(R, B, D, C) bytes (linear in R; 0: bad shape). */
 size_t dbmm_workspace_bytes_linear_sweep_step(int64_t R, int64_t B, int64_t D, int64_t C);
@@ -736,8 +760,8 @@ int dbmm_linear_sweep_step(const float* table, int64_t n_rows, const int64_t* id
 
 /* Replica-batched evaluation forward of the linear probe: logits [R][B][C] and per-row CE [R][B] (the bits of dbmm_linear_ce_fwd),
  * group counters and the float64 loss sum (loss_sum[r] += sum_b (double)loss_rows[r][b], fixed order) of R replicas over the SAME B
- * rows: idx [B] rows of the table, or idx == NULL: rows row0 .. row0 + B - 1 (outside the table: DBMM_E_SHAPE).  One memset + one
- * kernel whatever R is.  w [R][C][D], b [R][C]. */
+ * rows: idx [B] rows of the table (clamped into it), or idx == NULL: rows row0 .. row0 + B - 1 (outside the table: DBMM_E_SHAPE).
+ * One memset + one kernel whatever R is.  w [R][C][D], b [R][C].  Out-of-range labels and group ids as in dbmm_linear_sweep_step. */
 size_t dbmm_workspace_bytes_linear_sweep_eval(int64_t R, int64_t B);
 int dbmm_linear_sweep_eval(const float* table, int64_t n_rows, const int64_t* idx, int64_t row0, const int64_t* labels,
                            const int64_t* groups, const float* w, const float* b, float* logits, float* loss_rows,
@@ -758,7 +782,8 @@ int dbmm_linear_sweep_eval(const float* table, int64_t n_rows, const int64_t* id
  *   dbmm_adapter_sweep_step_weighted, dbmm_linear_sweep_step_weighted
  *       the sweep steps with row_w [Rw][n_rows] over the TABLE's rows, Rw = 1 (shared by the replicas) or R (else DBMM_E_SHAPE):
  *       batch row b of replica r weighs row_w[(Rw == 1 ? 0 : r) * n_rows + idx[r][b] clamped into the table], the clamp the labels
- *       use.  The group counters stay unweighted; counted != 0 adds (double)L[r] * B to loss_sum[r]. */
+ *       use, in the backward's gradient scale and in the weighted mean alike.  The group counters stay unweighted; counted != 0
+ *       adds (double)L[r] * B to loss_sum[r]. */
 int dbmm_weighted_mean(const float* x, const float* row_w, float* out, int64_t n, void* stream);
 int dbmm_l2norm_sim_ce_bwd_rows(const float* z, const float* inv_norm, float ebd_weight, int blended, const float* tn,
                                 const float* logits, const int64_t* labels, const float* row_w, float temperature,
