@@ -50,6 +50,8 @@ KERNEL_SOURCES = (
     ("supcon_", ("supcon.hip", "common.h")),
     ("sets_", ("supcon_sets.hip", "common.h")),
     ("kmeans_", ("kmeans.hip", "common.h")),
+    ("label_", ("erase.hip", "common.h")),
+    ("erase_rows_", ("erase.hip", "common.h")),
 )
 
 
@@ -233,6 +235,9 @@ _SIGS = {
     "dbmm_kmeans_begin": [_P, _L, _L, _L, _P, _Z, _P],
     "dbmm_kmeans_iterate": [_P, _L, _L, _L, _L, _P, _Z, _P],
     "dbmm_kmeans_assign": [_P, _P, _P, _P, _L, _L, _L, _P],
+    "dbmm_workspace_bytes_label_colsums": [_L, _L, _L],
+    "dbmm_label_colsums": [_P, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
+    "dbmm_erase_rows": [_P, _P, _P, _P, _P, _L, _L, _L, _P],
 }
 _RESTYPES = {
     "dbmm_error_string": ctypes.c_char_p,
@@ -255,6 +260,7 @@ _RESTYPES = {
     "dbmm_workspace_bytes_covariance": c_size_t,
     "dbmm_workspace_bytes_sym_eig": c_size_t,
     "dbmm_workspace_bytes_kmeans": c_size_t,
+    "dbmm_workspace_bytes_label_colsums": c_size_t,
     "dbmm_supcon_workspace_bytes": c_size_t,
     "dbmm_supcon_sets_workspace_bytes": c_size_t,
     "dbmm_workspace_bytes_adapter_train_step_sets": c_size_t,

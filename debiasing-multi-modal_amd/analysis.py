@@ -589,3 +589,226 @@ def separation_report(train_table, val_table, test_table, transform=None):
             within[int(cls)] = silhouette(ops.gather_rows(x, torch.from_numpy(idx).to(x.device)), c[idx])["score"]
         out[split] = {"group": _score_or_nan(x, table.targets_group.cpu().numpy()), "spurious_within_class": within}
     return out
+
+
+# ---- linear concept erasure: the rows changed so that no linear classifier reads a labelling (Belrose et al. 2023, "LEACE") ---------------
+# Post-hoc debiasing of frozen embeddings, in closed form from three moments: the column sums, the scatter matrix (ops.covariance) and
+# the per-label column sums (ops.label_column_sums), each one read of the rows.  The eraser is x -> x - sum_k ((x - mean) . A_k) B_k with
+# r <= G - 1 vector pairs; ops.erase_rows applies it in one read and one write.  separation_report and cluster_agreement measure what it
+# destroys; every training path runs unchanged on erased_table's rows.
+
+ERASURE_METHODS = ("leace", "orth")
+ERASURE_MAX_LABELS = 16   # ops.LABEL_SUMS_MAX_G
+ERASURE_RANK_RTOL = 1e-10  # a singular value of the decomposed matrix counts above this fraction of the largest ...
+ERASURE_RANK_FLOOR = 1e-5  # ... as long as the cross-covariance itself has that many above this fraction of sqrt(lambda_max)
+ERASURE_FP32_RIDGE = 2.0 ** -24  # erasure_fit's ridge per dimension: its scatter matrix is fp32-accurate
+
+
+def erasure_from_moments(scatter, center, mean, n, label_sums, counts, method="leace", ridge=0.0):
+    """The host step of `erasure_fit`, numpy only.  scatter float64 [D, D]: sum_i (x_i - center)(x_i - center)^T about `center` (any
+    vector near the mean, as pca_from_scatter takes it); mean float64 [D]: the rows' mean; n rows; label_sums float64 [G, D]: the RAW
+    per-label sums of the rows; counts [G]: the rows per label (they add up to n).
+
+    With Sxx = (scatter - n (mean - center)(mean - center)^T) / n and Sxz [D, G], column g = (label_sums[g] - counts[g] mean) / n:
+      "leace"  W = Sxx^(-1/2), Wp = Sxx^(1/2) from one eigh, eigenvalues below D eps lambda_max dropped (a pseudo-inverse: n < D works);
+               U = an orthonormal basis of the column space of W Sxz (SVD); A = (W U)^T, B = (Wp U)^T: the least change of the rows,
+               in the norm Sxx^-1 induces, after which every label's mean is the overall mean (Belrose et al. 2023, theorem 4.3).
+      "orth"   U = a basis of the column space of Sxz; A = B = U^T: the mean projection (Haghighatkhah et al. 2022).
+    Both erase by x -> x - sum_k ((x - mean) . A_k) B_k.
+
+    The rank r is the number of singular values of the decomposed matrix above 1e-10 of the largest, but no more than the number of
+    singular values of Sxz ITSELF above 1e-5 sqrt(lambda_max): the columns add up to zero, so r <= G - 1, and what a previous
+    erasure left behind -- the rounding of float32 rows, 2^-24 of their entries -- is rank 0, not G - 1 directions of noise.  That
+    floor is taken on Sxz because the whitening multiplies noise along a direction of small variance by 1 / its deviation.
+
+    `ridge` (a fraction of lambda_max, "leace" only) is added to every kept eigenvalue before the two roots are taken: Wp W stays
+    the identity on the kept directions, so the erasure stays exact, it is least in the norm (Sxx + ridge lambda_max I)^-1, and W
+    is bounded by (ridge lambda_max)^(-1/2).  For a scatter matrix that is itself rounded (erasure_fit's comes from fp32 products):
+    its null directions (n < D) come out with eigenvalues of either sign at the rounding level, and without a ridge the positive
+    ones are whitened by 1 / sqrt(noise).
+
+    Returns {'mean' float32 [D], 'A' float32 [r, D], 'B' float32 [r, D], 'rank', 'method', 'singular_values' float64 [G] (of the
+    decomposed matrix)}.  Rank 0 (one label, or labels whose means coincide) is a valid fit with empty A and B.  An unknown
+    method, a label with count 0, n < 2 and a negative ridge raise ValueError."""
+    mean, A, B, sv = _erasure_vectors64(scatter, center, mean, n, label_sums, counts, method, ridge)
+    r, D = A.shape
+    return {"mean": mean.astype(np.float32), "A": np.ascontiguousarray(A, dtype=np.float32).reshape(r, D),
+            "B": np.ascontiguousarray(B, dtype=np.float32).reshape(r, D), "rank": r, "method": method, "singular_values": sv}
+
+
+def _erasure_vectors64(scatter, center, mean, n, label_sums, counts, method, ridge=0.0):
+    """erasure_from_moments before its float32 rounding: (mean [D], A [r, D], B [r, D], singular values [G]), float64"""
+    if method not in ERASURE_METHODS:
+        raise ValueError(f"erasure: method = {method!r}; one of {ERASURE_METHODS}")
+    if not ridge >= 0.0:
+        raise ValueError(f"erasure: ridge = {ridge}; a fraction of the largest eigenvalue, not negative")
+    scatter = np.asarray(scatter, dtype=np.float64)
+    sums = np.asarray(label_sums, dtype=np.float64)
+    cnt = np.asarray(counts).astype(np.int64).ravel()
+    D = scatter.shape[0]
+    if scatter.shape != (D, D) or sums.ndim != 2 or sums.shape[1] != D or cnt.shape != (sums.shape[0],):
+        raise ValueError(f"erasure: scatter {scatter.shape}, label_sums {sums.shape}, counts {cnt.shape}")
+    G = sums.shape[0]
+    if not 1 <= G <= ERASURE_MAX_LABELS:
+        raise ValueError(f"erasure: {G} labels (1..{ERASURE_MAX_LABELS})")
+    if n < 2:
+        raise ValueError(f"erasure needs at least two rows, got {n}")
+    if (cnt <= 0).any() or cnt.sum() != n:
+        raise ValueError(f"erasure: counts {cnt.tolist()} for {n} rows; every label needs a row and every row a label")
+    mean = np.asarray(mean, dtype=np.float64)
+    d = mean - np.asarray(center).astype(np.float64)
+    Sxx = (scatter - np.float64(n) * np.outer(d, d)) / np.float64(n)
+    Sxz = (sums - cnt.astype(np.float64)[:, None] * mean[None, :]).T / np.float64(n)          # [D, G]
+    w, V = np.linalg.eigh(Sxx)                                                                   # ascending
+    top = max(w[-1], 0.0)
+    raw = np.linalg.svd(Sxz, compute_uv=False)
+    above = int((raw > ERASURE_RANK_FLOOR * np.sqrt(top)).sum())                                 # what stands above the rows' own rounding
+    if method == "leace":
+        keep = w > D * np.finfo(np.float64).eps * top
+        w, V = w[keep] + ridge * top, V[:, keep]
+        root = np.sqrt(w)
+        W, Wp = (V / root) @ V.T, (V * root) @ V.T
+        M = W @ Sxz
+    else:
+        W = Wp = None
+        M = Sxz
+    U, s, _ = np.linalg.svd(M, full_matrices=False)                                              # s descending, [min(D, G)]
+    r = min(int((s > ERASURE_RANK_RTOL * s[0]).sum()), above) if s[0] > 0 else 0
+    U = U[:, :r]
+    A, B = (U.T, U.T) if method == "orth" else ((W @ U).T, (Wp @ U).T)
+    sv = np.zeros(G, dtype=np.float64)
+    sv[:len(s)] = s
+    return mean, np.asarray(A).reshape(r, D), np.asarray(B).reshape(r, D), sv
+
+
+def balanced_rows(labels, seed=0):
+    """Sorted int64 indices of min-count rows of every label (np.unique order), drawn without replacement from a private
+    np.random.RandomState(seed): the global stream is left alone.  Fitting an eraser on the group-balanced rows
+    (balanced_rows(table.group_array)) makes the erased attribute independent of the class there, so that erasing it does not take
+    the class with it: on a confounded split the spurious attribute's direction IS partly the class's."""
+    l = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    l = l.ravel()
+    if l.size == 0:
+        raise ValueError("balanced_rows: no labels")
+    uniq, dense, counts = np.unique(l, return_inverse=True, return_counts=True)
+    rng, m = np.random.RandomState(seed), int(counts.min())
+    picks = [rng.choice(np.flatnonzero(dense == g), size=m, replace=False) for g in range(len(uniq))]
+    return np.sort(np.concatenate(picks)).astype(np.int64)
+
+
+def erasure_fit(embeddings, labels=None, method="leace", rows=None, transform=None):
+    """The eraser of a labelling of a split's rows (`erasure_from_moments`' dict plus 'labels': the unique labels, 'counts' and 'n').
+
+    `embeddings`: an EmbeddingTable (its targets_spurious unless `labels` is given) or a device tensor [N, D] with `labels` [N]: any
+    integers -- the spurious attribute, the groups, `pseudo_groups`' clusters --, mapped to dense ids by np.unique; more than 16
+    raise ValueError before anything is launched, like an unknown method.  `rows`: an int64 index set (`balanced_rows`): the fit
+    uses ops.gather_rows of those rows and their labels only.  `transform` (a callable emb -> emb) is applied batch by batch in
+    eval mode first, as in `kmeans` / `silhouette`.
+
+    Three reads of the rows and nothing N x D allocated apart from the gathered or transformed rows when they are asked for:
+    _column_sums for the centre (float32 of the fp32-block mean), ops.covariance for the scatter about it, ops.label_column_sums
+    for the float64 per-label sums -- whose total over n is the float64 mean the fit centres on, so that the cross-covariance's
+    columns add up to zero to the last bit's worth and the rank is G - 1, not G.  The scatter matrix is fp32-accurate (exact fp32
+    products of rows centred in fp32), so "leace" whitens with erasure_from_moments' ridge = D 2^-24: the erasure stays exact, and
+    the vectors stay bounded where the rows leave directions empty (n < D)."""
+    if method not in ERASURE_METHODS:
+        raise ValueError(f"erasure: method = {method!r}; one of {ERASURE_METHODS}")
+    if isinstance(embeddings, trainer.EmbeddingTable) and labels is None:
+        labels = embeddings.targets_spurious
+    x, l_np = _rows_and_groups(embeddings, labels)
+    if rows is not None:
+        rows = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows).astype(np.int64).ravel()
+        if rows.size == 0 or rows.min() < 0 or rows.max() >= x.shape[0]:
+            raise ValueError(f"erasure_fit: rows must index the {x.shape[0]} rows")
+        l_np = l_np[rows]
+    uniq, dense = np.unique(l_np, return_inverse=True)
+    G = len(uniq)
+    if G > ERASURE_MAX_LABELS:
+        raise ValueError(f"erasure_fit: {G} labels; at most {ERASURE_MAX_LABELS}")
+    if l_np.shape[0] < 2:
+        raise ValueError(f"erasure needs at least two rows, got {l_np.shape[0]}")
+    x = x.float().contiguous()
+    if rows is not None:
+        x = ops.gather_rows(x, torch.from_numpy(rows).to(x.device))
+    if transform is not None:
+        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
+    n = x.shape[0]
+    center = (_column_sums(x) / n).astype(np.float32)
+    scatter = ops.covariance(x, torch.from_numpy(center).to(x.device))
+    sums, counts = ops.label_column_sums(x, torch.from_numpy(dense.reshape(-1).astype(np.int64)).to(x.device), G)
+    sums, counts = sums.cpu().numpy(), counts.cpu().numpy()
+    fit = erasure_from_moments(scatter.cpu().numpy(), center, sums.sum(0) / n, n, sums, counts, method, ridge=x.shape[1] * ERASURE_FP32_RIDGE)
+    fit.update(labels=uniq, counts=counts, n=n)
+    return fit
+
+
+def erase(fit, embeddings, out=None):
+    """The rows of `embeddings` (an EmbeddingTable or a device tensor [N, D]) after the eraser `fit` (erasure_fit's dict), on the fused
+    kernel (ops.erase_rows: one read, one write, nothing else allocated): a device tensor [N, D], or `out` -- which may be the
+    input tensor itself: in place.  Rank 0 returns a copy (or `out` filled with the rows) and launches no kernel of ours."""
+    x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+    x = x.float().contiguous()
+    if fit["rank"] == 0:
+        if out is None:
+            return x.clone()
+        if out.data_ptr() != x.data_ptr():
+            out.copy_(x)
+        return out
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(x.device)
+    return ops.erase_rows(x, dev(fit["mean"]), dev(fit["A"]), dev(fit["B"]), out=out)
+
+
+def erased_table(table, fit):
+    """An EmbeddingTable with the erased rows (a new tensor; the source is left alone) and the table's own labels, y_pred and
+    filenames, built as pseudo_group_table builds its table: what train_all_epochs, train_sweep, train_jtt and the reports take."""
+    out = trainer.EmbeddingTable(erase(fit, table), table.targets.cpu().numpy(), table.targets_spurious.cpu().numpy(), y_pred=None,
+                                 filenames=table.filenames, device=table.device)
+    out.y_pred = table.y_pred
+    return out
+
+
+def label_mean_gap(x, labels):
+    """The largest |entry| of (a label's mean - the overall mean) over the labels of the rows x (device [N, D]), in float64 from
+    ops.label_column_sums: what an eraser of that labelling brings to rounding level."""
+    l_np = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    uniq, dense = np.unique(l_np, return_inverse=True)
+    sums, counts = ops.label_column_sums(x, torch.from_numpy(dense.reshape(-1).astype(np.int64)).to(x.device), len(uniq))
+    sums, counts = sums.cpu().numpy(), counts.cpu().numpy().astype(np.float64)
+    return float(np.abs(sums / counts[:, None] - sums.sum(0) / counts.sum()).max())
+
+
+def erasure_report(opt, fit, train_table, val_table, test_table):
+    """What an eraser does to the three splits: {'train': r, 'val': r, 'test': r} with r = {'before': m, 'after': m,
+    'relative_change': ||r(X) - X||_F / ||X - mean||_F} and m = {'class': the class prompts' group accuracies
+    (validate_zs_linear_probing on opt.text_embedding_dir), 'spurious_acc': the accuracy of the spurious prompts on the spurious
+    attribute (the same function on opt.text_spurious_embedding_dir, target="spurious"), 'gap': label_mean_gap of the fit's
+    labelling where the split carries it (the table's spurious attribute or groups; else None)}."""
+    bs = max(int(getattr(opt, "batch_size", 0) or 0), 4096)
+    ratio = train_table.group_ratio.numpy()
+    mean = torch.from_numpy(fit["mean"])
+
+    def measures(table, labels):
+        return {"class": trainer.validate_zs_linear_probing(table, opt.text_embedding_dir, opt.zs_temperature, bs, ratio)[2],
+                "spurious_acc": trainer.validate_zs_linear_probing(table, opt.text_spurious_embedding_dir, opt.zs_temperature, bs, ratio,
+                                                                   target="spurious")[1],
+                "gap": None if labels is None else label_mean_gap(table.embeddings, labels)}
+
+    out = {}
+    for split, table in (("train", train_table), ("val", val_table), ("test", test_table)):
+        labels = None
+        for cand in (table.targets_spurious, table.targets_group, table.targets):
+            if np.array_equal(np.unique(cand.cpu().numpy()), np.asarray(fit["labels"])):
+                labels = cand
+                break
+        after = erased_table(table, fit)
+        m_dev, diff, spread = mean.to(table.device), 0.0, 0.0
+        for i in range(0, len(table), bs):                                           # batch by batch: no second copy of the split in float64
+            a, b = after.embeddings[i:i + bs].double(), table.embeddings[i:i + bs].double()
+            diff += (a - b).pow(2).sum().item()
+            spread += (b - m_dev).pow(2).sum().item()
+        diff, spread = diff ** 0.5, spread ** 0.5
+        out[split] = {"before": measures(table, labels), "after": measures(after, labels),
+                      "relative_change": diff / spread if spread > 0 else 0.0}
+    return out

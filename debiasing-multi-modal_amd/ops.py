@@ -1702,6 +1702,93 @@ def kmeans_fit(x, centers0, max_iter=100, check_every=8):
     return centers, labels, info
 
 
+LABEL_SUMS_MAX_G = 16               # labels of the per-label column sums (csrc/erase.hip); the value of KMEANS_MAX_K
+ERASE_MAX_R = 15                    # rank of the update of erase_rows: at most 16 labels, whose centred means have rank <= 15
+
+
+def label_column_sums(x, labels, n_labels):
+    """(sums float64 [G, D], counts int64 [G]): the RAW per-label column sums of the rows x fp32 [N, D] (D % 64 == 0, D <= 4096,
+    N <= 2^23) and the rows per label, from one read of x (dbmm_label_colsums).  labels int64 [N], compared as 64-bit: a value
+    outside [0, n_labels) is in no sum and no count.  n_labels in 1..16.  float64 from the first add, row order inside a range,
+    the ranges merged in a fixed order: the same bits on every call."""
+    N, D = _erase_rows_operand("label_column_sums", x)
+    if not torch.is_tensor(labels):
+        raise _lib.DbmmError("label_column_sums: labels must be a contiguous int64 [N] device tensor")
+    require_cuda(labels)
+    if labels.dtype != torch.int64 or not labels.is_contiguous() or labels.dim() != 1:
+        raise _lib.DbmmError("label_column_sums: labels must be a contiguous int64 [N] tensor")
+    if labels.numel() != N:
+        raise _lib.DbmmError(f"label_column_sums: {labels.numel()} labels for {N} rows")
+    if labels.device != x.device:
+        raise _lib.DbmmError(f"label_column_sums: labels is on {labels.device}, x on {x.device}")
+    G = int(n_labels)
+    if not 1 <= G <= LABEL_SUMS_MAX_G:
+        raise _lib.DbmmError(f"label_column_sums: n_labels = {G} outside 1..{LABEL_SUMS_MAX_G}")
+    L = _lib.lib()
+    nbytes = L.dbmm_workspace_bytes_label_colsums(N, D, G)
+    if nbytes == 0:
+        raise DbmmUnsupported(f"label_column_sums: no kernel for N = {N}, D = {D}, G = {G}")
+    ws = _empty((nbytes // 8,), device=x.device, dtype=torch.float64)                # the partials: sized by (N, D, G), not cached
+    sums = _empty((G, D), device=x.device, dtype=torch.float64)
+    counts = _empty((G,), device=x.device, dtype=torch.int64)
+    rc = L.dbmm_label_colsums(x.data_ptr(), labels.data_ptr(), sums.data_ptr(), counts.data_ptr(), N, D, G, ws.data_ptr(), nbytes, stream())
+    if rc == _lib.E_UNSUPPORTED:
+        raise DbmmUnsupported(f"label_column_sums: no kernel for N = {N}, D = {D}")
+    check(rc, "label_column_sums")
+    return sums, counts
+
+
+def _erase_rows_operand(what, x):
+    require_cuda(x)
+    _f32c(x, f"{what}: x")
+    if x.dim() != 2 or not 1 <= x.shape[0] <= 1 << 23:
+        raise _lib.DbmmError(f"{what}: x must be [N, D] with N in 1..2^23, got {tuple(x.shape)}")
+    N, D = x.shape
+    if D % 64 or D > 4096 or D == 0:
+        raise DbmmUnsupported(f"{what}: D = {D}; the kernel serves D % 64 == 0, D <= 4096")
+    if x.data_ptr() % 16:
+        raise _lib.DbmmError(f"{what}: x is not 16-byte aligned")
+    return N, D
+
+
+def erase_rows(x, center, A, B, out=None):
+    """y fp32 [N, D] = x - ((x - center) @ A.T) @ B in one read and one write of the rows (dbmm_erase_rows): A, B fp32 [R, D] with R
+    in 1..15, center fp32 [D], x fp32 [N, D] (D % 64 == 0, D <= 4096, N <= 2^23).  `out`: None (a new tensor), x itself (in place:
+    a row is read completely before it is written) or a tensor of x's shape that does not overlap x.  Nothing N x D is allocated
+    beyond the result.  A row's result depends on that row only: erasing a slice gives the bits of the slice, and in place gives
+    the bits of out of place."""
+    N, D = _erase_rows_operand("erase_rows", x)
+    for name, t in (("center", center), ("A", A), ("B", B)):
+        if not torch.is_tensor(t):
+            raise _lib.DbmmError(f"erase_rows: {name} must be a device tensor")
+        require_cuda(t)
+        _f32c(t, f"erase_rows: {name}")
+        if t.device != x.device:
+            raise _lib.DbmmError(f"erase_rows: {name} is on {t.device}, x on {x.device}")
+        if t.data_ptr() % 16:
+            raise _lib.DbmmError(f"erase_rows: {name} is not 16-byte aligned")
+    if center.dim() != 1 or center.shape[0] != D:
+        raise _lib.DbmmError(f"erase_rows: center must be [{D}], got {tuple(center.shape)}")
+    if A.dim() != 2 or B.dim() != 2 or A.shape[1] != D or tuple(B.shape) != tuple(A.shape) or not 1 <= A.shape[0] <= ERASE_MAX_R:
+        raise _lib.DbmmError(f"erase_rows: A and B must both be [R, {D}] with R in 1..{ERASE_MAX_R}, got {tuple(A.shape)} and {tuple(B.shape)}")
+    R = A.shape[0]
+    if out is None:
+        out = _empty((N, D), device=x.device, dtype=torch.float32)
+    else:
+        require_cuda(out)
+        _f32c(out, "erase_rows: out")
+        if tuple(out.shape) != (N, D) or out.device != x.device or out.data_ptr() % 16:
+            raise _lib.DbmmError(f"erase_rows: out must be a 16-byte aligned [{N}, {D}] tensor on {x.device}, got {tuple(out.shape)} on {out.device}")
+        lo, hi = out.data_ptr(), out.data_ptr() + N * D * 4
+        if out.data_ptr() != x.data_ptr() and lo < x.data_ptr() + N * D * 4 and x.data_ptr() < hi:
+            raise _lib.DbmmError("erase_rows: out overlaps x without being x; rows would be read after they were written")
+    rc = _lib.lib().dbmm_erase_rows(x.data_ptr(), center.data_ptr(), A.data_ptr(), B.data_ptr(), out.data_ptr(), N, D, R, stream())
+    if rc == _lib.E_UNSUPPORTED:
+        raise DbmmUnsupported(f"erase_rows: no kernel for N = {N}, D = {D}")
+    check(rc, "erase_rows")
+    return out
+
+
 # ---- fp16 mode of the transformer towers (csrc/f16_ops.hip) -------------------------------------------------------
 
 def _f16c(t):

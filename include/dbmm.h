@@ -954,6 +954,31 @@ int dbmm_kmeans_iterate(const float* x, int64_t N, int64_t D, int64_t K, int64_t
 int dbmm_kmeans_assign(const float* x, const float* centers, int32_t* labels, float* dmin, int64_t N, int64_t D, int64_t K,
                        void* stream);
 
+/* Linear concept erasure of the rows x fp32 [N][D] (contiguous): the moment that PCA's two (column sums, scatter) lack, and the
+ * application of a fitted eraser.  The reference has no counterpart.
+ *   dbmm_label_colsums  sums double [G][D]: sums[g][d] = sum over i with labels[i] == g of x[i][d], the RAW sums, and counts int64
+ *                       [G], from ONE read of x.  labels int64 [N], compared as 64 bits: a value outside [0, G) (-1, G, 2^32 + 1) is
+ *                       in no sum and no count.  Per (one of P row ranges, 256 columns) the rows are added in row order in float64
+ *                       from the first add (there is no fp32 chain); the partials are added in a fixed order (range order within
+ *                       each quarter of the ranges, then the quarters in order).  P = min(ceil(2048 / ceil(D / 256)), ceil(N / 64))
+ *                       depends on (N, D) only.  Two launches on `stream`, no memset, no floating-point atomics: two calls give
+ *                       the same bits.  The workspace holds the partials: float64 [P][G][D], then int64 [P][16].
+ *   dbmm_erase_rows     y[i][d] = x[i][d] - sum_k ((x[i] - center) . A[k]) B[k][d] for A, B fp32 [R][D], R in 1..15, in one read and
+ *                       one write of the rows; y may be x (a row is read completely before any of it is written) and must otherwise
+ *                       not overlap it.  A wave takes 4 / 2 / 1 rows (D <= 1024 / <= 2048 / above) and keeps them in registers:
+ *                       (x - center) in fp32, one fp32 fmaf chain per (row, k) over the lane's columns in column order, a fixed
+ *                       shuffle tree, t = sum_k s_k B[k][d] as one fmaf chain in k order, y = x - t.  A row's result depends on that
+ *                       row only: erasing a slice gives the bits of the slice.  One launch on `stream`, no workspace.
+ * Both: D % 64 != 0 or D > 4096: DBMM_E_UNSUPPORTED; N outside 1..2^23, G outside 1..16, R outside 1..15: DBMM_E_SHAPE; then null
+ * pointers: DBMM_E_ARG; a short workspace: DBMM_E_WORKSPACE; x, center, A, B, y or the workspace not 16-byte aligned (labels,
+ * sums, counts: 8-byte): DBMM_E_ALIGN.  Every check precedes the first launch.  dbmm_workspace_bytes_label_colsums is 0 for a
+ * shape that is not served. */
+size_t dbmm_workspace_bytes_label_colsums(int64_t N, int64_t D, int64_t G);
+int dbmm_label_colsums(const float* x, const int64_t* labels, double* sums, int64_t* counts, int64_t N, int64_t D, int64_t G,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int dbmm_erase_rows(const float* x, const float* center, const float* A, const float* B, float* y, int64_t N, int64_t D, int64_t R,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
