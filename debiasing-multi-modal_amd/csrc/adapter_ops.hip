@@ -371,6 +371,9 @@ extern "C" int dbmm_adapter_fwd(const float* x, const float* w1, const float* b1
     if (!x || !w1 || !b1 || !gamma || !beta || !w2 || !b2 || !h || !r || !z) return DBMM_E_ARG;
     if (!running_mean || !running_var) return DBMM_E_ARG;
     if (train && (!mean || !invstd)) return DBMM_E_ARG;
+    // before the first launch, as dbmm_adapter_bwd has it: the BatchNorm statistics kernel takes any H and updates the running
+    // statistics, so a width only dbmm_bn1d_relu refuses must not get that far
+    if (B <= 0 || D <= 0 || H <= 0 || (D & 3) || (H & 3) || (train && B < 2)) return DBMM_E_SHAPE;
     if (dbmm_adapter_fast_shape(B, D, H) && (!train || B >= 2) && dbmm_aligned16(x) && dbmm_aligned16(w1) && dbmm_aligned16(w2) && dbmm_aligned16(h) &&
         dbmm_aligned16(r) && dbmm_aligned16(z) && dbmm_aligned16(gamma) && dbmm_aligned16(beta) &&
         dbmm_aligned16(train ? mean : running_mean) && dbmm_aligned16(train ? invstd : running_var) && dbmm_opt(OPT_ADAPTER_STEP_FUSED))

@@ -165,7 +165,7 @@ struct Geo {
 // lanes, and all residual loads of a half tile are in flight together.  (The per-element path
 // below it was latency-bound at ~1 TB/s on the conv3 + residual layers.)
 // ---------------------------------------------------------------------------------------------
-template <int BM, int BN, int WAVES_M, int WAVES_N, int AMODE, int WMODE, int BK, int FAST, int FIXUP, int DMA>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int AMODE, int WMODE, int BK, int FAST, int FIXUP, int DMA, int CHAIN2 = 1>
 __device__ __forceinline__ void igemm_tile(const IgemmP& p, float* lds, int tile, int kb, int ke, float* partial,
                                            int fix_c0) {
     using G = Geo<BM, BN, WAVES_M, WAVES_N, BK>;
@@ -443,9 +443,13 @@ __device__ __forceinline__ void igemm_tile(const IgemmP& p, float* lds, int tile
     // product) that measured 5 - 6 x the rounding error of a blocked fp32 sum.  The tiles with at most two accumulator blocks per wave
     // (32 x 128, 128 x 32, 64 x 64, 128 x 64) on the FAST loader therefore move their running sums into a second set every 128
     // products, so that no chain is longer than 128 products plus K / 128 block sums; up to K = 128 nothing moves and the result is
-    // the single chain's.  (The 128 x 128 tile has no registers for a second set, and the generic loader's staging registers leave none
-    // at these occupancies either -- the second set spilled there: both keep the single chain.)
-    constexpr bool TWO_LEVEL = !FIXUP && FAST && TM * TN <= 2;
+    // the single chain's.  The generic loader's GEMM modes (AMODE 0 / 2: K tails, K-major operands -- the adapter's dr = dz W2 at K = D =
+    // 1024 measured 1.7e-06 on one chain against 3.1e-07 on the FAST loader, 5.6 x, and its dh missed 4 x torch's float32 error) do the
+    // same; their staging registers leave no room for the second set at the FAST loader's occupancy (it spilled there), so launch_cfg
+    // gives those instantiations one resident workgroup per CU fewer.  (The 128 x 128 tile has no registers for a second set and the
+    // generic loader's conv gather keeps its occupancy: both keep the single chain; so do the generic loader's stream-K kernels,
+    // CHAIN2 = 0, which cut K into shares anyway and are short of registers as it is.)
+    constexpr bool TWO_LEVEL = !FIXUP && CHAIN2 && (FAST || AMODE != 1) && TM * TN <= 2;
     constexpr int FLUSH = 128 / BK;
     f32x16 tot[TWO_LEVEL ? TM : 1][TWO_LEVEL ? TN : 1];
     if constexpr (TWO_LEVEL) {
@@ -1316,7 +1320,7 @@ __global__ __launch_bounds__(256, MINB) void igemm_f32_kernel(const IgemmP p_in)
             float* partial = (kb == 0 && ke == nk)
                                  ? nullptr
                                  : p.sk_ws + ((size_t)blockIdx.x * 2 + (seg ? 1 : 0)) * (size_t)(BM * BN);
-            igemm_tile<BM, BN, WAVES_M, WAVES_N, AMODE, WMODE, BK, FAST, 0, DMA>(p, lds, tile, kb, ke, partial, 0);
+            igemm_tile<BM, BN, WAVES_M, WAVES_N, AMODE, WMODE, BK, FAST, 0, DMA, FAST>(p, lds, tile, kb, ke, partial, 0);
             u += ke - kb;
         }
     }
@@ -1476,10 +1480,16 @@ int launch_cfg(IgemmP& p, hipStream_t s, int nbatch, void* ws, size_t ws_bytes) 
         }
     }
     if (!launched) {
-        if (p.sk_blocks)
+        // the generic loader's GEMM modes keep a second accumulator set (igemm_tile, TWO_LEVEL): 77 - 90 VGPRs + 16 per accumulator block
+        // against the 80 / 96 that 6 / 5 resident workgroups leave at the 16-deep chunk, so one workgroup per CU fewer.  The stream-K
+        // kernels of this loader keep the single chain and MINB.
+        constexpr int MB_G = (AMODE != 1 && BK == 16 && (BM / WM / 32) * (BN / WN / 32) <= 2) ? MINB - 1 : MINB;
+        if (p.sk_blocks) {
             hipLaunchKernelGGL((igemm_f32_kernel<BM, BN, WM, WN, AMODE, WMODE, BK, MINB, 0, 1, 0>), grid, dim3(256), 0, s, p);
-        else
-            hipLaunchKernelGGL((igemm_f32_kernel<BM, BN, WM, WN, AMODE, WMODE, BK, MINB, 0, 0, 0>), grid, dim3(256), 0, s, p);
+        } else {
+            g_last_cfg[7] = MB_G;
+            hipLaunchKernelGGL((igemm_f32_kernel<BM, BN, WM, WN, AMODE, WMODE, BK, MB_G, 0, 0, 0>), grid, dim3(256), 0, s, p);
+        }
     }
     DBMM_CHECK_LAUNCH();
     if (p.sk_blocks) {

@@ -983,6 +983,12 @@ def adapter_fwd(x, w1, b1, gamma, beta, running_mean, running_var, nbt, w2, b2, 
     _f32c(x)
     B, D = x.shape
     H = w1.shape[0]
+    # the library refuses these too (DBMM_E_SHAPE, before its first launch); here the message can name the limit
+    if D % 4 or H % 4:
+        raise _lib.DbmmError(f"adapter_fwd: input width {D} and hidden width {H}: both must be multiples of 4 (the kernels read and "
+                             "write rows in 16-byte pieces)")
+    if train and B < 2:
+        raise _lib.DbmmError(f"adapter_fwd: train-mode BatchNorm1d needs at least 2 rows, got {B}")
     dev = x.device
     h = _empty((B, H), device=dev, dtype=torch.float32)
     r = _empty((B, H), device=dev, dtype=torch.float32)

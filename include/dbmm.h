@@ -473,7 +473,9 @@ int dbmm_bn1d_relu(const float* h, const float* mean, const float* invstd, const
 
 /* Adapter.forward (final_main.py:173): z = Linear2(relu(bn(Linear1(x)))).
  * train != 0: batch statistics (saved to mean/invstd, running stats updated).
- * Saves h (pre-BN) and r (post-ReLU) for the backward pass. */
+ * Saves h (pre-BN) and r (post-ReLU) for the backward pass.
+ * B <= 0, D <= 0, H <= 0, D % 4 != 0, H % 4 != 0, or train with B < 2: DBMM_E_SHAPE, like dbmm_adapter_bwd.  The shape is checked
+ * before the first launch: a refused call leaves running_mean, running_var and nbt as they were. */
 int dbmm_adapter_fwd(const float* x, const float* w1, const float* b1, const float* gamma,
                      const float* beta, float* running_mean, float* running_var, int64_t* nbt,
                      const float* w2, const float* b2, float* h, float* mean, float* invstd,

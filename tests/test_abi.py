@@ -54,3 +54,10 @@ def test_argument_validation_without_gpu(built):
     assert L.dbmm_mha_core(p, p, 1, 4, 100, 2, 0, None) == -1          # E != heads*64
     assert L.dbmm_l2norm_sim_ce_fwd(p, None, 0.5, p, None, 0.01, p, None, None, None, None, 4, 8, 9, None) == -1
     assert L.dbmm_sgd_momentum(0, None, None, None, None, 0.1, 0.9, 0.0, 1, None) == -4
+    # dbmm_adapter_fwd checks its shape before its first launch (a hidden width of 30 used to reach the BatchNorm statistics kernel,
+    # which advanced the running statistics before dbmm_bn1d_relu refused): (B, D, H, train) -> DBMM_E_SHAPE, with host pointers
+    fwd = lambda B, D, H, train: L.dbmm_adapter_fwd(*([p] * 15), B, D, H, train, 1e-5, 0.1, None)
+    for B, D, H, train in ((8, 1024, 30, 1), (8, 1024, 30, 0), (8, 1022, 128, 1), (8, 6, 4, 0), (1, 1024, 128, 1), (1, 8, 4, 1),
+                           (0, 8, 4, 0), (8, 0, 4, 1), (8, 8, 0, 1), (-1, 8, 4, 0)):
+        assert fwd(B, D, H, train) == -1, (B, D, H, train)
+    assert L.dbmm_adapter_fwd(*([p] * 14), None, 8, 1024, 30, 1, 1e-5, 0.1, None) == -4          # a null pointer is still named first
