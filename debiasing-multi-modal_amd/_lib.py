@@ -49,9 +49,9 @@ KERNEL_SOURCES = (
     ("sym_eig_", ("sym_eig.hip", "common.h")),
     ("supcon_", ("supcon.hip", "common.h")),
     ("sets_", ("supcon_sets.hip", "common.h")),
-    ("kmeans_", ("kmeans.hip", "common.h")),
-    ("label_", ("erase.hip", "common.h")),
-    ("erase_rows_", ("erase.hip", "common.h")),
+    ("kmeans_", ("kmeans.hip", "label_sums.h", "common.h")),
+    ("label_", ("erase.hip", "label_sums.h", "common.h")),
+    ("erase_rows_", ("erase.hip", "label_sums.h", "common.h")),
 )
 
 

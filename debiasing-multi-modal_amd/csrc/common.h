@@ -1,14 +1,14 @@
 // Shared helpers for the gfx950 kernels of libdbmm_hip.so, each defined ONCE here:
 //   - the vector typedefs of the MFMA fragments and 8 / 16-byte accesses (f16x8, u32x4, ...);
 //   - DBMM_N_CU and dbmm_cut_slices: persistent-grid sizing;
-//   - wave_sum / wave_max, xcd_first / xcd_remap: wave reductions, the split of tile ids over the XCDs and the tile -> workgroup map;
+//   - wave_sum / wave_sum_f64 / wave_max, xcd_first / xcd_remap: wave reductions, the split of tile ids over the XCDs and the tile -> workgroup map;
 //   - desc / glds16 with OOR and EXT_LIM: rebased buffer descriptors and LDS-DMA loads;
 //   - scale_exp / pow2f / split2h_pair / frag / pack2: the fp16 (hi, lo) split under an exact power-of-two scale, the
 //     library's precision contract.  Every parity kernel splits with THESE functions.
 // plus the internal C entries that one kernel file calls in another.
 // What only the persistent 256-tile kernels share is defined once in persistent_tiles.h (tile_walk, work_item, slice_store / slice_sum,
-// absmax_fold, ring_rows, plan_tiles), the fp16 ring of two of them in fp16_ring.inc, and the epilogues that a main kernel and its fixup
-// kernel both run in gemm_f16_8ph_epilogue.inc, gemm_pair_8ph_epilogue.inc and conv3x3_halo8_epilogue.inc.
+// absmax_fold, ring_rows, plan_tiles), the fp16 ring of two of them in fp16_ring.inc, the per-label column sums of k-means and the label sums
+// and their fixed-order merge in label_sums.h, and the epilogues that a main kernel and its fixup kernel both run in gemm_f16_8ph_epilogue.inc, gemm_pair_8ph_epilogue.inc and conv3x3_halo8_epilogue.inc.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,8 +83,20 @@ float* dbmm_supcon_spare(void* workspace, int64_t B);
 
 static inline bool dbmm_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// fp32 rows [N][D] of the analysis kernels that give a lane whole float4s of 64-column groups (covariance.hip, erase.hip)
+static inline int dbmm_rows_shape(int64_t N, int64_t D) {
+    if (D <= 0 || (D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
+    if (N < 1 || N > (1 << 23)) return DBMM_E_SHAPE;
+    return DBMM_OK;
+}
+
 // wave64 butterfly sum / max (all lanes get the result)
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;

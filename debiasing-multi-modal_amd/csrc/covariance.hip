@@ -166,17 +166,11 @@ void launch_project(const float* x, const float* c, const float* basis, float* y
     hipLaunchKernelGGL(project_rows_kernel<K>, dim3(grid), dim3(256), 0, s, x, c, basis, y, N, D);
 }
 
-inline int pca_shape(int64_t N, int64_t D) {
-    if (D <= 0 || (D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
-    if (N < 1 || N > (1 << 23)) return DBMM_E_SHAPE;
-    return DBMM_OK;
-}
-
 }  // namespace
 
 // see include/dbmm.h
 extern "C" size_t dbmm_workspace_bytes_covariance(int64_t N, int64_t D) {
-    if (pca_shape(N, D) != DBMM_OK) return 0;
+    if (dbmm_rows_shape(N, D) != DBMM_OK) return 0;
     int P, rows;
     cov_ranges(N, D, P, rows);
     return (size_t)P * (size_t)cov_tiles(D) * TILE_BYTES;
@@ -185,7 +179,7 @@ extern "C" size_t dbmm_workspace_bytes_covariance(int64_t N, int64_t D) {
 // see include/dbmm.h
 extern "C" int dbmm_covariance(const float* x, const float* center, double* scatter, int64_t N, int64_t D, void* workspace, size_t workspace_bytes,
                                void* stream) {
-    const int rc = pca_shape(N, D);
+    const int rc = dbmm_rows_shape(N, D);
     if (rc != DBMM_OK) return rc;
     if (!x || !center || !scatter || !workspace) return DBMM_E_ARG;
     if (workspace_bytes < dbmm_workspace_bytes_covariance(N, D)) return DBMM_E_WORKSPACE;
@@ -203,7 +197,7 @@ extern "C" int dbmm_covariance(const float* x, const float* center, double* scat
 
 // see include/dbmm.h
 extern "C" int dbmm_project_rows(const float* x, const float* center, const float* basis, float* y, int64_t N, int64_t D, int64_t K, void* stream) {
-    const int rc = pca_shape(N, D);
+    const int rc = dbmm_rows_shape(N, D);
     if (rc != DBMM_OK) return rc;
     if (K < 1 || K > 8) return DBMM_E_SHAPE;
     if (!x || !center || !basis || !y) return DBMM_E_ARG;

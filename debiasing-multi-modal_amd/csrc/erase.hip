@@ -3,17 +3,9 @@
 //   sums[g][d]  = sum over i with labels[i] == g of x[i][d],   double [G][D], and counts[g], int64 [G]: one read of x
 //   y[i][d]     = x[i][d] - sum_k ((x[i] - c) . A[k]) B[k][d],  float [N][D], R = 1..15: one read and one write of x, y may be x
 //
-// Label sums, two launches, no memset, no floating-point atomics.  The structure is the one kmeans_sums_kernel documents
-// (kmeans.hip), restated here for int64 labels that nobody fitted:
-//   label_sums_kernel<KP>   a wave owns (one of P row ranges, a slab of 256 columns), a lane a float4 of columns, and walks its rows
-//                           in order, sixteen loads in flight.  FLOAT64 FROM THE FIRST ADD.  A row's label is wave-uniform and is
-//                           compared AS 64 BITS with every j < KP: the row goes into acc[j] as fma(w_j, x, acc[j]) with the scalar
-//                           w_j = 1 under label == j and 0 otherwise -- 1 x v is v and + 0 x v changes no bit --, so these are KP
-//                           predicated adds on register-resident accumulators: no dynamic register index, no branch in the loop.
-//                           A label outside [0, G) (-1, G, 2^32 + 1) matches no j < G: it is in no sum and no count.
-//   label_merge_kernel      adds the P partials in a fixed order (each quarter of the ranges in range order by one wave, then the
-//                           quarters in order) and writes the RAW sums and the counts; the caller divides.
-// P depends on (N, D) only (ls_ranges), so two calls add the same numbers in the same order.
+// Label sums: label_sums_kernel<KP> and label_merge_kernel are the unit body and the fixed-order merge of label_sums.h on int64 labels that
+// nobody fitted, compared AS 64 BITS: a label outside [0, G) (-1, G, 2^32 + 1) is in no sum and no count.  The merge writes the RAW sums
+// and the counts; the caller divides.
 //
 // Erasure: erase_rows_kernel<RP, PR, NCH>, one launch.  It starts from project_rows_kernel (covariance.hip): a wave per group of PR
 // rows, float4 loads, one fp32 fmaf chain per (row, k) over the lane's columns in column order, a fixed butterfly.  The lane KEEPS
@@ -23,91 +15,27 @@
 // the PR x NCH float4 of the rows fit a lane (PR NCH <= 16), so it depends on D alone and a row's arithmetic does not depend on
 // its neighbours, on N or on where the row sits: erasing a slice gives the bits of the slice.  The R projections are padded to
 // RP = 1 / 2 / 4 / 8 / 16 accumulators per row, as k-means pads K.
-#include "common.h"
+#include "label_sums.h"
 
 namespace {
 
-constexpr int SLAB_COLS = 256;             // columns of a wave: a float4 per lane
-constexpr int UNITS = 2048;                // (range, column slab) units aimed at: eight waves per CU
-constexpr int MIN_RANGE = 64;              // a row range is not cut below 64 rows
-constexpr int GMAX = 16;
-constexpr int DEPTH = 16;                  // rows in flight per wave of the sums kernel
+using namespace label_sums;
+
 constexpr int RMAX = 15;
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-inline int ls_slabs(long long D) { return (int)((D + SLAB_COLS - 1) / SLAB_COLS); }
-// row ranges P and rows per range, from (N, D) alone
-inline void ls_ranges(long long N, long long D, int& P, int& rows) {
-    const long long slabs = ls_slabs(D);
-    long long p = (UNITS + slabs - 1) / slabs, cap = (N + MIN_RANGE - 1) / MIN_RANGE;
-    p = p < cap ? p : cap;
-    p = p < 1 ? 1 : p;
-    P = (int)p;
-    rows = (int)((N + p - 1) / p);
-}
 
 // workspace, in bytes: partial sums float64 [P][G][D] | partial counts int64 [P][16]
 inline size_t ls_bytes(int64_t N, int64_t D, int64_t G) {
     int P, rows;
-    ls_ranges(N, D, P, rows);
-    return (size_t)P * G * D * 8 + (size_t)P * GMAX * 8;
+    ranges(N, D, P, rows);
+    return part_bytes(P, G, D) + count_bytes(P);
 }
 
 // ---- per-label column sums, per (row range, column slab) ------------------------------------------------------------------------------------
 template <int KP>
 __global__ __launch_bounds__(256) void label_sums_kernel(const float* __restrict__ x, const long long* __restrict__ labels, double* __restrict__ part,
                                                          long long* __restrict__ cntp, int N, int D, int G, int P, int rows, int slabs) {
-    const int lane = threadIdx.x & 63;
-    const int unit = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-    if (unit >= P * slabs) return;
-    const int p = unit / slabs, s = unit - p * slabs;
-    const int col = s * SLAB_COLS + lane * 4;
-    const bool active = col < D;
-    const int lcol = active ? col : 0;                                           // a lane past the last column loads column 0 and stores nothing
-    const int r0 = (int)min((long long)p * rows, (long long)N), r1 = (int)min((long long)r0 + rows, (long long)N);
-    double acc[KP][4];
-    int cnt[KP];
-#pragma unroll
-    for (int j = 0; j < KP; ++j) {
-        cnt[j] = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[j][e] = 0.0;
-    }
-    for (int r = r0; r < r1; r += DEPTH) {
-        long long lab[DEPTH];
-        f32x4 xv[DEPTH];
-#pragma unroll
-        for (int u = 0; u < DEPTH; ++u) {
-            const int row = min(r + u, r1 - 1);                                  // past the end: a row read again and added nowhere
-            lab[u] = r + u < r1 ? labels[row] : -1LL;                            // wave-uniform, 64 bits
-            xv[u] = *(const f32x4*)(x + (size_t)row * D + lcol);
-        }
-#pragma unroll
-        for (int u = 0; u < DEPTH; ++u) {
-            const double v[4] = {(double)xv[u][0], (double)xv[u][1], (double)xv[u][2], (double)xv[u][3]};
-#pragma unroll
-            for (int j = 0; j < KP; ++j) {                                       // row order within every accumulator
-                const bool hit = lab[u] == (long long)j;                         // the 64-bit comparison: 2^32 + 1 is not label 1
-                const double w = hit ? 1.0 : 0.0;                                // a scalar: 1 x v is v, and + 0 x v changes no bit
-                cnt[j] += hit ? 1 : 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[j][e] = fma(w, v[e], acc[j][e]);
-            }
-        }
-    }
-    if (active) {
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            if (j >= G) continue;
-            f64x2* o = (f64x2*)(part + ((size_t)p * G + j) * D + col);           // (16-byte stores: the workspace's alignment)
-            o[0] = (f64x2){acc[j][0], acc[j][1]};
-            o[1] = (f64x2){acc[j][2], acc[j][3]};
-        }
-    }
-    if (s != 0 || lane != 0) return;
-#pragma unroll
-    for (int j = 0; j < KP; ++j) cntp[(size_t)p * GMAX + j] = cnt[j];            // the first column slab: the range's row counts (KP <= 16 words)
+    const int unit = wave_unit();
+    if (unit < P * slabs) unit_sums<KP, long long>(unit, x, labels, part, cntp, N, D, G, rows, slabs);
 }
 
 // ---- merge: the raw sums and the counts ---------------------------------------------------------------------------------------------------------
@@ -117,39 +45,19 @@ __global__ __launch_bounds__(256) void label_merge_kernel(double* __restrict__ s
     __shared__ long long red[4];
     __shared__ double quarter[4][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = blockIdx.y, d = blockIdx.x * 64 + lane;
-    // a fixed order: each quarter of the ranges in range order, then the quarters in order; sixteen loads in flight per thread
-    const int pq = (P + 3) / 4, p0 = min(w * pq, P), p1 = min(p0 + pq, P);
-    const size_t stride = (size_t)G * D;
-    const double* in = part + (size_t)j * D + (d < D ? d : 0);
-    double sum = 0.0;
-    for (int b = p0; b < p1; b += 16) {
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = in[(size_t)min(b + u, p1 - 1) * stride];
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-            if (b + u < p1) sum += v[u];
-    }
-    quarter[w][lane] = sum;
-    __syncthreads();
-    if (w == 0 && d < D) sums[(size_t)j * D + d] = ((quarter[0][lane] + quarter[1][lane]) + quarter[2][lane]) + quarter[3][lane];
+    quarter_sums(part + (size_t)j * D + (d < D ? d : 0), (size_t)G * D, P, quarter);
+    if (w == 0 && d < D) sums[(size_t)j * D + d] = merge_sum(quarter, lane);
     if (blockIdx.x != 0) return;
-    long long n = 0;                                                             // integers: the order does not matter
-    for (int p = threadIdx.x; p < P; p += 256) n += cntp[(size_t)p * GMAX + j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    if (lane == 0) red[w] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[j] = red[0] + red[1] + red[2] + red[3];
+    const long long n = merge_count(cntp, j, P, red);
+    if (threadIdx.x == 0) counts[j] = n;
 }
 
 template <int KP>
 void launch_label_sums(const float* x, const int64_t* labels, char* ws, int N, int D, int G, hipStream_t s) {
     int P, rows;
-    ls_ranges(N, D, P, rows);
-    const int slabs = ls_slabs(D), units = P * slabs;
-    hipLaunchKernelGGL(label_sums_kernel<KP>, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, x, (const long long*)labels, (double*)ws,
-                       (long long*)(ws + (size_t)P * G * D * 8), N, D, G, P, rows, slabs);
+    ranges(N, D, P, rows);
+    hipLaunchKernelGGL(label_sums_kernel<KP>, dim3(sums_grid(P, D)), dim3(256), 0, s, x, (const long long*)labels, (double*)ws,
+                       (long long*)(ws + part_bytes(P, G, D)), N, D, G, P, rows, slabs(D));
 }
 
 // ---- erasure: y = x - sum_k ((x - c) . A_k) B_k -------------------------------------------------------------------------------------------------
@@ -235,26 +143,20 @@ void dispatch_erase(const float* x, const float* c, const float* A, const float*
     else launch_erase<RP, 1, 16>(x, c, A, B, y, N, D, R, s);
 }
 
-inline int erase_shape(int64_t N, int64_t D) {
-    if (D <= 0 || (D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
-    if (N < 1 || N > (1 << 23)) return DBMM_E_SHAPE;
-    return DBMM_OK;
-}
-
 }  // namespace
 
 // see include/dbmm.h
 extern "C" size_t dbmm_workspace_bytes_label_colsums(int64_t N, int64_t D, int64_t G) {
-    if (erase_shape(N, D) != DBMM_OK || G < 1 || G > GMAX) return 0;
+    if (dbmm_rows_shape(N, D) != DBMM_OK || G < 1 || G > MAX_LABELS) return 0;
     return ls_bytes(N, D, G);
 }
 
 // see include/dbmm.h
 extern "C" int dbmm_label_colsums(const float* x, const int64_t* labels, double* sums, int64_t* counts, int64_t N, int64_t D, int64_t G,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-    const int rc = erase_shape(N, D);
+    const int rc = dbmm_rows_shape(N, D);
     if (rc != DBMM_OK) return rc;
-    if (G < 1 || G > GMAX) return DBMM_E_SHAPE;
+    if (G < 1 || G > MAX_LABELS) return DBMM_E_SHAPE;
     if (!x || !labels || !sums || !counts || !workspace) return DBMM_E_ARG;
     if (workspace_bytes < ls_bytes(N, D, G)) return DBMM_E_WORKSPACE;
     if (!dbmm_aligned16(x) || !dbmm_aligned16(workspace) || (((uintptr_t)labels) & 7u) || (((uintptr_t)sums) & 7u) || (((uintptr_t)counts) & 7u))
@@ -267,9 +169,9 @@ extern "C" int dbmm_label_colsums(const float* x, const int64_t* labels, double*
     else launch_label_sums<16>(x, labels, ws, (int)N, (int)D, (int)G, s);
     DBMM_CHECK_LAUNCH();
     int P, rows;
-    ls_ranges(N, D, P, rows);
+    ranges(N, D, P, rows);
     hipLaunchKernelGGL(label_merge_kernel, dim3((unsigned)(D / 64), (unsigned)G), dim3(256), 0, s, sums, (long long*)counts, (const double*)ws,
-                       (const long long*)(ws + (size_t)P * G * D * 8), (int)D, (int)G, P);
+                       (const long long*)(ws + part_bytes(P, G, D)), (int)D, (int)G, P);
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
 }
@@ -277,7 +179,7 @@ extern "C" int dbmm_label_colsums(const float* x, const int64_t* labels, double*
 // see include/dbmm.h
 extern "C" int dbmm_erase_rows(const float* x, const float* center, const float* A, const float* B, float* y, int64_t N, int64_t D, int64_t R,
                                void* stream) {
-    const int rc = erase_shape(N, D);
+    const int rc = dbmm_rows_shape(N, D);
     if (rc != DBMM_OK) return rc;
     if (R < 1 || R > RMAX) return DBMM_E_SHAPE;
     if (!x || !center || !A || !B || !y) return DBMM_E_ARG;

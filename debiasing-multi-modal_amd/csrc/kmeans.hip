@@ -8,62 +8,37 @@
 //                             other, and the differences have no cancellation to manage (the |x|^2 + |c|^2 - 2 x.c form does).  A row's
 //                             result depends on that row and the centres only.  Writes label[i] (lowest index on an exact tie) and
 //                             dmin[i], and counts the rows whose label changed: one integer atomic per workgroup of 64 rows.
-//   kmeans_sums_kernel<KP>    per-cluster column sums IN FLOAT64 FROM THE FIRST ADD: a wave owns (one of P row ranges, a slab of 256
-//                             columns), a lane a float4 of columns, and walks its rows in order, sixteen loads in flight.  The label of a
-//                             row is wave-uniform; the row goes into acc[j] as fma(w_j, x, acc[j]) with the scalar w_j = 1 under
-//                             label == j and 0 otherwise, for each j: 1 x v is v and + 0 x v changes no bit, so these are K
-//                             predicated adds on register-resident accumulators at one v_fma_f64 each -- no dynamic register index,
-//                             no branch in the loop.  (A row that is not finite therefore reaches every centre, not one; such a fit is
-//                             lost either way.)  The covariance kernel's rule -- no fp32 chain longer than 1024 rows -- holds with
-//                             nothing to fold: there is no fp32 chain.  fp32 accumulators, centred or not, miss a centre entry near
-//                             zero by many of ITS ulps when the rows' entries cancel; float64 ones give the rounding of the mean.
-//                             The first slab's wave also writes the range's int64 row counts and its float64 sum of dmin
-//                             (lane-strided, a fixed butterfly).  Its very first wave latches the changed-label counter for the merge
-//                             and resets it with plain stores.
-//   kmeans_merge_kernel       adds the P partials in a fixed order (each quarter of the ranges in range order by one wave, then the
-//                             quarters in order), c_j <- fp32(sum_j / n_j) in float64, unless the latched counter is 0: then no
-//                             label moved, the state becomes `converged` and the centres stay the ones the labels, dmin and the
-//                             inertia were computed against.  A cluster with no rows keeps its centre and reports count 0.  One
-//                             workgroup writes the status: iterations, changed rows, inertia (a fixed order too), counts.
-// P depends on (N, D) only (km_ranges), so two runs add the same numbers in the same order: no floating-point atomics, no memset.
+//   kmeans_sums_kernel<KP>    per-cluster column sums IN FLOAT64 FROM THE FIRST ADD, per (one of P row ranges, slab of 256 columns): the unit
+//                             body of label_sums.h on the int labels of the assignment.  The first slab's wave also writes the range's
+//                             float64 sum of dmin (lane-strided, a fixed butterfly).  The very first wave latches the changed-label
+//                             counter for the merge and resets it with plain stores.
+//   kmeans_merge_kernel       adds the P partials in label_sums.h's fixed order, c_j <- fp32(sum_j / n_j) in float64, unless the latched
+//                             counter is 0: then no label moved, the state becomes `converged` and the centres stay the ones the labels,
+//                             dmin and the inertia were computed against.  A cluster with no rows keeps its centre and reports count 0.
+//                             One workgroup writes the status: iterations, changed rows, inertia (a fixed order too), counts.
+// P depends on (N, D) only (label_sums::ranges), so two runs add the same numbers in the same order: no floating-point atomics, no memset.
 //
 // The state word lives in the workspace: every kernel reads it first and returns at once unless it is `running`, so iterations enqueued
 // after convergence are no-ops and the result does not depend on how the host cuts the iterations into calls.  Inside one launch nobody
 // reads a word that another workgroup of that launch writes, except the state itself in the merge, which only ever moves to
 // `converged` there -- when no workgroup of the merge has anything left to write.  That is why the counter is latched by the sums
 // kernel: a merge workgroup that reset it could be overtaken by one that has yet to read it.
-#include "common.h"
+#include "label_sums.h"
 
 namespace {
+
+using namespace label_sums;
 
 constexpr int PR = 4;                      // rows per wave step of the assignment
 constexpr int WG_STEPS = 4;                // steps per wave: a workgroup assigns 4 waves x 4 steps x 4 rows
 constexpr int WG_ROWS = 4 * WG_STEPS * PR;
-constexpr int SLAB_COLS = 256;             // columns of a wave of the sums kernel: a float4 per lane
-constexpr int UNITS = 2048;                // (range, column slab) units aimed at: eight waves per CU
-constexpr int MIN_RANGE = 64;              // a row range is not cut below 64 rows
-constexpr int KMAX = 16;
-constexpr int DEPTH = 16;                  // rows in flight per wave of the sums kernel
 
 // status block, 8-byte words at offset 0 of the workspace (include/dbmm.h documents it: Python reads it)
 constexpr int ST_ITER = 0, ST_STATE = 1, ST_CHANGED = 2, ST_INERTIA = 3, ST_COUNTS = 4, ST_COUNTER = 20, ST_LATCH = 21;
 constexpr int ST_WORDS = 32;
 constexpr long long RUNNING = 0, CONVERGED = 1;
 
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
 inline size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-inline int km_slabs(long long D) { return (int)((D + SLAB_COLS - 1) / SLAB_COLS); }
-// row ranges P and rows per range, from (N, D) alone
-inline void km_ranges(long long N, long long D, int& P, int& rows) {
-    const long long slabs = km_slabs(D);
-    long long p = (UNITS + slabs - 1) / slabs, cap = (N + MIN_RANGE - 1) / MIN_RANGE;
-    p = p < cap ? p : cap;
-    p = p < 1 ? 1 : p;
-    P = (int)p;
-    rows = (int)((N + p - 1) / p);
-}
-
 // workspace, in bytes: status | centres fp32 [K][D] | labels int32 [N] | dmin fp32 [N] | partial sums float64 [P][K][D] |
 // partial counts int64 [P][16] | partial inertia float64 [P]; every part starts 16-byte aligned
 struct Layout {
@@ -72,21 +47,15 @@ struct Layout {
 };
 inline Layout layout(int64_t N, int64_t D, int64_t K) {
     Layout l;
-    km_ranges(N, D, l.P, l.rows);
+    ranges(N, D, l.P, l.rows);
     l.c = ST_WORDS * 8;
     l.lab = l.c + (size_t)K * D * 4;
     l.dmin = l.lab + pad16((size_t)N * 4);
     l.part = l.dmin + pad16((size_t)N * 4);
-    l.cnt = l.part + (size_t)l.P * K * D * 8;
-    l.inert = l.cnt + (size_t)l.P * KMAX * 8;
+    l.cnt = l.part + part_bytes(l.P, K, D);
+    l.inert = l.cnt + count_bytes(l.P);
     l.total = l.inert + pad16((size_t)l.P * 8);
     return l;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // ---- begin: the start centres, labels = -1 (every row changes in the first assignment), a cleared status ----------------------------
@@ -167,81 +136,22 @@ __global__ __launch_bounds__(256) void kmeans_sums_kernel(const float* __restric
                                                           double* __restrict__ part, long long* __restrict__ cntp, double* __restrict__ inert,
                                                           long long* __restrict__ st, int N, int D, int K, int P, int rows, int slabs) {
     if (st[ST_STATE] != RUNNING) return;
-    const int lane = threadIdx.x & 63;
-    const int unit = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63, unit = wave_unit();
     if (unit == 0 && lane == 0) {                                                // this iteration's assignment is complete: latch its count
         st[ST_LATCH] = st[ST_COUNTER];
         st[ST_COUNTER] = 0;
     }
     if (unit >= P * slabs) return;
-    const int p = unit / slabs, s = unit - p * slabs;
-    const int col = s * SLAB_COLS + lane * 4;
-    const bool active = col < D;
-    const int lcol = active ? col : 0;                                           // a lane past the last column loads column 0 and stores nothing
-    const int r0 = (int)min((long long)p * rows, (long long)N), r1 = (int)min((long long)r0 + rows, (long long)N);
-    double acc[KP][4];
-    int cnt[KP];
-#pragma unroll
-    for (int j = 0; j < KP; ++j) {
-        cnt[j] = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[j][e] = 0.0;
-    }
-    for (int r = r0; r < r1; r += DEPTH) {
-        int lab[DEPTH];
-        f32x4 xv[DEPTH];
-#pragma unroll
-        for (int u = 0; u < DEPTH; ++u) {
-            const int row = min(r + u, r1 - 1);                                  // past the end: a row read again and added nowhere
-            lab[u] = r + u < r1 ? labels[row] : -1;                              // wave-uniform
-            xv[u] = *(const f32x4*)(x + (size_t)row * D + lcol);
-        }
-#pragma unroll
-        for (int u = 0; u < DEPTH; ++u) {
-            const double v[4] = {(double)xv[u][0], (double)xv[u][1], (double)xv[u][2], (double)xv[u][3]};
-#pragma unroll
-            for (int j = 0; j < KP; ++j) {                                       // row order within every accumulator
-                const double w = lab[u] == j ? 1.0 : 0.0;                        // a scalar: 1 x v is v, and + 0 x v changes no bit
-                cnt[j] += lab[u] == j ? 1 : 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[j][e] = fma(w, v[e], acc[j][e]);
-            }
-        }
-    }
-    if (active) {
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            if (j >= K) continue;
-            f64x2* o = (f64x2*)(part + ((size_t)p * K + j) * D + col);           // (16-byte stores: the workspace's alignment)
-            o[0] = (f64x2){acc[j][0], acc[j][1]};
-            o[1] = (f64x2){acc[j][2], acc[j][3]};
-        }
-    }
-    if (s != 0) return;
-    // the first column slab: the range's row counts and its sum of dmin
+    const Unit u = unit_sums<KP, int>(unit, x, labels, part, cntp, N, D, K, rows, slabs);
+    if (u.s != 0) return;
+    // the first column slab: the range's sum of dmin
     double a = 0.0;
-    for (int i = r0 + lane; i < r1; i += 64) a += (double)dmin[i];
+    for (int i = u.r0 + lane; i < u.r1; i += 64) a += (double)dmin[i];
     a = wave_sum_f64(a);
-    if (lane == 0) {
-        inert[p] = a;
-#pragma unroll
-        for (int j = 0; j < KP; ++j) cntp[(size_t)p * KMAX + j] = cnt[j];
-    }
+    if (lane == 0) inert[u.p] = a;
 }
 
 // ---- merge: new centres, the status ------------------------------------------------------------------------------------------------------------
-// rows of cluster j over all ranges: every thread of the workgroup gets the sum (integers: the order does not matter)
-__device__ __forceinline__ long long merge_count(const long long* __restrict__ cntp, int j, int P, long long* red) {
-    long long n = 0;
-    for (int p = threadIdx.x; p < P; p += 256) n += cntp[(size_t)p * KMAX + j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    __syncthreads();                                                             // the previous call's sums have been read
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // grid (ceil(D / 64), K), 256 threads: a lane owns one entry of one centre, the four waves a quarter of the ranges each
 __global__ __launch_bounds__(256) void kmeans_merge_kernel(float* __restrict__ c, const double* __restrict__ part, const long long* __restrict__ cntp,
                                                            const double* __restrict__ inert, long long* __restrict__ st, int D, int K, int P) {
@@ -252,23 +162,8 @@ __global__ __launch_bounds__(256) void kmeans_merge_kernel(float* __restrict__ c
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = blockIdx.y, d = blockIdx.x * 64 + lane;
     if (changed != 0) {
         const long long n = merge_count(cntp, j, P, red);
-        // a fixed order: each quarter of the ranges in range order, then the quarters in order; sixteen loads in flight per thread
-        const int pq = (P + 3) / 4, p0 = min(w * pq, P), p1 = min(p0 + pq, P);
-        const size_t stride = (size_t)K * D;
-        const double* in = part + (size_t)j * D + (d < D ? d : 0);
-        double sum = 0.0;
-        for (int b = p0; b < p1; b += 16) {
-            double v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = in[(size_t)min(b + u, p1 - 1) * stride];
-#pragma unroll
-            for (int u = 0; u < 16; ++u)
-                if (b + u < p1) sum += v[u];
-        }
-        quarter[w][lane] = sum;
-        __syncthreads();
-        if (w == 0 && n > 0 && d < D)
-            c[(size_t)j * D + d] = (float)((((quarter[0][lane] + quarter[1][lane]) + quarter[2][lane]) + quarter[3][lane]) / (double)n);
+        quarter_sums(part + (size_t)j * D + (d < D ? d : 0), (size_t)K * D, P, quarter);
+        if (w == 0 && n > 0 && d < D) c[(size_t)j * D + d] = (float)(merge_sum(quarter, lane) / (double)n);
     }
     if (blockIdx.x != 0 || j != 0) return;
     for (int k = 0; k < K; ++k) {
@@ -291,7 +186,7 @@ __global__ __launch_bounds__(256) void kmeans_merge_kernel(float* __restrict__ c
 
 inline int km_shape(int64_t N, int64_t D, int64_t K) {
     if (K < 1 || N < K || D <= 0 || (D & 3)) return DBMM_E_SHAPE;
-    if (K > KMAX || D > 4096 || N > 0x7fffffffLL) return DBMM_E_UNSUPPORTED;
+    if (K > MAX_LABELS || D > 4096 || N > 0x7fffffffLL) return DBMM_E_UNSUPPORTED;
     return DBMM_OK;
 }
 
@@ -301,10 +196,9 @@ void launch_assign(const float* x, const float* c, int* labels, float* dmin, lon
 }
 template <int KP>
 void launch_sums(const float* x, char* ws, const Layout& l, int N, int D, int K, hipStream_t s) {
-    const int slabs = km_slabs(D), units = l.P * slabs;
-    hipLaunchKernelGGL(kmeans_sums_kernel<KP>, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, x, (const int*)(ws + l.lab),
+    hipLaunchKernelGGL(kmeans_sums_kernel<KP>, dim3(sums_grid(l.P, D)), dim3(256), 0, s, x, (const int*)(ws + l.lab),
                        (const float*)(ws + l.dmin), (double*)(ws + l.part), (long long*)(ws + l.cnt), (double*)(ws + l.inert), (long long*)ws, N, D,
-                       K, l.P, l.rows, slabs);
+                       K, l.P, l.rows, slabs(D));
 }
 
 // K padded to 2 / 4 / 8 / 16: the kernels' register arrays

@@ -32,12 +32,6 @@ constexpr int MAX_WG = DBMM_N_CU;                                  // persistent
 constexpr int NO_GROUP = 15;                                       // rows past N / labels outside [0, G): in no bucket
 constexpr size_t HEAD_BYTES = 256;                                 // workspace head: the centred absmax (uint bits)
 
-__device__ __forceinline__ double wave_sum_f64(double v) {         // butterfly: every lane gets the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct RowInfo { float norm; int group; };                         // |hi + lo|^2 in scaled units, group label or NO_GROUP
 
 // max |x - centre| over the split (an integer max of the float bits: the order of the atomics does not matter)

@@ -1456,37 +1456,74 @@ def gather_rows(table, idx):
     return out
 
 
+# ---- the analysis kernels (pairdist, covariance, k-means, label sums, erasure): every operand is refused here, before any allocation or launch
+def _rows_operand(what, x, mult=64, max_n=1 << 23):
+    """(N, D) of the rows x: an fp32 contiguous 16-byte aligned [N, D] device tensor with N in 1..max_n (None: any N >= 1), else
+    DbmmError; D a positive multiple of `mult` up to 4096 -- the widths the kernels serve --, else DbmmUnsupported"""
+    require_cuda(x)
+    _f32c(x, f"{what}: x")
+    if x.dim() != 2 or x.shape[0] < 1 or (max_n is not None and x.shape[0] > max_n):
+        raise _lib.DbmmError(f"{what}: x must be [N, D] with N {'>= 1' if max_n is None else f'in 1..{max_n}'}, got {tuple(x.shape)}")
+    N, D = x.shape
+    if D % mult or D > 4096 or D == 0:
+        raise DbmmUnsupported(f"{what}: D = {D}; the kernel serves D % {mult} == 0, D <= 4096")
+    if x.data_ptr() % 16:
+        raise _lib.DbmmError(f"{what}: x is not 16-byte aligned")
+    return N, D
+
+
+def _ids_operand(what, name, ids, x):
+    """ids (`name`: groups, labels): a contiguous int64 [N] tensor on x's device, one id per row of x"""
+    if not torch.is_tensor(ids):
+        raise _lib.DbmmError(f"{what}: {name} must be a contiguous int64 [N] device tensor, got {type(ids).__name__}")
+    require_cuda(ids)
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or ids.dim() != 1:
+        raise _lib.DbmmError(f"{what}: {name} must be a contiguous int64 [N] tensor, got {ids.dtype} {tuple(ids.shape)}")
+    if ids.numel() != x.shape[0]:
+        raise _lib.DbmmError(f"{what}: {ids.numel()} {name} for {x.shape[0]} rows")
+    if ids.device != x.device:
+        raise _lib.DbmmError(f"{what}: {name} is on {ids.device}, x on {x.device}")
+
+
+def _f32_operand(what, name, t, x, n=None):
+    """an fp32 contiguous 16-byte aligned operand on x's device; n: the elements the kernels will index (a [D] vector as `center`)"""
+    if not torch.is_tensor(t):
+        raise _lib.DbmmError(f"{what}: {name} must be a device tensor, got {type(t).__name__}")
+    require_cuda(t)
+    _f32c(t, f"{what}: {name}")
+    if n is not None and t.numel() != n:
+        raise _lib.DbmmError(f"{what}: {name} has {t.numel()} elements where the kernels will index {n}")
+    if t.device != x.device:
+        raise _lib.DbmmError(f"{what}: {name} is on {t.device}, x on {x.device}")
+    if t.data_ptr() % 16:
+        raise _lib.DbmmError(f"{what}: {name} is not 16-byte aligned")
+
+
+def _served(rc, what, request):
+    """a C entry's return code: DBMM_E_UNSUPPORTED is DbmmUnsupported (no kernel for this valid request), any other failure DbmmError"""
+    if rc == _lib.E_UNSUPPORTED:
+        raise DbmmUnsupported(f"{what}: no kernel for {request}")
+    check(rc, what)
+
+
 def pairdist_group_sums(x, groups, n_groups, center):
     """S float64 [G, G], symmetric: S[a, b] = sum over unordered pairs i < j with {groups[i], groups[j]} = {a, b} of
     ||x[i] - x[j]||_2, on the fused Gram-and-distance kernel (dbmm_pairdist_group_sums): no N x N matrix, float64 sums in a fixed
     order.  x fp32 [N, D] (D % 64 == 0, D <= 4096), groups int64 [N] in [0, n_groups) (n_groups <= 8), center fp32 [D]: a vector
     near the rows' mean (the split's mean vector), subtracted before the products are formed.  The whole split's sum is
     S.triu().sum(); group a's own is S[a, a]."""
-    require_cuda(x, groups, center)
-    _f32c(x)
-    _f32c(center)
-    if x.dim() != 2 or x.shape[0] < 1:
-        raise _lib.DbmmError(f"pairdist_group_sums: x must be [N, D] with N >= 1, got {tuple(x.shape)}")
-    N, D = x.shape
-    if groups.dtype != torch.int64 or not groups.is_contiguous() or groups.dim() != 1:
-        raise _lib.DbmmError("pairdist_group_sums: groups must be a contiguous int64 [N] tensor")
-    _sized("pairdist_group_sums: groups", groups, N)
-    _sized("pairdist_group_sums: center", center, D)
-    if groups.device != x.device or center.device != x.device:
-        raise _lib.DbmmError(f"pairdist_group_sums: groups is on {groups.device}, center on {center.device}, x on {x.device}")
+    N, D = _rows_operand("pairdist_group_sums", x)
+    _ids_operand("pairdist_group_sums", "groups", groups, x)
+    _f32_operand("pairdist_group_sums", "center", center, x, D)
     if not 1 <= n_groups <= 8:
         raise _lib.DbmmError(f"pairdist_group_sums: n_groups = {n_groups} outside 1..8")
-    if D % 64 or D > 4096:
-        raise DbmmUnsupported(f"pairdist_group_sums: D = {D}; the kernel serves D % 64 == 0, D <= 4096")
     L = _lib.lib()
     nbytes = L.dbmm_workspace_bytes_pairdist(N, D)
     ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # the planes: sized by the call, not cached
     out = _empty((n_groups, n_groups), device=x.device, dtype=torch.float64)
     rc = L.dbmm_pairdist_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), out.data_ptr(), N, D, n_groups, ws.data_ptr(),
                                     ws.numel() * 4, stream())
-    if rc == _lib.E_UNSUPPORTED:
-        raise DbmmUnsupported(f"pairdist_group_sums: no kernel for N = {N}, D = {D}")
-    check(rc, "pairdist_group_sums")
+    _served(rc, "pairdist_group_sums", f"N = {N}, D = {D}")
     return out
 
 
@@ -1500,47 +1537,19 @@ def pairdist_row_group_sums(x, groups, n_groups, center):
     still gets its own), center fp32 [D]: a vector near the rows' mean (the split's mean vector), subtracted before the products
     are formed.  The diagonal is left out by index: R[i, groups[i]] of a group's only row and the column of an empty group are
     exactly 0.  Rows sorted by group take the kernel's fast path; any order gives the same sums to 1e-6."""
-    require_cuda(x, groups, center)
-    _f32c(x)
-    _f32c(center)
-    if x.dim() != 2 or x.shape[0] < 1:
-        raise _lib.DbmmError(f"pairdist_row_group_sums: x must be [N, D] with N >= 1, got {tuple(x.shape)}")
-    N, D = x.shape
-    if groups.dtype != torch.int64 or not groups.is_contiguous() or groups.dim() != 1:
-        raise _lib.DbmmError("pairdist_row_group_sums: groups must be a contiguous int64 [N] tensor")
-    _sized("pairdist_row_group_sums: groups", groups, N)
-    _sized("pairdist_row_group_sums: center", center, D)
-    if groups.device != x.device or center.device != x.device:
-        raise _lib.DbmmError(f"pairdist_row_group_sums: groups is on {groups.device}, center on {center.device}, x on {x.device}")
+    N, D = _rows_operand("pairdist_row_group_sums", x)
+    _ids_operand("pairdist_row_group_sums", "groups", groups, x)
+    _f32_operand("pairdist_row_group_sums", "center", center, x, D)
     if not 1 <= n_groups <= PAIRDIST_ROWS_MAX_G:
         raise _lib.DbmmError(f"pairdist_row_group_sums: n_groups = {n_groups} outside 1..{PAIRDIST_ROWS_MAX_G}")
-    if D % 64 or D > 4096:
-        raise DbmmUnsupported(f"pairdist_row_group_sums: D = {D}; the kernel serves D % 64 == 0, D <= 4096")
     L = _lib.lib()
     nbytes = L.dbmm_workspace_bytes_pairdist_rows(N, D, n_groups)
     ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # planes and partials: sized by the call, not cached
     out = _empty((N, n_groups), device=x.device, dtype=torch.float64)
     rc = L.dbmm_pairdist_row_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), out.data_ptr(), N, D, n_groups, ws.data_ptr(),
                                         ws.numel() * 4, stream())
-    if rc == _lib.E_UNSUPPORTED:
-        raise DbmmUnsupported(f"pairdist_row_group_sums: no kernel for N = {N}, D = {D}")
-    check(rc, "pairdist_row_group_sums")
+    _served(rc, "pairdist_row_group_sums", f"N = {N}, D = {D}")
     return out
-
-
-def _pca_operands(what, x, center):
-    require_cuda(x, center)
-    _f32c(x)
-    _f32c(center)
-    if x.dim() != 2 or x.shape[0] < 1:
-        raise _lib.DbmmError(f"{what}: x must be [N, D] with N >= 1, got {tuple(x.shape)}")
-    N, D = x.shape
-    _sized(f"{what}: center", center, D)
-    if center.device != x.device:
-        raise _lib.DbmmError(f"{what}: center is on {center.device}, x on {x.device}")
-    if D % 64 or D > 4096:
-        raise DbmmUnsupported(f"{what}: D = {D}; the kernel serves D % 64 == 0, D <= 4096")
-    return N, D
 
 
 def covariance(x, center):
@@ -1548,34 +1557,29 @@ def covariance(x, center):
     scatter kernel (dbmm_covariance): no centred copy of x, exact fp32 products, no fp32 chain longer than 1024 rows, float64 sums
     in a fixed order; symmetric to the bit and the same bits on every call.  x fp32 [N, D] (D % 64 == 0, D <= 4096), center fp32
     [D]: a vector near the rows' mean."""
-    N, D = _pca_operands("covariance", x, center)
+    N, D = _rows_operand("covariance", x)
+    _f32_operand("covariance", "center", center, x, D)
     L = _lib.lib()
     nbytes = L.dbmm_workspace_bytes_covariance(N, D)
     ws = _empty((nbytes + 7) // 8, device=x.device, dtype=torch.float64)            # the partial tiles: sized by (N, D), not cached
     out = _empty((D, D), device=x.device, dtype=torch.float64)
     rc = L.dbmm_covariance(x.data_ptr(), center.data_ptr(), out.data_ptr(), N, D, ws.data_ptr(), ws.numel() * 8, stream())
-    if rc == _lib.E_UNSUPPORTED:
-        raise DbmmUnsupported(f"covariance: no kernel for N = {N}, D = {D}")
-    check(rc, "covariance")
+    _served(rc, "covariance", f"N = {N}, D = {D}")
     return out
 
 
 def project_rows(x, center, basis):
     """y fp32 [N, K] = (x - center) @ basis.T in one read of x (dbmm_project_rows): basis fp32 [K, D], K in 1..8.  A row's
     coordinates do not depend on the other rows: projecting a slice gives the bits of the slice of the projection."""
-    N, D = _pca_operands("project_rows", x, center)
-    require_cuda(basis)
-    _f32c(basis)
+    N, D = _rows_operand("project_rows", x)
+    _f32_operand("project_rows", "center", center, x, D)
+    _f32_operand("project_rows", "basis", basis, x)
     if basis.dim() != 2 or basis.shape[1] != D or not 1 <= basis.shape[0] <= 8:
         raise _lib.DbmmError(f"project_rows: basis must be [K, {D}] with K in 1..8, got {tuple(basis.shape)}")
-    if basis.device != x.device:
-        raise _lib.DbmmError(f"project_rows: basis is on {basis.device}, x on {x.device}")
     K = basis.shape[0]
     out = _empty((N, K), device=x.device, dtype=torch.float32)
     rc = _lib.lib().dbmm_project_rows(x.data_ptr(), center.data_ptr(), basis.data_ptr(), out.data_ptr(), N, D, K, stream())
-    if rc == _lib.E_UNSUPPORTED:
-        raise DbmmUnsupported(f"project_rows: no kernel for N = {N}, D = {D}")
-    check(rc, "project_rows")
+    _served(rc, "project_rows", f"N = {N}, D = {D}")
     return out
 
 
@@ -1636,19 +1640,13 @@ _KMEANS_STATUS = 256                # bytes of the status block at the head of t
 
 
 def _kmeans_operands(what, x, centers):
-    require_cuda(x, centers)
-    _f32c(x)
-    _f32c(centers)
-    if x.dim() != 2 or x.shape[0] < 1:
-        raise _lib.DbmmError(f"{what}: x must be [N, D] with N >= 1, got {tuple(x.shape)}")
-    N, D = x.shape
+    N, D = _rows_operand(what, x, mult=4, max_n=None)
+    _f32_operand(what, "centers", centers, x)
     if centers.dim() != 2 or centers.shape[1] != D or centers.shape[0] < 1:
         raise _lib.DbmmError(f"{what}: centers must be [K, {D}] with K >= 1, got {tuple(centers.shape)}")
-    if centers.device != x.device:
-        raise _lib.DbmmError(f"{what}: centers is on {centers.device}, x on {x.device}")
     K = centers.shape[0]
-    if K > KMEANS_MAX_K or D % 4 or D > 4096:
-        raise DbmmUnsupported(f"{what}: K = {K}, D = {D}; the kernels serve K <= {KMEANS_MAX_K}, D % 4 == 0, D <= 4096")
+    if K > KMEANS_MAX_K:
+        raise DbmmUnsupported(f"{what}: K = {K}; the kernels serve K <= {KMEANS_MAX_K}")
     return N, D, K
 
 
@@ -1661,9 +1659,7 @@ def kmeans_assign(x, centers):
     labels = _empty((N,), device=x.device, dtype=torch.int32)
     dmin = _empty((N,), device=x.device, dtype=torch.float32)
     rc = _lib.lib().dbmm_kmeans_assign(x.data_ptr(), centers.data_ptr(), labels.data_ptr(), dmin.data_ptr(), N, D, K, stream())
-    if rc == _lib.E_UNSUPPORTED:
-        raise DbmmUnsupported(f"kmeans_assign: no kernel for N = {N}, D = {D}, K = {K}")
-    check(rc, "kmeans_assign")
+    _served(rc, "kmeans_assign", f"N = {N}, D = {D}, K = {K}")
     return labels, dmin
 
 
@@ -1717,16 +1713,8 @@ def label_column_sums(x, labels, n_labels):
     N <= 2^23) and the rows per label, from one read of x (dbmm_label_colsums).  labels int64 [N], compared as 64-bit: a value
     outside [0, n_labels) is in no sum and no count.  n_labels in 1..16.  float64 from the first add, row order inside a range,
     the ranges merged in a fixed order: the same bits on every call."""
-    N, D = _erase_rows_operand("label_column_sums", x)
-    if not torch.is_tensor(labels):
-        raise _lib.DbmmError("label_column_sums: labels must be a contiguous int64 [N] device tensor")
-    require_cuda(labels)
-    if labels.dtype != torch.int64 or not labels.is_contiguous() or labels.dim() != 1:
-        raise _lib.DbmmError("label_column_sums: labels must be a contiguous int64 [N] tensor")
-    if labels.numel() != N:
-        raise _lib.DbmmError(f"label_column_sums: {labels.numel()} labels for {N} rows")
-    if labels.device != x.device:
-        raise _lib.DbmmError(f"label_column_sums: labels is on {labels.device}, x on {x.device}")
+    N, D = _rows_operand("label_column_sums", x)
+    _ids_operand("label_column_sums", "labels", labels, x)
     G = int(n_labels)
     if not 1 <= G <= LABEL_SUMS_MAX_G:
         raise _lib.DbmmError(f"label_column_sums: n_labels = {G} outside 1..{LABEL_SUMS_MAX_G}")
@@ -1738,23 +1726,8 @@ def label_column_sums(x, labels, n_labels):
     sums = _empty((G, D), device=x.device, dtype=torch.float64)
     counts = _empty((G,), device=x.device, dtype=torch.int64)
     rc = L.dbmm_label_colsums(x.data_ptr(), labels.data_ptr(), sums.data_ptr(), counts.data_ptr(), N, D, G, ws.data_ptr(), nbytes, stream())
-    if rc == _lib.E_UNSUPPORTED:
-        raise DbmmUnsupported(f"label_column_sums: no kernel for N = {N}, D = {D}")
-    check(rc, "label_column_sums")
+    _served(rc, "label_column_sums", f"N = {N}, D = {D}")
     return sums, counts
-
-
-def _erase_rows_operand(what, x):
-    require_cuda(x)
-    _f32c(x, f"{what}: x")
-    if x.dim() != 2 or not 1 <= x.shape[0] <= 1 << 23:
-        raise _lib.DbmmError(f"{what}: x must be [N, D] with N in 1..2^23, got {tuple(x.shape)}")
-    N, D = x.shape
-    if D % 64 or D > 4096 or D == 0:
-        raise DbmmUnsupported(f"{what}: D = {D}; the kernel serves D % 64 == 0, D <= 4096")
-    if x.data_ptr() % 16:
-        raise _lib.DbmmError(f"{what}: x is not 16-byte aligned")
-    return N, D
 
 
 def erase_rows(x, center, A, B, out=None):
@@ -1763,16 +1736,9 @@ def erase_rows(x, center, A, B, out=None):
     a row is read completely before it is written) or a tensor of x's shape that does not overlap x.  Nothing N x D is allocated
     beyond the result.  A row's result depends on that row only: erasing a slice gives the bits of the slice, and in place gives
     the bits of out of place."""
-    N, D = _erase_rows_operand("erase_rows", x)
+    N, D = _rows_operand("erase_rows", x)
     for name, t in (("center", center), ("A", A), ("B", B)):
-        if not torch.is_tensor(t):
-            raise _lib.DbmmError(f"erase_rows: {name} must be a device tensor")
-        require_cuda(t)
-        _f32c(t, f"erase_rows: {name}")
-        if t.device != x.device:
-            raise _lib.DbmmError(f"erase_rows: {name} is on {t.device}, x on {x.device}")
-        if t.data_ptr() % 16:
-            raise _lib.DbmmError(f"erase_rows: {name} is not 16-byte aligned")
+        _f32_operand("erase_rows", name, t, x)
     if center.dim() != 1 or center.shape[0] != D:
         raise _lib.DbmmError(f"erase_rows: center must be [{D}], got {tuple(center.shape)}")
     if A.dim() != 2 or B.dim() != 2 or A.shape[1] != D or tuple(B.shape) != tuple(A.shape) or not 1 <= A.shape[0] <= ERASE_MAX_R:
@@ -1781,17 +1747,14 @@ def erase_rows(x, center, A, B, out=None):
     if out is None:
         out = _empty((N, D), device=x.device, dtype=torch.float32)
     else:
-        require_cuda(out)
-        _f32c(out, "erase_rows: out")
-        if tuple(out.shape) != (N, D) or out.device != x.device or out.data_ptr() % 16:
+        _f32_operand("erase_rows", "out", out, x)
+        if tuple(out.shape) != (N, D):
             raise _lib.DbmmError(f"erase_rows: out must be a 16-byte aligned [{N}, {D}] tensor on {x.device}, got {tuple(out.shape)} on {out.device}")
         lo, hi = out.data_ptr(), out.data_ptr() + N * D * 4
         if out.data_ptr() != x.data_ptr() and lo < x.data_ptr() + N * D * 4 and x.data_ptr() < hi:
             raise _lib.DbmmError("erase_rows: out overlaps x without being x; rows would be read after they were written")
     rc = _lib.lib().dbmm_erase_rows(x.data_ptr(), center.data_ptr(), A.data_ptr(), B.data_ptr(), out.data_ptr(), N, D, R, stream())
-    if rc == _lib.E_UNSUPPORTED:
-        raise DbmmUnsupported(f"erase_rows: no kernel for N = {N}, D = {D}")
-    check(rc, "erase_rows")
+    _served(rc, "erase_rows", f"N = {N}, D = {D}")
     return out
 
 

@@ -65,3 +65,23 @@ def test_persistent_tile_statement_stated_once(statement, where):
 @pytest.mark.parametrize("name", ("tile_walk", "work_item", "work_slices", "slice_store", "slice_sum", "absmax_fold", "ring_rows"))
 def test_persistent_tile_helper_defined_once(name):
     assert _where(r"__device__\s[^;(){}]*?\b%s\s*\([^;{}]*\)\s*\{" % name) == [("persistent_tiles.h", 1)]
+
+
+# What the k-means sums and the label sums share (csrc/label_sums.h; DESIGN.md, sections 6c and 6e): the partition, the unit body, the
+# fixed-order merge.  The promise is the same bits on every call; a second copy of the order could move without the other.
+def test_wave_sum_f64_defined_once_in_common_h():
+    assert _where(r"__device__\s[^;(){}]*?\bwave_sum_f64\s*\([^;{}]*\)\s*\{") == [("common.h", 1)]
+
+
+@pytest.mark.parametrize("name", ("wave_unit", "unit_sums", "quarter_sums", "merge_sum", "merge_count"))
+def test_label_sums_helper_defined_once(name):
+    assert _where(r"__device__\s[^;(){}]*?\b%s\s*\([^;{}]*\)\s*\{" % name) == [("label_sums.h", 1)]
+
+
+@pytest.mark.parametrize("statement", [
+    "((quarter[0][lane] + quarter[1][lane]) + quarter[2][lane]) + quarter[3][lane]",   # the merge order (merge_sum)
+    "acc[j][e] = fma(w, v[e], acc[j][e])",                                            # the predicated add (unit_sums)
+    "long long p = (UNITS + sl - 1) / sl",                                            # the partition (ranges)
+])
+def test_label_sums_statement_stated_once(statement):
+    assert _where(re.escape(statement)) == [("label_sums.h", 1)]

@@ -224,3 +224,89 @@ def test_what_raises():
         analysis.erasure_from_moments(*moments64(x, wide))
     with pytest.raises(ValueError):
         analysis.erasure_fit(object(), wide, method="inlp")                  # refused before the rows are looked at
+
+
+# ---- the device's order of the per-label column sums (csrc/label_sums.h), restated ------------------------------------------------------------
+def sums_ranges(N, D):
+    """(P, rows): the row ranges of the sums kernels from (N, D) alone -- 2048 (range, slab of 256 columns) units aimed at, no range
+    below 64 rows, at least one"""
+    slabs = -(-D // 256)
+    P = max(1, min(-(-2048 // slabs), -(-N // 64)))
+    return P, -(-N // P)
+
+
+def _butterfly(a):
+    """lane 0 of the wave's xor butterfly over the last axis (64 lanes)"""
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        a = a + a[..., lanes ^ o]
+    return a[..., 0]
+
+
+def fixed_order_sums(x, labels, G):
+    """(sums float64 [G, D], counts int64 [G]) of the fp32 rows x added in the device's order: inside a range every label's rows in row
+    order (fp32 values are exact in float64; fma(1, v, acc) is acc + v and fma(0, v, acc) leaves acc, so another label's row adds
+    + 0 v), each quarter of the ranges in range order, then ((q0 + q1) + q2) + q3.  Vectorised over the ranges; labels outside
+    [0, G) are in no sum and no count."""
+    N, D = x.shape
+    P, rows = sums_ranges(N, D)
+    xp = np.zeros((P * rows, D))
+    xp[:N] = x
+    lp = np.full(P * rows, -1, dtype=np.int64)
+    lp[:N] = labels
+    xp, lp = xp.reshape(P, rows, D), lp.reshape(P, rows)
+    part = np.zeros((P, G, D))
+    for i in range(rows):
+        w = (lp[:, i, None] == np.arange(G)).astype(np.float64)                  # [P, G]: 1 under label == j, else 0
+        part = w[:, :, None] * xp[:, i, None, :] + part
+    pq = -(-P // 4)
+    quarter = np.zeros((4, G, D))
+    for q in range(4):
+        for p in range(min(q * pq, P), min(q * pq + pq, P)):
+            quarter[q] = quarter[q] + part[p]
+    inside = labels[(labels >= 0) & (labels < G)]
+    return ((quarter[0] + quarter[1]) + quarter[2]) + quarter[3], np.bincount(inside, minlength=G).astype(np.int64)
+
+
+def fixed_order_inertia(dmin, D):
+    """the float64 sum of the fp32 dmin [N] in the k-means kernels' order: per range a lane adds every 64th row in row order and the
+    wave's butterfly folds the lanes; then a lane adds a contiguous run of the ranges in range order and a butterfly folds those"""
+    N = dmin.shape[0]
+    P, rows = sums_ranges(N, D)
+    steps = -(-rows // 64)
+    dp = np.zeros((P, steps * 64))
+    for p in range(P):
+        r0 = min(p * rows, N)
+        r1 = min(r0 + rows, N)
+        dp[p, :r1 - r0] = dmin[r0:r1]
+    lanes = np.zeros((P, 64))
+    for k in range(steps):
+        lanes = lanes + dp[:, 64 * k:64 * k + 64]
+    inert = _butterfly(lanes)
+    run = -(-P // 64)
+    total = np.zeros(64)
+    for lane in range(64):
+        for p in range(lane * run, min((lane + 1) * run, P)):
+            total[lane] = total[lane] + inert[p]
+    return float(_butterfly(total))
+
+
+@pytest.mark.parametrize("N,D,G", [(1, 64, 1), (259, 64, 3), (1027, 512, 16), (20001, 64, 3)])
+def test_fixed_order_sums_are_sums(N, D, G):
+    """the restated order against long double, within the bound of the device test: a label's column adds n_g float64 numbers, at
+    most n_g - 1 additions round, each by 2^-53 of a partial sum that is at most sum |x|"""
+    assert sums_ranges(N, D) == {1: (1, 1), 259: (5, 52), 1027: (17, 61), 20001: (313, 64)}[N]
+    rng = np.random.RandomState(N + D)
+    x = (rng.standard_normal((N, D)) * 2.0 ** rng.randint(-20, 21, size=(N, 1))).astype(np.float32)   # scales apart: the additions round
+    labels = rng.randint(-1, G, size=N).astype(np.int64)                         # -1: in no sum
+    sums, counts = fixed_order_sums(x, labels, G)
+    chain = np.stack([np.add.reduce(x[labels == g].astype(np.float64), axis=0) for g in range(G)])
+    assert N == 1 or (sums != chain).any()                                       # the order shows in the bits: one row-order chain differs
+    assert counts.tolist() == [int((labels == g).sum()) for g in range(G)]
+    for g in range(G):
+        sel = x[labels == g].astype(np.longdouble)
+        err = np.abs(sums[g].astype(np.longdouble) - sel.sum(0)).astype(np.float64)
+        assert (err <= (counts[g] * 2.0 ** -52 * np.abs(sel).sum(0)).astype(np.float64)).all()
+    dmin = np.abs(x[:, 0])
+    total = fixed_order_inertia(dmin, D)
+    assert abs(total - float(dmin.astype(np.longdouble).sum())) <= N * 2.0 ** -52 * float(dmin.astype(np.float64).sum())
