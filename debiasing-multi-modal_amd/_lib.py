@@ -42,6 +42,7 @@ KERNEL_SOURCES = (
     ("adapter_step", ("adapter_step.hip", "adapter_bodies.inc", "common.h")),
     ("sweep_", ("adapter_sweep.hip", "adapter_bodies.inc", "common.h")),
     ("linear_sweep_", ("linear_sweep.hip", "linear_bodies.inc", "common.h")),
+    ("linear_prox_", ("linear_prox.hip", "linear_bodies.inc", "common.h")),
     ("linear_", ("linear_step.hip", "linear_bodies.inc", "common.h")),
     ("pairdist_", ("pairdist.hip", "fp16_ring.inc", "persistent_tiles.h", "common.h")),
     ("covariance_", ("covariance.hip", "common.h")),
@@ -238,6 +239,7 @@ _SIGS = {
     "dbmm_workspace_bytes_label_colsums": [_L, _L, _L],
     "dbmm_label_colsums": [_P, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
     "dbmm_erase_rows": [_P, _P, _P, _P, _P, _L, _L, _L, _P],
+    "dbmm_linear_prox_fit": [_P, _L] + [_P] * 10 + [_L, _L, _L, _L, _L, _I, _P],
 }
 _RESTYPES = {
     "dbmm_error_string": ctypes.c_char_p,

@@ -5,6 +5,7 @@ Every function requires HIP tensors -- there is no CPU path here.
 import ctypes
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -1443,6 +1444,62 @@ def linear_sweep_eval(table, idx, labels, groups, w, b, counts, loss_sum, row0=0
     if rc:
         check(rc, "linear_sweep_eval")
     return logits, rows
+
+
+PROX_MAX_R = 256                    # fits of one dbmm_linear_prox_fit launch (csrc/linear_prox.hip: one workgroup each)
+
+# the state of R L1-probe fits between launches: iterate w [R, C, D] / b [R, C], extrapolated point v / c (float32), t float64 [R]
+ProxState = namedtuple("ProxState", "w b v c t")
+
+
+def linear_prox_state(R, C, D, device, w=None, b=None):
+    """the start of R fits: t = 1 and V = W (zero weights unless `w` [R, C, D] / `b` [R, C] are given)"""
+    w = torch.zeros((R, C, D), dtype=torch.float32, device=device) if w is None else w.to(device, torch.float32).contiguous().clone()
+    b = torch.zeros((R, C), dtype=torch.float32, device=device) if b is None else b.to(device, torch.float32).contiguous().clone()
+    if tuple(w.shape) != (R, C, D) or tuple(b.shape) != (R, C):
+        raise _lib.DbmmError(f"linear prox state: w {tuple(w.shape)}, b {tuple(b.shape)} for R={R} C={C} D={D}")
+    return ProxState(w, b, w.clone(), b.clone(), torch.ones((R,), dtype=torch.float64, device=device))
+
+
+def linear_prox_fit(table, idx, labels, lam, step, state, iters, accelerate=True):
+    """`iters` FISTA iterations of R L1-penalised logistic probes in ONE launch (dbmm_linear_prox_fit, one workgroup per fit): fit r
+    minimises (1 / n) sum CE + lam[r] ||W||_1 over rows idx[r] (int64 [R, n], clamped into the table) of `table` ([N, D] fp32; labels
+    int64 [N]) with step[r] = 1 / L; lam, step float32 [R] on the device.  `state` (a ProxState; linear_prox_state starts one) is
+    advanced in place, so a fit may be split over any number of calls.  accelerate=False: plain ISTA (beta = 0).  Returns stats
+    float32 [R, 4] of the call's last iteration: max |dW|, max |W|, nonzeros of W, CE mean at the extrapolated point."""
+    require_cuda(table, idx, labels, lam, step, *state)
+    w, b, v, c, t = state
+    if table.dim() != 2 or w.dim() != 3 or b.dim() != 2:
+        raise _lib.DbmmError(f"linear prox: table [N, D], w [R, C, D], b [R, C] expected; got {tuple(table.shape)}, {tuple(w.shape)}, "
+                             f"{tuple(b.shape)}")
+    R, C, D = w.shape
+    for nm, x in (("table", table), ("w", w), ("b", b), ("v", v), ("c", c), ("lam", lam), ("step", step)):
+        _f32c(x, "linear prox " + nm)
+    if table.shape[1] != D or tuple(b.shape) != (R, C) or v.shape != w.shape or c.shape != b.shape:
+        raise _lib.DbmmError(f"linear prox: table {tuple(table.shape)}, b {tuple(b.shape)}, v {tuple(v.shape)}, c {tuple(c.shape)} against "
+                             f"w {tuple(w.shape)}")
+    if not (1 <= R <= PROX_MAX_R) or not (1 <= C <= 8) or D % 4 or not (4 <= D <= 1024) or table.shape[0] < 1:
+        raise _lib.DbmmError(f"linear prox serves 1..{PROX_MAX_R} fits, C <= 8 classes, D % 4 == 0 and D <= 1024; got R={R} C={C} D={D}")
+    if labels.dtype != torch.int64 or not labels.is_contiguous():
+        raise _lib.DbmmError("linear prox: labels must be a contiguous int64 tensor")
+    _sized("linear prox labels", labels, table.shape[0])
+    if idx.dtype != torch.int64 or not idx.is_contiguous() or idx.dim() != 2 or idx.shape[0] != R or idx.shape[1] < 1:
+        raise _lib.DbmmError("linear prox: idx must be a contiguous int64 [R, n] tensor with n >= 1")
+    _operand("linear prox t", t, torch.float64, (R,))
+    _sized("linear prox lam", lam, R)
+    _sized("linear prox step", step, R)
+    if any(x.device != table.device for x in (idx, labels, lam, step, w, b, v, c, t)):
+        raise _lib.DbmmError("linear prox: all operands must be on one device")
+    iters = int(iters)
+    if not (1 <= iters <= 1 << 20):
+        raise _lib.DbmmError(f"linear prox: iters in 1..2^20 expected, got {iters}")
+    stats = _empty((R, 4), device=table.device, dtype=torch.float32)
+    rc = _lib.lib().dbmm_linear_prox_fit(table.data_ptr(), table.shape[0], idx.data_ptr(), labels.data_ptr(), lam.data_ptr(), step.data_ptr(),
+                                         w.data_ptr(), b.data_ptr(), v.data_ptr(), c.data_ptr(), t.data_ptr(), stats.data_ptr(), R,
+                                         idx.shape[1], D, C, iters, int(bool(accelerate)), stream())
+    if rc:
+        check(rc, "linear_prox_fit")
+    return stats
 
 
 def gather_rows(table, idx):

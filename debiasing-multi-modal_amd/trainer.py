@@ -12,6 +12,7 @@ reproduces `DataLoader(shuffle=True)`'s index stream from the global torch RNG, 
 adapter's balance_val draw the per-epoch group balancing from the global numpy RNG.
 """
 import os
+import time
 from collections import namedtuple
 from copy import copy, deepcopy
 from functools import partial
@@ -19,7 +20,7 @@ from functools import partial
 import numpy as np
 import torch
 
-from . import adapter, contrastive, ops
+from . import adapter, contrastive, dfr, ops
 from . import optim as O
 
 NEW_ORDER_FOR_PRINT = ["weighted_mean_acc", "worst_acc", "acc_0_0", "acc_0_1", "acc_1_0", "acc_1_1", "mean_acc"]
@@ -798,6 +799,153 @@ def prediction_errors(table, classifier, target="class", batch_size=4096):
         logits = classifier.loss(emb, y)[1]
         wrong.append(logits.argmax(1) != y)
     return torch.cat(wrong).cpu().numpy()
+
+
+@torch.no_grad()
+def _probe_counts(emb, labels, groups, n_groups, W, b, rows=None):
+    """(n, correct) counters [R, G, 2] and CE sums [R] (numpy) of R linear probes W [R, C, D], b [R, C] over the rows `rows` (int64
+    numpy; None: all) of the embeddings `emb`.  On the device: ops.linear_sweep_eval in chunks of 16 probes; embeddings on the host
+    (the solver="reference" path of train_dfr, which runs without a GPU) are scored in torch."""
+    R, dev = W.shape[0], emb.device
+    counts = torch.zeros((R, n_groups, 2), dtype=torch.int64, device=dev)
+    loss = torch.zeros(R, dtype=torch.float64, device=dev)
+    idx = None if rows is None else torch.as_tensor(rows, dtype=torch.int64).to(dev)
+    W, b = W.to(dev, torch.float32).contiguous(), b.to(dev, torch.float32).contiguous()
+    if dev.type == "cuda":
+        for r0 in range(0, R, 16):
+            ops.linear_sweep_eval(emb, idx, labels, groups, W[r0:r0 + 16], b[r0:r0 + 16], counts[r0:r0 + 16], loss[r0:r0 + 16])
+    else:
+        x, y, g = (emb, labels, groups) if idx is None else (emb[idx], labels[idx], groups[idx])
+        for r in range(R):
+            logits = x @ W[r].t() + b[r]
+            loss[r] = torch.nn.functional.cross_entropy(logits.double(), y, reduction="sum")
+            hit = logits.argmax(1) == y
+            counts[r, :, 0] = torch.bincount(g, minlength=n_groups)[:n_groups]
+            counts[r, :, 1] = torch.bincount(g[hit], minlength=n_groups)[:n_groups]
+    return counts.cpu().numpy(), loss.cpu().numpy()
+
+
+def _worst_group_acc(c):
+    """smallest correct / n over the groups of one probe's counters [G, 2]"""
+    return float((c[:, 1] / np.maximum(c[:, 0], 1)).min())
+
+
+def train_dfr(opt, train_table, val_table, test_table, transform=None, log=None):
+    """Deep feature reweighting, DFR-Val (Kirichenko et al. 2023), as one call: L1-penalised logistic probes (dfr.fit_l1_probes)
+    on group-balanced subsets of the VALIDATION split, on frozen embeddings.  No learning rate is involved.
+
+    Standardise (opt.dfr_preprocess, default True): column mean and population standard deviation of the TRAIN table from float64
+    sums (a constant column's 0 becomes 1); the probes see a standardised copy of the val table.  `transform` (a stage-1 adapter, any
+    callable on [B, D] rows) is applied first, batch by batch in eval mode, to all three tables.
+    Tune: val is split into two halves by a private RandomState(opt.dfr_seed, default 0); for every C of opt.dfr_c_grid (sklearn's C:
+    lam = 1 / (C n); default dfr.DEFAULT_C_GRID) and each of opt.dfr_tune_retrains (default 1) balanced subsets of the first half
+    (analysis.balanced_rows' rule over group_array, private streams) one probe is fitted -- all of them in ONE fit_l1_probes call --
+    and scored by its worst-group accuracy on the second half.  The best mean score wins, ties go to the smaller C.
+    Refit: opt.dfr_retrains (default 10) balanced subsets of the whole val split at the chosen C; weights and intercepts are
+    averaged, the standardisation is folded into them in float64 (W / sigma, b - sum W mu / sigma) and they are loaded into an
+    adapter.LinearClassifier that works on the (transformed) raw embeddings, which every evaluation path takes unchanged.
+    opt.dfr_solver: "device" (default; the fused kernel) or "reference" (dfr.prox_fit_reference in float64: runs on host tables,
+    without a GPU); opt.dfr_tol (1e-4), opt.dfr_max_iter (1000), opt.dfr_check_every (32).  The global random streams are untouched.
+
+    Refused with ValueError before a model is built or anything is launched: a group absent from val or from one of its halves, more
+    than 8 classes, a val label outside [0, n_cls), an empty grid, a non-positive C.
+
+    Returns (classifier, ((train), (val), (test)) scores as `validate` gives them, record).  The val score is on rows the probe was
+    TRAINED on (every refit subset is drawn from val): only the test score is held out.  The record holds the chosen C, the tuning
+    table (C, per-subset worst-group accuracies, their mean), per-retrain nnz / iterations / convergence, and the step set-up and
+    fit seconds.  `log` (a list) receives `dfr_tune`, `dfr_fit` and `dfr_eval` records."""
+    c_grid = [float(c) for c in getattr(opt, "dfr_c_grid", dfr.DEFAULT_C_GRID)]
+    n_cls = int(getattr(opt, "n_cls", val_table.n_classes))
+    seed = int(getattr(opt, "dfr_seed", 0))
+    n_tune, n_fit = int(getattr(opt, "dfr_tune_retrains", 1)), int(getattr(opt, "dfr_retrains", 10))
+    solver = getattr(opt, "dfr_solver", "device")
+    kw = dict(solver=solver, tol=float(getattr(opt, "dfr_tol", 1e-4)), max_iter=int(getattr(opt, "dfr_max_iter", 1000)),
+              check_every=int(getattr(opt, "dfr_check_every", 32)), n_classes=n_cls)
+    target = getattr(opt, "train_target", "class")
+    if solver not in ("device", "reference"):
+        raise ValueError(f"train_dfr: opt.dfr_solver 'device' or 'reference' expected, got {solver!r}")
+    if n_tune < 1 or n_fit < 1:
+        raise ValueError(f"train_dfr: dfr_tune_retrains >= 1 and dfr_retrains >= 1 expected, got {n_tune}, {n_fit}")
+    groups = np.asarray(val_table.group_array)
+    halves = dfr.val_halves(len(val_table), seed)
+    dfr.check_options(c_grid, n_cls, val_table.labels(target).cpu().numpy(), groups, val_table.n_groups, halves)
+    rec = (lambda **k: log.append(k)) if log is not None else (lambda **k: None)
+    dev = val_table.device
+    bs_eval = max(int(getattr(opt, "batch_size", 4096)), 4096)
+
+    def rows_of(table):
+        if transform is None:
+            return table.embeddings
+        from . import analysis
+        return analysis._transformed_rows(table.embeddings, transform, bs_eval)
+
+    xt, xv = rows_of(train_table), rows_of(val_table)
+    D = xv.shape[1]
+    if bool(getattr(opt, "dfr_preprocess", True)):
+        mean, std = dfr.column_moments(xt)
+        zv = dfr.standardised(xv, mean.to(dev), std.to(dev))
+    else:
+        mean, std = torch.zeros(D, dtype=torch.float64, device=dev), torch.ones(D, dtype=torch.float64, device=dev)
+        zv = xv
+    labels, gdev = val_table.labels(target), val_table.targets_group
+
+    # tune: every (C, subset) of half A is one fit of one call; scored on half B
+    subsets = dfr.balanced_subsets(groups, halves[0], [seed + 1 + j for j in range(n_tune)])
+    n = subsets.shape[1]
+    idx = np.concatenate([subsets] * len(c_grid))                          # C-major: fit i * n_tune + j is (c_grid[i], subset j)
+    lam = np.repeat([1.0 / (c * n) for c in c_grid], n_tune)
+    t0 = time.perf_counter()
+    fit = dfr.fit_l1_probes(zv, idx, labels, lam, **kw)
+    counts, _ = _probe_counts(zv, labels, gdev, val_table.n_groups, fit.weights, fit.intercepts, rows=halves[1])
+    tune_seconds = time.perf_counter() - t0
+    worst = np.array([_worst_group_acc(c) for c in counts]).reshape(len(c_grid), n_tune)
+    table = [dict(C=c, worst_acc=worst[i].tolist(), mean=float(worst[i].mean())) for i, c in enumerate(c_grid)]
+    best = dfr.pick_c(c_grid, [t["mean"] for t in table])
+    C = c_grid[best]
+    rec(kind="dfr_tune", C=C, table=table, subsets=subsets, halves=halves, counts=counts, iterations=fit.iterations.numpy(),
+        converged=fit.converged.numpy(), nnz=fit.nnz.numpy(), setup_seconds=fit.setup_seconds, seconds=tune_seconds)
+
+    # refit on balanced subsets of the whole val split at the chosen C; average; fold the standardisation in
+    subsets = dfr.balanced_subsets(groups, np.arange(len(val_table)), [seed + 1 + n_tune + j for j in range(n_fit)])
+    t0 = time.perf_counter()
+    refit = dfr.fit_l1_probes(zv, subsets, labels, [1.0 / (C * subsets.shape[1])] * n_fit, **kw)
+    fit_seconds = time.perf_counter() - t0
+    W, b = dfr.fold_standardisation(refit.weights.double().mean(0), refit.intercepts.double().mean(0), mean.to(dev), std.to(dev))
+    rec(kind="dfr_fit", C=C, subsets=subsets, iterations=refit.iterations.numpy(), converged=refit.converged.numpy(),
+        nnz=refit.nnz.numpy(), weights=refit.weights.cpu(), intercepts=refit.intercepts.cpu(), setup_seconds=refit.setup_seconds,
+        seconds=fit_seconds)
+    with torch.random.fork_rng(devices=[]):                                # nn.Linear's initialisation draws; the weights are replaced
+        classifier = adapter.LinearClassifier(D, n_cls)
+    with torch.no_grad():
+        classifier.fc.weight.copy_(W.float())
+        classifier.fc.bias.copy_(b.float())
+    classifier = classifier.to(dev).eval()
+
+    ratio = train_table.group_ratio.numpy()
+    scores = []
+    for split, table_, x in (("train", train_table, xt), ("val", val_table, xv), ("test", test_table, None)):
+        x = rows_of(table_) if x is None else x
+        if dev.type == "cuda":
+            scored = table_
+            if transform is not None:
+                scored = copy(table_)
+                scored.embeddings = x
+            st = {}
+            res = validate(scored, classifier, bs_eval, ratio, target="class" if split == "test" else target, stats=st)
+            c = st["counts"]
+        else:
+            tg = "class" if split == "test" else target
+            cs, ls = _probe_counts(x, table_.labels(tg), table_.targets_group, table_.n_groups, classifier.fc.weight.detach()[None],
+                                   classifier.fc.bias.detach()[None])
+            c = cs[0]
+            res = _scores(table_, c, float(ls[0]), len(table_), ratio)
+        rec(kind="dfr_eval", split=split, loss=res[0], acc=res[1], group_acc=res[2], counts=c)
+        scores.append(res)
+    record = dict(C=C, tuning=table, nnz=refit.nnz.tolist(), iterations=refit.iterations.tolist(), converged=refit.converged.tolist(),
+                  tune_iterations=fit.iterations.tolist(), tune_converged=fit.converged.tolist(), solver=solver,
+                  setup_seconds=fit.setup_seconds + refit.setup_seconds, tune_seconds=tune_seconds, fit_seconds=fit_seconds,
+                  mean=mean.cpu(), std=std.cpu())
+    return classifier, tuple(scores), record
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -981,6 +981,29 @@ int dbmm_label_colsums(const float* x, const int64_t* labels, double* sums, int6
 int dbmm_erase_rows(const float* x, const float* center, const float* A, const float* B, float* y, int64_t N, int64_t D, int64_t R,
                     void* stream);
 
+/* L1-penalised logistic probes by FISTA, `iters` iterations in ONE launch (csrc/linear_prox.hip): replica r of R <= 256 is one
+ * workgroup that keeps its iterate in LDS and minimises
+ *     F(W, b) = (1 / n) sum_i CE(softmax(W x_i + b), y_i) + lam[r] ||W||_1        (the intercept b is not penalised)
+ * over the rows idx[r][0 .. n) of a shared table fp32 [n_rows][D] (clamped into it; labels int64 [n_rows], read as labels[idx],
+ * compared as 64 bits: a label outside [0, C) scores NaN).  The reference has no counterpart.  One iteration, from the state
+ * (W, b, V, c, t):  G, g = gradient of the CE mean at (V, c);  W' = soft(V - step[r] G, step[r] lam[r]) with soft(z, tau) =
+ * sign(z) max(|z| - tau, 0) (an exact +0 inside the threshold);  b' = c - step[r] g;  t' = (1 + sqrt(1 + 4 t^2)) / 2 in float64;
+ * beta = (float)((t - 1) / t'), or 0 when accelerate == 0 (plain ISTA);  V' = W' + beta (W' - W), c' = b' + beta (b' - b).
+ *   lam, step  fp32 [R], on the device (step = 1 / L, L = half the largest eigenvalue of (1 / n) [X, 1]^T [X, 1]: the caller's)
+ *   w, v       fp32 [R][C][D];  b, c fp32 [R][C];  t float64 [R]: the state, updated in place.  A fresh fit starts from w = v,
+ *              b = c, t = 1.  Nothing else is carried between iterations, so K iterations in one call are the K iterations of
+ *              several calls, bit for bit.
+ *   stats      fp32 [R][4], written by the call's last iteration: max |W' - W|, max |W'|, the number of nonzeros of W', and the CE
+ *              mean at that iteration's (V, c).
+ * Every sum has a fixed order that depends on (n, D, C) only: two calls give the same bits, and a replica's bits depend neither on R
+ * nor on its place among the replicas.  One launch on `stream`, no workspace, no atomics.
+ * Null pointer: DBMM_E_ARG; R outside 1..256, n < 1, C outside 1..8, D % 4 != 0, D outside 4..1024, n_rows < 1, iters outside
+ * 1..2^20: DBMM_E_SHAPE; table, w, v or stats not 16-byte aligned (idx, labels, t: 8-byte): DBMM_E_ALIGN.  Every check precedes
+ * the launch. */
+int dbmm_linear_prox_fit(const float* table, int64_t n_rows, const int64_t* idx, const int64_t* labels, const float* lam,
+                         const float* step, float* w, float* b, float* v, float* c, double* t, float* stats, int64_t R, int64_t n,
+                         int64_t D, int64_t C, int64_t iters, int accelerate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
