@@ -224,6 +224,8 @@ _SIGS = {
     "dbmm_group_loss_sum": [_P, _P, _P, _L, _L, _P],
     "dbmm_workspace_bytes_pairdist": [_L, _L],
     "dbmm_pairdist_group_sums": [_P, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_pairdist_rbf": [_L, _L, _L],
+    "dbmm_pairdist_rbf_group_sums": [_P, _P, _P, _P, _L, _P, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_pairdist_rows": [_L, _L, _L],
     "dbmm_pairdist_row_group_sums": [_P, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_covariance": [_L, _L],
@@ -258,6 +260,7 @@ _RESTYPES = {
     "dbmm_workspace_bytes_linear_sweep_step": c_size_t,
     "dbmm_workspace_bytes_linear_sweep_eval": c_size_t,
     "dbmm_workspace_bytes_pairdist": c_size_t,
+    "dbmm_workspace_bytes_pairdist_rbf": c_size_t,
     "dbmm_workspace_bytes_pairdist_rows": c_size_t,
     "dbmm_workspace_bytes_covariance": c_size_t,
     "dbmm_workspace_bytes_sym_eig": c_size_t,

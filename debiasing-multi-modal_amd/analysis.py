@@ -591,6 +591,184 @@ def separation_report(train_table, val_table, test_table, transform=None):
     return out
 
 
+# ---- kernel two-sample (MMD^2) and dependence (HSIC) scores: is a labelling still in the rows, beyond what a linear map sees? --------------
+# Gretton et al. 2012 (MMD) and 2005 (HSIC) with the RBF kernel exp(-gamma ||x - y||^2) at a ladder of bandwidths.  Both are sums of kernel
+# values over all pairs, bucketed by (label, label): ops.pairdist_rbf_group_sums gives the L x G x G bucket sums in one pass, nothing
+# N x N is stored, and everything after it is numpy on L G^2 numbers.  Zero in the limit exactly when the groups' distributions coincide
+# (MMD) or the labelling is independent of the rows (HSIC); the null comes from relabelling (mmd_permutation_test).
+
+RBF_SCALES = (0.25, 1.0, 4.0)
+
+
+def _variance_sum(x, chunk=1 << 12):
+    """sum over the columns of the population variance of the rows x (any torch tensor [N, D]), from float64 sums in two passes over
+    row chunks -- dfr.column_moments' arithmetic without its replacement of a constant column's 0 by 1, which would count here"""
+    n = x.shape[0]
+    s = torch.zeros(x.shape[1], dtype=torch.float64, device=x.device)
+    for i in range(0, n, chunk):
+        s += x[i:i + chunk].double().sum(0)
+    mean, q = s / n, 0.0
+    for i in range(0, n, chunk):
+        q += ((x[i:i + chunk].double() - mean) ** 2).sum().item()
+    return q / n
+
+
+def rbf_gammas(embeddings, scales=RBF_SCALES, transform=None):
+    """The bandwidth ladder gamma_k = scales[k] / m, float64 [len(scales)], with m the mean squared distance between two different
+    rows, 2 N / (N - 1) * sum_d var_d: the "mean heuristic".  Deterministic, two reads of the rows and no N^2 work.  In D = 1024 the
+    squared distances of a split concentrate, so m sits close to the median the usual heuristic takes; how close on real CLIP rows
+    has not been measured here.  `embeddings`: an EmbeddingTable or a tensor [N, D] (a host tensor works too); `transform` as in
+    `silhouette`.  Fewer than two rows, rows that are all equal or a scale <= 0 raise ValueError."""
+    x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError("rbf_gammas: the rows must be an EmbeddingTable or a tensor [N, D]")
+    x = x.float()
+    if transform is not None:
+        x = _transformed_rows(x.contiguous(), transform, TRANSFORM_ROWS)
+    n = x.shape[0]
+    scales = np.asarray(scales, dtype=np.float64).ravel()
+    if n < 2 or scales.size == 0 or not (np.isfinite(scales).all() and (scales > 0).all()):
+        raise ValueError(f"rbf_gammas: {n} rows, scales = {scales.tolist()}; at least two rows and finite scales > 0")
+    m = 2.0 * n / (n - 1.0) * _variance_sum(x)
+    if not (m > 0 and np.isfinite(m)):
+        raise ValueError(f"rbf_gammas: the mean squared distance of the rows is {m}")
+    return scales / m
+
+
+def _kernel_sums(K, counts):
+    K = np.asarray(K, dtype=np.float64)
+    n = np.asarray(counts).astype(np.float64).ravel()
+    if K.ndim != 3 or K.shape[1] != K.shape[2] or n.shape != (K.shape[1],):
+        raise ValueError(f"K {K.shape} is not [L, G, G] for {n.shape[0]} counts")
+    return K, n
+
+
+def mmd_from_sums(K, counts, unbiased=True):
+    """The host step of `mmd`, numpy only.  K float64 [L, G, G] as ops.pairdist_rbf_group_sums returns it (sums over unordered pairs,
+    the diagonal i = j left out), counts [G]: the rows per label.  Returns {'kernel_mean': [L, G, G], 'mmd2': [L, G, G], 'mmd2_sum':
+    [G, G]}: kernel_mean[l, a, b] is the mean kernel value between a row of a and a row of b -- K / (n_a n_b) off the diagonal, on it
+    2 K / (n_a (n_a - 1)) (the U-statistic: pairs of different rows) or, with unbiased=False, (2 K + n_a) / n_a^2 (the V-statistic:
+    k(x, x) = 1 counted); mmd2[l, a, b] = kernel_mean[l, a, a] + kernel_mean[l, b, b] - 2 kernel_mean[l, a, b] with a zero
+    diagonal; mmd2_sum is the equal-weight multi-kernel statistic, the sum over l.  nan wherever a label has fewer than two rows
+    (unbiased) or none; nothing is raised.  The unbiased estimate can be slightly negative."""
+    K, n = _kernel_sums(K, counts)
+    G = n.shape[0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = K / np.outer(n, n)[None]
+        d = np.arange(G)
+        kd = K[:, d, d]
+        mean[:, d, d] = 2.0 * kd / (n * (n - 1.0)) if unbiased else (2.0 * kd + n) / (n * n)
+        mean[:, d, d] = np.where(n >= (2 if unbiased else 1), mean[:, d, d], np.nan)
+        mean[:, n == 0, :] = np.nan
+        mean[:, :, n == 0] = np.nan
+        within = mean[:, d, d]
+        mmd2 = within[:, :, None] + within[:, None, :] - 2.0 * mean
+    bad = np.isnan(mmd2[:, d, d])
+    mmd2[:, d, d] = np.where(bad, np.nan, 0.0)
+    return {"kernel_mean": mean, "mmd2": mmd2, "mmd2_sum": mmd2.sum(0)}
+
+
+def hsic_from_sums(K, counts):
+    """The biased HSIC tr(K H L H) / N^2 of the rows against their labels, delta kernel on the labels, per bandwidth: float64 [L],
+    numpy only.  K, counts as in mmd_from_sums.  With p = counts / N and Kfull[a][b] the sum over ORDERED pairs with the diagonal
+    (K off the diagonal, 2 K + n_a on it) it is sum_ab Kfull[a][b] (delta_ab - p_a - p_b + sum p^2) / N^2."""
+    K, n = _kernel_sums(K, counts)
+    N = n.sum()
+    G = n.shape[0]
+    p = n / N
+    full = K.copy()
+    d = np.arange(G)
+    full[:, d, d] = 2.0 * K[:, d, d] + n
+    w = np.eye(G) - p[:, None] - p[None, :] + (p * p).sum()
+    return (full * w[None]).sum((1, 2)) / (N * N)
+
+
+def mmd(embeddings, groups=None, gammas=None, scales=RBF_SCALES, transform=None, unbiased=True):
+    """RBF-kernel MMD^2 between every two groups of a split's rows, and the HSIC of the rows against the grouping, at up to four
+    bandwidths from ONE pass of the fused Gram kernel (ops.pairdist_rbf_group_sums; nothing N x N is stored).
+
+    `embeddings`: an EmbeddingTable (its targets_group unless `groups` is given) or a device tensor [N, D] with `groups` [N] (any
+    integers; they go through np.unique, at most 8 of them: more raise DbmmUnsupported, fewer than two ValueError, both before
+    anything is launched).  `transform` as in `silhouette`.  `gammas`: 1..4 bandwidths; by default rbf_gammas(scales) of the same
+    (transformed) rows.  The rows are sorted by label with one gather, as group_stats sorts them; the centre is that copy's mean.
+    Returns mmd_from_sums' dict (indexed by the labels in np.unique order) plus 'hsic': [L] (hsic_from_sums), 'gammas', 'labels',
+    'counts'.  The kernel's precondition for its 1e-4 bound is gamma (|a|^2 + |b|^2) <= 64 for centred rows a, b: the default
+    ladder's largest gamma, 4 / m, keeps it as long as no row lies more than 4 root-mean-square radii from the centre (m is twice the mean squared radius)."""
+    x, g_np = _rows_and_groups(embeddings, groups)
+    uniq, dense, counts = np.unique(g_np, return_inverse=True, return_counts=True)
+    G, N = len(uniq), x.shape[0]
+    if G > 8:
+        raise ops.DbmmUnsupported(f"mmd: {G} labels; the kernel buckets at most 8")
+    if G < 2:
+        raise ValueError(f"mmd needs at least two labels with rows, got {G}")
+    x = x.float().contiguous()
+    if transform is not None:
+        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
+    gammas = rbf_gammas(x, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    dense = dense.reshape(-1)
+    order = np.argsort(dense, kind="stable")
+    xs = ops.gather_rows(x, torch.from_numpy(order).to(x.device))
+    center = torch.from_numpy((_column_sums(xs) / N).astype(np.float32)).to(x.device)
+    gs = torch.from_numpy(dense[order].astype(np.int64)).to(x.device)
+    K = ops.pairdist_rbf_group_sums(xs, gs, G, center, gammas.tolist()).cpu().numpy()
+    out = mmd_from_sums(K, counts, unbiased=unbiased)
+    out.update(hsic=hsic_from_sums(K, counts), gammas=gammas, labels=uniq, counts=counts)
+    return out
+
+
+def mmd_permutation_test(embeddings, groups, pair, n_perm=20, seed=0, **mmd_kw):
+    """The kernel two-sample test between the two labels in `pair`: their rows are pooled (one gather, `transform` applied once),
+    the bandwidths are fixed from the pooled rows once (`gammas`, else rbf_gammas of `scales`), and the observed mmd2_sum is compared
+    with `n_perm` relabellings.  Relabelling k is labels[rng.permutation(n)] with rng = np.random.default_rng(seed), one draw per
+    permutation in order, labels the pooled rows' 0 / 1 (pair[0] / pair[1]) in row order; each is one `mmd` call (rows re-sorted by
+    the new labels, so the kernel's fast path holds).  Returns {'stat', 'null': float64 [n_perm], 'p': (1 + #{null >= stat}) /
+    (1 + n_perm)}.  The cost is n_perm + 1 passes of the kernel over the pooled rows."""
+    x, g_np = _rows_and_groups(embeddings, groups)
+    a, b = pair
+    if a == b:
+        raise ValueError(f"mmd_permutation_test: pair = {pair!r} names one label twice")
+    idx = np.flatnonzero((g_np == a) | (g_np == b))
+    labels = (g_np[idx] == b).astype(np.int64)
+    if labels.sum() < 2 or (1 - labels).sum() < 2:
+        raise ValueError(f"mmd_permutation_test: labels {a!r} and {b!r} need at least two rows each")
+    transform = mmd_kw.pop("transform", None)
+    scales = mmd_kw.pop("scales", RBF_SCALES)
+    gammas = mmd_kw.pop("gammas", None)
+    xp = ops.gather_rows(x.float().contiguous(), torch.from_numpy(idx).to(x.device))
+    if transform is not None:
+        xp = _transformed_rows(xp, transform, TRANSFORM_ROWS)
+    gammas = rbf_gammas(xp, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    stat = float(mmd(xp, labels, gammas=gammas, **mmd_kw)["mmd2_sum"][0, 1])
+    rng = np.random.default_rng(seed)
+    null = np.array([mmd(xp, labels[rng.permutation(len(labels))], gammas=gammas, **mmd_kw)["mmd2_sum"][0, 1] for _ in range(n_perm)],
+                    dtype=np.float64).reshape(n_perm)
+    return {"stat": stat, "null": null, "p": (1.0 + float((null >= stat).sum())) / (1.0 + n_perm)}
+
+
+def dependence_report(train_table, val_table, test_table, transform=None, scales=RBF_SCALES):
+    """How much of the groups, and within each class of the spurious attribute, is left in a representation, by kernel scores:
+    {'train': r, 'val': r, 'test': r} with r = {'group': `mmd`'s mmd2_sum [G, G] over targets_group, 'spurious_within_class': {class:
+    the mmd2_sum between the two places among that class's rows, nan if only one is present}, 'hsic_spurious': the [L] HSIC of the
+    rows against targets_spurious (nan if only one place is present)}; every call takes its bandwidths from its own rows
+    (rbf_gammas of `scales`).  `transform` is applied once per split, as in separation_report: run it raw, with an adapter, and on
+    erased_table's rows -- the within-class numbers are the ones that should fall."""
+    out = {}
+    for split, table in (("train", train_table), ("val", val_table), ("test", test_table)):
+        x = _device_rows(table, transform)
+        y, c = table.targets.cpu().numpy(), table.targets_spurious.cpu().numpy()
+        within = {}
+        for cls in np.unique(y):
+            idx = np.flatnonzero(y == cls)
+            if len(np.unique(c[idx])) < 2:
+                within[int(cls)] = float("nan")
+                continue
+            within[int(cls)] = float(mmd(ops.gather_rows(x, torch.from_numpy(idx).to(x.device)), c[idx], scales=scales)["mmd2_sum"][0, 1])
+        hsic = mmd(x, c, scales=scales)["hsic"] if len(np.unique(c)) >= 2 else np.full(len(scales), np.nan)
+        out[split] = {"group": mmd(x, table.targets_group.cpu().numpy(), scales=scales)["mmd2_sum"], "spurious_within_class": within,
+                      "hsic_spurious": hsic}
+    return out
+
+
 # ---- linear concept erasure: the rows changed so that no linear classifier reads a labelling (Belrose et al. 2023, "LEACE") ---------------
 # Post-hoc debiasing of frozen embeddings, in closed form from three moments: the column sums, the scatter matrix (ops.covariance) and
 # the per-label column sums (ops.label_column_sums), each one read of the rows.  The eraser is x -> x - sum_k ((x - mean) . A_k) B_k with

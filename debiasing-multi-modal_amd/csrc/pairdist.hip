@@ -23,6 +23,14 @@
 // workgroup map is static), and pairdist_fold_kernel adds the workgroups' 64 sums in workgroup order.  Rows sorted by group make
 // nearly every tile single-bucket (the fast path: no predicates); mixed, ragged and diagonal tiles take the predicated path.
 // Workspace: the planes (4 Dp bytes per row), 8 bytes per row, 512 bytes per workgroup -- O(N D), never O(N^2).
+//
+// Element maps.  The tile kernel is a template on what a pair adds to its bucket: DistanceMap (sqrt(d^2), one sum: the kernel above) and
+// RbfMap (exp(-gamma_l d^2) for L <= 4 bandwidths: the bucket sums MMD^2 and HSIC are made of, dbmm_pairdist_rbf_group_sums).  For RbfMap
+// d^2 stays in the accumulator registers and the reduction above runs once per l, l OUTSIDE the lane's 128 elements: a runtime loop, so
+// the instructions that form a bandwidth's sums are the same whatever L is (L = 4 in one call equals four L = 1 calls bit for bit).
+// k = exp2(c_l d^2) on the hardware exponential, c_l = -gamma_l log2(e) 2^(-2s) with the split's scale exponent s read on the device.
+// Everything else -- planes, RowInfo, ring, walk, clamp, masks, wave slots, the workgroup's running sums (thread 64 l + b), the fold -- is
+// one text; the workspace grows by 512 bytes per workgroup and bandwidth.
 #include <stdlib.h>
 #include "persistent_tiles.h"
 
@@ -84,18 +92,50 @@ __global__ __launch_bounds__(256) void pairdist_split_kernel(const float* __rest
     }
 }
 
+constexpr int RBF_MAX_L = 4;                                      // bandwidths of one RBF pass: e_wsum [4][8][64] is 16 KB beside the ring
+
 struct PairDistP {
-    const u16* P; const RowInfo* info; double* part;               // part [MAX_WG][64]: a workgroup's sums per (row group * 8 + column group)
+    const u16* P; const RowInfo* info; double* part;               // part [MAX_WG][L][64]: a workgroup's sums per (l, row group * 8 + column group)
     long long ldp, p_total;                                        // halves per row of P (2 Dp), bytes of P
     int N, T, nb, n_tiles;                                         // T = Dp / 64 K tiles per plane, nb = row blocks of 256
+    const unsigned* amax_bits; double gamma[RBF_MAX_L]; int L;     // RbfMap only: the split's absmax (its scale exponent), the L bandwidths
 };
 
+// The element maps of the tile kernel: what a pair adds to its bucket, from its d^2 >= 0 in scaled units (2^-2s of the rows' own).
+// pre() is applied once to every accumulator element, in place; val(a, coef(p, l)) is summed, once per l < n_sums(p).
+struct DistanceMap {                                               // ||x_i - x_j||: one sum per bucket, in units of 2^-s
+    static constexpr int MAX_L = 1;
+    static constexpr bool SCALED = true;
+    static __device__ __forceinline__ int n_sums(const PairDistP&) { return 1; }
+    static __device__ __forceinline__ float pre(float d2) { return __builtin_sqrtf(d2); }
+    static __device__ __forceinline__ float coef(const PairDistP&, int) { return 0.f; }
+    static __device__ __forceinline__ float val(float a, float) { return a; }
+    static __device__ __forceinline__ float per_group(float c) { return c; }
+};
+struct RbfMap {                                                    // exp(-gamma_l ||x_i - x_j||^2), l < L: d^2 stays in the registers, L sums per bucket
+    static constexpr int MAX_L = RBF_MAX_L;
+    static constexpr bool SCALED = false;
+    static __device__ __forceinline__ int n_sums(const PairDistP& p) { return p.L; }
+    static __device__ __forceinline__ float pre(float d2) { return d2; }
+    // c_l = -gamma_l log2(e) 2^(-2s), formed in float64 (|s| <= 60: either factor alone may leave fp32's range) and rounded once
+    static __device__ __forceinline__ float coef(const PairDistP& p, int l) {
+        const double u = (double)pow2f(-scale_exp(__uint_as_float(*p.amax_bits)));
+        return (float)(-p.gamma[l] * 1.4426950408889634 * u * u);
+    }
+    // the hardware exponential on a non-positive argument: underflow to 0 is the answer
+    static __device__ __forceinline__ float val(float a, float c) { return __builtin_amdgcn_exp2f(c * a); }
+    // the predicated path's coefficient, opaque per row group: hoisted out of that loop the 128 float64 kernel values of a lane would
+    // have to live across it, and the registers go to them instead of d^2
+    static __device__ __forceinline__ float per_group(float c) { asm volatile("" : "+v"(c)); return c; }
+};
+
+template <class Map>
 __global__ __launch_bounds__(512, 1) void pairdist_tile_kernel(const PairDistP p) {
     __shared__ __attribute__((aligned(1024))) unsigned char lds[8 * PH_HALF];      // [buffer 2][Ah0, Bh0, Bh1, Ah1] = 128 KB
     __shared__ float e_norm[512];                                  // epilogue: norms of the tile's 256 rows, then of its 256 columns
     __shared__ unsigned char e_grp[512];
     __shared__ unsigned e_mask[2];                                 // groups present among the rows / the columns
-    __shared__ double e_wsum[8][64];                               // per wave, per bucket
+    __shared__ double e_wsum[Map::MAX_L][8][64];                   // per sum l, per wave, per bucket
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 2, wc = wid & 3;
     const int fr = lane & 31, fh = lane >> 5;
@@ -141,7 +181,8 @@ __global__ __launch_bounds__(512, 1) void pairdist_tile_kernel(const PairDistP p
 
     const int n_items = walk.n_whole;
     const int wm0 = wr * 128, wn0 = wc * 64;
-    double total = 0.0;                                               // thread b < 64: this workgroup's sum of bucket b
+    const int nl = Map::n_sums(p);
+    double total = 0.0;                                               // thread 64 l + b, l < nl: this workgroup's sum l of bucket b
     if (tid < 2) e_mask[tid] = 0u;
     if (n_items > 0) { set_tile(walk.first); ring_prologue(0); }
     for (int k = 0; k < n_items; ++k) {
@@ -171,88 +212,88 @@ __global__ __launch_bounds__(512, 1) void pairdist_tile_kernel(const PairDistP p
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float rn = e_norm[wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh];
-                acc[i][0][r] = __builtin_sqrtf(fmaxf(fmaf(-2.f, acc[i][0][r], rn + cn0), 0.f));
-                acc[i][1][r] = __builtin_sqrtf(fmaxf(fmaf(-2.f, acc[i][1][r], rn + cn1), 0.f));
+                acc[i][0][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][0][r], rn + cn0), 0.f));
+                acc[i][1][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][1][r], rn + cn1), 0.f));
             }
-        if (fast) {
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s += (double)acc[i][0][r] + (double)acc[i][1][r];
-            s = wave_sum_f64(s);
-            if (lane == 0) e_wsum[wid][(__builtin_ctz(mA) << 3) + __builtin_ctz(mB)] = s;
-        } else {
-            const int gb0 = e_grp[256 + c0], gb1 = e_grp[256 + c0 + 1];
-            for (unsigned ma = mA; ma; ma &= ma - 1) {
-                const int ga = __builtin_ctz(ma);
-                double v0 = 0.0, v1 = 0.0;
+        // one reduction per sum l, the same whatever nl is: l outside the lane's 128 elements, no second copy of the tile
+#pragma unroll 1
+        for (int l = 0; l < nl; ++l) {
+            const float cf = Map::coef(p, l);
+            if (fast) {
+                double s = 0.0;
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int lr = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                        const bool in = e_grp[lr] == ga;
-                        v0 += (in && (!diag || lr < c0)) ? (double)acc[i][0][r] : 0.0;
-                        v1 += (in && (!diag || lr < c0 + 1)) ? (double)acc[i][1][r] : 0.0;
+                    for (int r = 0; r < 16; ++r) s += (double)Map::val(acc[i][0][r], cf) + (double)Map::val(acc[i][1][r], cf);
+                s = wave_sum_f64(s);
+                if (lane == 0) e_wsum[l][wid][(__builtin_ctz(mA) << 3) + __builtin_ctz(mB)] = s;
+            } else {
+                const int gb0 = e_grp[256 + c0], gb1 = e_grp[256 + c0 + 1];
+                for (unsigned ma = mA; ma; ma &= ma - 1) {
+                    const int ga = __builtin_ctz(ma);
+                    const float cg = Map::per_group(cf);
+                    double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int lr = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                            const bool in = e_grp[lr] == ga;
+                            v0 += (in && (!diag || lr < c0)) ? (double)Map::val(acc[i][0][r], cg) : 0.0;
+                            v1 += (in && (!diag || lr < c0 + 1)) ? (double)Map::val(acc[i][1][r], cg) : 0.0;
+                        }
+                    for (unsigned mb = mB; mb; mb &= mb - 1) {
+                        const int gb = __builtin_ctz(mb);
+                        const double s = wave_sum_f64((gb0 == gb ? v0 : 0.0) + (gb1 == gb ? v1 : 0.0));
+                        if (lane == 0) e_wsum[l][wid][(ga << 3) + gb] = s;
                     }
-                for (unsigned mb = mB; mb; mb &= mb - 1) {
-                    const int gb = __builtin_ctz(mb);
-                    const double s = wave_sum_f64((gb0 == gb ? v0 : 0.0) + (gb1 == gb ? v1 : 0.0));
-                    if (lane == 0) e_wsum[wid][(ga << 3) + gb] = s;
                 }
             }
         }
         __syncthreads();
-        if (tid < 64 && ((mA >> (tid >> 3)) & 1u) && ((mB >> (tid & 7)) & 1u)) {
+        if (tid < 64 * nl && ((mA >> ((tid & 63) >> 3)) & 1u) && ((mB >> (tid & 7)) & 1u)) {
             double s = 0.0;
 #pragma unroll
-            for (int w = 0; w < 8; ++w) s += e_wsum[w][tid];
+            for (int w = 0; w < 8; ++w) s += e_wsum[tid >> 6][w][tid & 63];
             total += s;
         }
         __syncthreads();
         if (tid < 2) e_mask[tid] = 0u;                                // for the next tile: its atomics come after that tile's ring barriers
     }
-    if (tid < 64) p.part[(size_t)blockIdx.x * 64 + tid] = total;
+    if (tid < 64 * nl) p.part[(size_t)blockIdx.x * (64 * nl) + tid] = total;
 }
 
-// workgroup sums -> S [G][G]: bucket (a, b) of the kernel is "row in group a, column in group b"; unordered pairs fold (a, b) and (b, a)
+// workgroup sums -> S [L][G][G], block l folds sum l: bucket (a, b) of the kernel is "row in group a, column in group b"; unordered pairs
+// fold (a, b) and (b, a).  amax_bits: distances were taken in units of 2^-s and are rescaled; null for kernel values, which have no unit
 __global__ __launch_bounds__(64) void pairdist_fold_kernel(const double* __restrict__ part, int n_wg, const unsigned* __restrict__ amax_bits, int G,
                                                            double* __restrict__ S) {
     __shared__ double tot[64];
-    const int b = threadIdx.x;
+    const int b = threadIdx.x, l = blockIdx.x, nl = gridDim.x;
     double s = 0.0;
-    for (int w = 0; w < n_wg; ++w) s += part[(size_t)w * 64 + b];
+    for (int w = 0; w < n_wg; ++w) s += part[((size_t)w * nl + l) * 64 + b];
     tot[b] = s;
     __syncthreads();
     const int ga = b >> 3, gb = b & 7;
     if (ga < G && gb < G) {
-        const int e = -scale_exp(__uint_as_float(*amax_bits));       // distances were taken in units of 2^-s
+        const int e = amax_bits ? -scale_exp(__uint_as_float(*amax_bits)) : 0;
         const double v = ga == gb ? tot[b] : tot[(ga << 3) + gb] + tot[(gb << 3) + ga];
-        S[ga * G + gb] = ldexp(v, e);
+        S[(l * G + ga) * G + gb] = ldexp(v, e);
     }
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline long long padded_dim(long long D) { return (D + 127) / 128 * 128; }
 
-}  // namespace
-
-// see include/dbmm.h
-extern "C" size_t dbmm_workspace_bytes_pairdist(int64_t N, int64_t D) {
-    if (N <= 0 || D <= 0) return 0;
+// the workspace of a bucket pass with L sums per bucket: head, RowInfo, planes, the workgroups' partials
+inline size_t bucket_workspace_bytes(int64_t N, int64_t D, int64_t L) {
     const size_t Dp = (size_t)padded_dim(D);
-    return HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256) + align_up((size_t)N * 2 * Dp * 2, 256) + (size_t)MAX_WG * 64 * sizeof(double);
+    return HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256) + align_up((size_t)N * 2 * Dp * 2, 256) + (size_t)MAX_WG * (size_t)L * 64 * sizeof(double);
 }
 
-// see include/dbmm.h
-extern "C" int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N, int64_t D,
-                                        int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > 8) return DBMM_E_SHAPE;
-    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
-    if (!x || !groups || !center || !sums || !workspace) return DBMM_E_ARG;
-    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
-    if (workspace_bytes < dbmm_workspace_bytes_pairdist(N, D)) return DBMM_E_WORKSPACE;
+// absmax, split, tiles, fold for one element map; the operands have been checked.  gammas: RbfMap's L bandwidths (host), else null and L = 1
+template <class Map>
+int bucket_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums, int64_t N, int64_t D, int64_t G,
+                void* workspace, void* stream) {
     const long long Dp = padded_dim(D);
     char* ws = (char*)workspace;
     unsigned* amax = (unsigned*)ws;
@@ -273,14 +314,54 @@ extern "C" int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, c
     p.P = P; p.info = info; p.part = part;
     p.ldp = 2 * Dp; p.p_total = (long long)N * 2 * Dp * 2;
     p.N = (int)N; p.T = (int)(Dp / 64); p.nb = (int)((N + 255) / 256);
+    p.amax_bits = amax; p.L = (int)L;
+    for (int l = 0; gammas && l < L; ++l) p.gamma[l] = gammas[l];
     const long long nt = (long long)p.nb * (p.nb + 1) / 2;
     p.n_tiles = (int)nt;
     const int grid = nt < MAX_WG ? (int)nt : MAX_WG;
-    hipLaunchKernelGGL(pairdist_tile_kernel, dim3(grid), dim3(512), 0, s, p);
+    hipLaunchKernelGGL(pairdist_tile_kernel<Map>, dim3(grid), dim3(512), 0, s, p);
     DBMM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pairdist_fold_kernel, dim3(1), dim3(64), 0, s, part, grid, amax, (int)G, sums);
+    hipLaunchKernelGGL(pairdist_fold_kernel, dim3((unsigned)L), dim3(64), 0, s, part, grid, Map::SCALED ? amax : (const unsigned*)nullptr, (int)G, sums);
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
+}
+
+}  // namespace
+
+// see include/dbmm.h
+extern "C" size_t dbmm_workspace_bytes_pairdist(int64_t N, int64_t D) {
+    if (N <= 0 || D <= 0) return 0;
+    return bucket_workspace_bytes(N, D, 1);
+}
+
+// see include/dbmm.h
+extern "C" int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N, int64_t D,
+                                        int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
+    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > 8) return DBMM_E_SHAPE;
+    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
+    if (!x || !groups || !center || !sums || !workspace) return DBMM_E_ARG;
+    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
+    if (workspace_bytes < dbmm_workspace_bytes_pairdist(N, D)) return DBMM_E_WORKSPACE;
+    return bucket_sums<DistanceMap>(x, groups, center, nullptr, 1, sums, N, D, G, workspace, stream);
+}
+
+// see include/dbmm.h
+extern "C" size_t dbmm_workspace_bytes_pairdist_rbf(int64_t N, int64_t D, int64_t L) {
+    if (N <= 0 || D <= 0 || L < 1 || L > RBF_MAX_L) return 0;
+    return bucket_workspace_bytes(N, D, L);
+}
+
+// see include/dbmm.h
+extern "C" int dbmm_pairdist_rbf_group_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums,
+                                            int64_t N, int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
+    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > 8 || L < 1 || L > RBF_MAX_L) return DBMM_E_SHAPE;
+    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
+    if (!x || !groups || !center || !gammas || !sums || !workspace) return DBMM_E_ARG;
+    for (int l = 0; l < L; ++l)
+        if (!(gammas[l] > 0.0) || !(gammas[l] <= 1.79769313486231570e308)) return DBMM_E_ARG;      // finite and positive
+    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
+    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rbf(N, D, L)) return DBMM_E_WORKSPACE;
+    return bucket_sums<RbfMap>(x, groups, center, gammas, L, sums, N, D, G, workspace, stream);
 }
 
 // ---- per-row, per-group sums: R[i][g] = sum over j != i with group[j] == g of ||x_i - x_j||_2, float64 [N][G] (the silhouette's input) -------

@@ -1584,7 +1584,47 @@ def pairdist_group_sums(x, groups, n_groups, center):
     return out
 
 
-PAIRDIST_ROWS_MAX_G = 16             # labels of the per-row distance sums (csrc/pairdist.hip); the value of KMEANS_MAX_K
+PAIRDIST_RBF_MAX_L = 4               # bandwidths of one RBF bucket pass (csrc/pairdist.hip: RBF_MAX_L)
+
+
+def _rbf_gammas(what, gammas):
+    """1..PAIRDIST_RBF_MAX_L finite numbers > 0 as a ctypes double array, else DbmmError naming the value"""
+    try:
+        vals = [float(g) for g in gammas]
+    except (TypeError, ValueError):
+        raise _lib.DbmmError(f"{what}: gammas must be a sequence of 1..{PAIRDIST_RBF_MAX_L} positive numbers, got {gammas!r}") from None
+    if not 1 <= len(vals) <= PAIRDIST_RBF_MAX_L:
+        raise _lib.DbmmError(f"{what}: {len(vals)} gammas; the kernel sums 1..{PAIRDIST_RBF_MAX_L} bandwidths in one pass")
+    for v in vals:
+        if not (v > 0 and math.isfinite(v)):
+            raise _lib.DbmmError(f"{what}: gamma = {v!r}; every bandwidth must be finite and > 0")
+    return (ctypes.c_double * len(vals))(*vals)
+
+
+def pairdist_rbf_group_sums(x, groups, n_groups, center, gammas):
+    """K float64 [L, G, G], symmetric in its last two axes: K[l, a, b] = sum over unordered pairs i < j with {groups[i], groups[j]} =
+    {a, b} of exp(-gammas[l] ||x[i] - x[j]||^2), on the fused Gram kernel (dbmm_pairdist_rbf_group_sums): pairdist_group_sums'
+    pass with the exponential for the square root, L bandwidths from one Gram product, no N x N matrix, float64 sums in a fixed
+    order -- the same bits on every call, and a bandwidth's sums do not depend on the others in the call.  Operands as
+    pairdist_group_sums; gammas: 1..4 finite numbers > 0 (host values).  The diagonal is left out by index: a V-statistic adds the
+    group's row count to K[l, a, a]."""
+    gam = _rbf_gammas("pairdist_rbf_group_sums", gammas)                            # host values: refused before any device is touched
+    N, D = _rows_operand("pairdist_rbf_group_sums", x)
+    _ids_operand("pairdist_rbf_group_sums", "groups", groups, x)
+    _f32_operand("pairdist_rbf_group_sums", "center", center, x, D)
+    if not 1 <= n_groups <= 8:
+        raise _lib.DbmmError(f"pairdist_rbf_group_sums: n_groups = {n_groups} outside 1..8")
+    L = _lib.lib()
+    nbytes = L.dbmm_workspace_bytes_pairdist_rbf(N, D, len(gam))
+    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # the planes: sized by the call, not cached
+    out = _empty((len(gam), n_groups, n_groups), device=x.device, dtype=torch.float64)
+    rc = L.dbmm_pairdist_rbf_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), ctypes.addressof(gam), len(gam), out.data_ptr(), N, D,
+                                        n_groups, ws.data_ptr(), ws.numel() * 4, stream())
+    _served(rc, "pairdist_rbf_group_sums", f"N = {N}, D = {D}")
+    return out
+
+
+PAIRDIST_ROWS_MAX_G = 16            # labels of the per-row distance sums (csrc/pairdist.hip); the value of KMEANS_MAX_K
 
 
 def pairdist_row_group_sums(x, groups, n_groups, center):

@@ -848,6 +848,22 @@ size_t dbmm_workspace_bytes_pairdist(int64_t N, int64_t D);
 int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N,
                              int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Group-wise sums of RBF kernel values for L bandwidths in one pass (what MMD^2 and HSIC need of the Gram matrix), without N x N:
+ *   sums double [L][G][G], symmetric in (a, b): sums[l][a][b] = sum over unordered pairs i < j with {groups[i], groups[j]} = {a, b}
+ *   of exp(-gammas[l] ||x[i] - x[j]||^2).  The diagonal is excluded by index: a V-statistic adds n_a (K_ii = 1) on the host.
+ * Operands, centring, split, d^2 and the walk of dbmm_pairdist_group_sums: the same tile kernel with another element map.  d^2 stays
+ * in the accumulator registers; per bandwidth every element goes through the hardware exp2 (the argument is <= 0, underflow to 0 is
+ * the answer) and the distance kernel's reduction (lane, wave, eight wave slots, workgroup, workgroups in order: float64, no
+ * floating-point atomics), so two calls give the same bits and a bandwidth's sums do not depend on L or on its position.
+ * gammas: a HOST array of L finite doubles > 0, read at call time (else DBMM_E_ARG).  L outside 1..4, G outside 1..8, N outside
+ * 1..2^23: DBMM_E_SHAPE; D % 64 != 0 or D > 4096: DBMM_E_UNSUPPORTED; x, center and the workspace 16-byte aligned.  A d^2 is good to
+ * about 7e-7 of its two rows' centred squared norms, a kernel value relatively to gamma times that.  The workspace is its own size:
+ * dbmm_workspace_bytes_pairdist's with L x 512 bytes per workgroup instead of 512 (0 for L outside 1..4). */
+size_t dbmm_workspace_bytes_pairdist_rbf(int64_t N, int64_t D, int64_t L);
+int dbmm_pairdist_rbf_group_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L,
+                                 double* sums, int64_t N, int64_t D, int64_t G, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 /* Per-row, per-group sums of Euclidean distances without the N x N matrix (what a silhouette needs of the distances):
  *   sums double [N][G]: sums[i][g] = sum over j != i with groups[j] == g of ||x[i] - x[j]||_2.
  * Operands, centring, split and distance arithmetic of dbmm_pairdist_group_sums; the kernel walks the full square of 256 x 256
