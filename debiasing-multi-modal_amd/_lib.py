@@ -228,6 +228,8 @@ _SIGS = {
     "dbmm_pairdist_rbf_group_sums": [_P, _P, _P, _P, _L, _P, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_pairdist_rows": [_L, _L, _L],
     "dbmm_pairdist_row_group_sums": [_P, _P, _P, _P, _L, _L, _L, _P, _Z, _P],
+    "dbmm_workspace_bytes_pairdist_rbf_rows": [_L, _L, _L, _L],
+    "dbmm_pairdist_rbf_row_group_sums": [_P, _P, _P, _P, _L, _P, _L, _L, _L, _P, _Z, _P],
     "dbmm_workspace_bytes_covariance": [_L, _L],
     "dbmm_covariance": [_P, _P, _P, _L, _L, _P, _Z, _P],
     "dbmm_project_rows": [_P, _P, _P, _P, _L, _L, _L, _P],
@@ -262,6 +264,7 @@ _RESTYPES = {
     "dbmm_workspace_bytes_pairdist": c_size_t,
     "dbmm_workspace_bytes_pairdist_rbf": c_size_t,
     "dbmm_workspace_bytes_pairdist_rows": c_size_t,
+    "dbmm_workspace_bytes_pairdist_rbf_rows": c_size_t,
     "dbmm_workspace_bytes_covariance": c_size_t,
     "dbmm_workspace_bytes_sym_eig": c_size_t,
     "dbmm_workspace_bytes_kmeans": c_size_t,

@@ -769,6 +769,334 @@ def dependence_report(train_table, val_table, test_table, transform=None, scales
     return out
 
 
+# ---- per-row kernel sums: a kernel probe, the MMD witness function and a normalised HSIC (CKA) --------------------------------------------
+# All three are made of R[l, i, g] = sum over j != i with label g of exp(-gamma_l ||x_i - x_j||^2), which ops.pairdist_rbf_row_group_sums gives
+# in one pass with nothing N x N stored.  The probe is the leave-one-out Parzen-window classifier (no training, no learning rate): whether
+# a labelling is still readable NON-linearly, as an accuracy, where after an erasure every linear probe is at chance by construction.  The
+# witness function (Gretton et al. 2012, section 2.3) names the rows that make two groups differ.  The alignment (Cortes et al. 2012;
+# the CKA of Kornblith et al. 2019 with the labels' delta kernel) is HSIC on a scale that can be compared across representations.
+
+KERNEL_REL = 1e-4   # the kernels' relative bound on a kernel value under their preconditions (csrc/pairdist.hip)
+
+
+def _sums_operands(what, R, labels, counts):
+    R = np.asarray(R, dtype=np.float64)
+    g = np.asarray(labels).astype(np.int64).ravel()
+    n = np.asarray(counts).astype(np.int64).ravel()
+    if R.ndim != 3 or g.shape != (R.shape[1],) or n.shape != (R.shape[2],):
+        raise ValueError(f"{what}: R {R.shape} is not [L, N, G] for {g.shape[0]} labels and {n.shape[0]} counts")
+    if g.size and (g.min() < -1 or g.max() >= R.shape[2]):
+        raise ValueError(f"{what}: labels must lie in [0, {R.shape[2]}) or be -1 (a query row)")
+    return R, g, n
+
+
+def _densities(R, g, n):
+    """(density [L, N, G], denominators [N, G]): R / (counts[g] - [labels[i] == g]), nan where that is 0"""
+    den = np.broadcast_to(n[None, :], (g.shape[0], n.shape[0])).copy()
+    own = np.flatnonzero(g >= 0)
+    den[own, g[own]] -= 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        density = np.where(den[None] > 0, R / np.where(den > 0, den, 1)[None].astype(np.float64), np.nan)
+    return density, den
+
+
+def parzen_from_sums(R, labels, counts, prior="uniform"):
+    """The host step of `kernel_probe`, numpy only.  R float64 [L, N, G] as ops.pairdist_rbf_row_group_sums returns it (the row itself
+    left out); labels int [N]: dense labels in [0, G), or -1 for a query row (in no label's sum); counts [G]: the REFERENCE rows per
+    label.  density[l, i, g] = R[l, i, g] / (counts[g] - [labels[i] == g]): the leave-one-out Parzen-window estimate of label g's
+    density at row i, up to the kernel's normalising constant, which is common to all labels; nan where that denominator is 0 (an
+    empty label; a label's only row, for its own label).  score is density for prior="uniform" (every label equally likely: the
+    balanced classifier) and R itself for prior="empirical" (the label frequencies as prior: the Nadaraya-Watson vote).  pred[l, i]
+    is the argmax of score over the labels with a denominator > 0, the lowest label on a tie, -1 for a row whose scores are all 0
+    (or that has no scorable label); margin[l, i] = (top1 - top2) / top1 of those scores, nan if top1 == 0 or fewer than two
+    labels are scorable.  Returns {'density', 'score': [L, N, G], 'pred': int64 [L, N], 'margin': [L, N]}.  Another `prior`,
+    shapes that do not match and labels outside [-1, G) raise ValueError."""
+    if prior not in ("uniform", "empirical"):
+        raise ValueError(f"parzen_from_sums: prior = {prior!r}; 'uniform' or 'empirical'")
+    R, g, n = _sums_operands("parzen_from_sums", R, labels, counts)
+    density, den = _densities(R, g, n)
+    ok = den > 0
+    score = density if prior == "uniform" else np.where(ok[None], R, np.nan)
+    s = np.where(ok[None], score, -np.inf)                             # scores are >= 0: -inf never wins against a scorable label
+    L, N, G = R.shape
+    pred = s.argmax(axis=2) if G else np.zeros((L, N), dtype=np.int64)  # the first maximum: the lowest label on a tie
+    top = np.sort(s, axis=2)[:, :, ::-1]
+    top1 = top[:, :, 0] if G else np.full((L, N), -np.inf)
+    pred = np.where(top1 > 0, pred, -1).astype(np.int64)
+    if G >= 2:
+        top2 = top[:, :, 1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            margin = np.where((top1 > 0) & (ok.sum(1) >= 2)[None], (top1 - np.where(np.isfinite(top2), top2, 0.0)) / np.where(top1 > 0, top1, 1.0), np.nan)
+    else:
+        margin = np.full((L, N), np.nan)
+    return {"density": density, "score": score, "pred": pred, "margin": margin}
+
+
+def witness_from_sums(R, labels, counts, a, b):
+    """The empirical MMD witness function between the labels a and b at every row, float64 [L, N], numpy only: density[:, :, a] -
+    density[:, :, b] with parzen_from_sums' leave-one-out densities (R, labels, counts as there; a, b dense label indices).  Positive
+    where a's rows are denser than b's.  The identity that ties it to `mmd`: its mean over the rows of a minus its mean over the
+    rows of b is the unbiased mmd2[l, a, b] of mmd_from_sums.  nan where a label has no row (or only the row itself)."""
+    R, g, n = _sums_operands("witness_from_sums", R, labels, counts)
+    G = n.shape[0]
+    if not (0 <= a < G and 0 <= b < G) or a == b:
+        raise ValueError(f"witness_from_sums: a = {a!r}, b = {b!r}; two different labels in [0, {G})")
+    density, _ = _densities(R, g, n)
+    return density[:, :, a] - density[:, :, b]
+
+
+def alignment_from_sums(K, K2_total, row_sq, counts):
+    """The host step of `kernel_alignment`, numpy only: the normalised HSIC (centred kernel alignment) of the RBF kernel against the
+    delta kernel of the labels, per bandwidth.  Ordered pairs, the diagonal k(x, x) = 1 included, p = counts / N:
+      hsic    = tr(K H L H) / N^2 = hsic_from_sums(K, counts);
+      hsic_kk = tr(K H K H) / N^2 = (A - 2 B / N + C^2 / N^2) / N^2, A = sum_ij k_ij^2 = N + 2 K2_total (k^2 is the kernel at 2 gamma),
+                B = sum_i (row sum of k)^2 = row_sq, C = sum_ij k_ij (K's own total);
+      hsic_ll = tr(L H L H) / N^2 = sum p^2 - 2 sum p^3 + (sum p^2)^2;
+      alignment = hsic / sqrt(hsic_kk hsic_ll), in [0, 1] up to rounding.
+    K float64 [L, G, G] as ops.pairdist_rbf_group_sums returns it at gamma (unordered pairs, the diagonal left out); K2_total [L]:
+    the sum over all unordered pairs at 2 gamma; row_sq [L]: sum_i (1 + sum_g R[l, i, g])^2; counts [G].
+    rel_bound [L] is the first-order propagation of the kernels' 1e-4 on every kernel value into the alignment:
+    b_kl / |hsic| + b_kk / (2 hsic_kk), b_kl = 1e-4 sum_ab Kfull_ab |w_ab| / N^2 (w as in hsic_from_sums), b_kk = 1e-4 (A + 4 B / N +
+    2 C^2 / N^2) / N^2.  It is part of the result on purpose: the centred quantities are differences of sums that nearly cancel when
+    the kernel is nearly constant (wide bandwidths in high D), and a bound above 1 says the alignment has no digits left.
+    Returns {'alignment', 'hsic', 'hsic_kk', 'hsic_ll' (a number), 'rel_bound'}: float64 [L]."""
+    K, n = _kernel_sums(K, counts)
+    L, G = K.shape[0], n.shape[0]
+    K2 = np.asarray(K2_total, dtype=np.float64).ravel()
+    B = np.asarray(row_sq, dtype=np.float64).ravel()
+    if K2.shape != (L,) or B.shape != (L,):
+        raise ValueError(f"alignment_from_sums: K {K.shape}, K2_total {K2.shape}, row_sq {B.shape}")
+    N = n.sum()
+    if not N > 0:
+        raise ValueError("alignment_from_sums: no rows")
+    p = n / N
+    d = np.arange(G)
+    full = K.copy()
+    full[:, d, d] = 2.0 * K[:, d, d] + n
+    w = np.eye(G) - p[:, None] - p[None, :] + (p * p).sum()
+    hsic = hsic_from_sums(K, counts)
+    A, C = N + 2.0 * K2, full.sum((1, 2))
+    hsic_kk = (A - 2.0 * B / N + C * C / (N * N)) / (N * N)
+    hsic_ll = (p ** 2).sum() - 2.0 * (p ** 3).sum() + (p ** 2).sum() ** 2
+    b_kl = KERNEL_REL * (full * np.abs(w)[None]).sum((1, 2)) / (N * N)
+    b_kk = KERNEL_REL * (A + 4.0 * B / N + 2.0 * C * C / (N * N)) / (N * N)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        alignment = hsic / np.sqrt(hsic_kk * hsic_ll)
+        rel_bound = b_kl / np.abs(hsic) + 0.5 * b_kk / hsic_kk
+    return {"alignment": alignment, "hsic": hsic, "hsic_kk": hsic_kk, "hsic_ll": float(hsic_ll), "rel_bound": rel_bound}
+
+
+def _labelled_rows(what, embeddings, labels, max_labels):
+    """(x, unique labels, dense ids [N], counts): the labels are counted and refused BEFORE the rows are looked at (more than
+    `max_labels`: DbmmUnsupported, fewer than two: ValueError), the rows must be device-resident"""
+    if isinstance(embeddings, trainer.EmbeddingTable):
+        x = embeddings.embeddings
+        labels = embeddings.targets_group if labels is None else labels
+    else:
+        x = embeddings
+    if labels is None:
+        raise ValueError(f"{what}: a device tensor of embeddings needs its `labels` array")
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError(f"{what}: the rows must be an EmbeddingTable or a tensor [N, D]")
+    l_np = (labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)).ravel()
+    if l_np.shape[0] != x.shape[0]:
+        raise ValueError(f"{what}: {l_np.shape[0]} labels for {x.shape[0]} rows")
+    uniq, dense, counts = np.unique(l_np, return_inverse=True, return_counts=True)
+    if len(uniq) > max_labels:
+        raise ops.DbmmUnsupported(f"{what}: {len(uniq)} labels; the kernel sums at most {max_labels}")
+    if len(uniq) < 2:
+        raise ValueError(f"{what} needs at least two labels with rows, got {len(uniq)}")
+    if not x.is_cuda:
+        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+    return x, uniq, dense.reshape(-1).astype(np.int64), counts
+
+
+def _sorted_row_sums(x, dense, G, gammas, extra=None):
+    """ops.pairdist_rbf_row_group_sums of the rows x sorted by their dense label (one gather; nearly every tile of the kernel then
+    holds one label), followed by the rows `extra` with label -1, centred on the mean of what is passed; R float64 [L, N (+ M), G] on
+    the host in the INPUT's row order, x's rows first"""
+    order = np.argsort(dense, kind="stable")
+    gs = dense[order]
+    if extra is not None:
+        order = np.concatenate([order, x.shape[0] + np.arange(extra.shape[0], dtype=np.int64)])
+        gs = np.concatenate([gs, np.full(extra.shape[0], -1, dtype=np.int64)])
+        x = torch.cat([x, extra])
+    xs = ops.gather_rows(x, torch.from_numpy(order).to(x.device))
+    center = torch.from_numpy((_column_sums(xs) / xs.shape[0]).astype(np.float32)).to(x.device)
+    Rs = ops.pairdist_rbf_row_group_sums(xs, torch.from_numpy(gs).to(x.device), G, center, np.asarray(gammas, dtype=np.float64).tolist()).cpu().numpy()
+    R = np.empty_like(Rs)
+    R[:, order] = Rs
+    return R
+
+
+def _probe_scores(pred, true, G):
+    """accuracy [L], recall [L, G] (nan for a label without rows), balanced accuracy [L] (the mean of the non-nan recalls) of the
+    dense predictions pred [L, n] against the dense labels true [n]"""
+    hit = pred == true[None, :]
+    recall = np.full((pred.shape[0], G), np.nan)
+    for g in range(G):
+        rows = true == g
+        if rows.any():
+            recall[:, g] = hit[:, rows].mean(1)
+    return {"accuracy": hit.mean(1), "recall": recall, "balanced_accuracy": np.nanmean(recall, axis=1)}
+
+
+def kernel_probe(embeddings, labels=None, gammas=None, scales=RBF_SCALES, transform=None, prior="uniform", query=None, query_labels=None):
+    """The kernel probe: a Parzen-window (kernel density) classifier of a labelling on a split's rows, RBF kernel, at up to four
+    bandwidths from ONE pass of the fused Gram kernel (ops.pairdist_rbf_row_group_sums; nothing N x N is stored).  No training and
+    no learning rate: it answers "is the attribute still readable non-linearly, and from which rows" as an accuracy.
+
+    `embeddings`: an EmbeddingTable (its targets_group unless `labels` is given) or a device tensor [N, D] with `labels` [N] (any
+    integers; they go through np.unique, at most 16 of them: more raise DbmmUnsupported, fewer than two ValueError, both before
+    anything is launched).  `transform` and the default bandwidths as in `mmd` (rbf_gammas(scales) of the transformed rows).  The
+    rows are sorted by label with one gather, the centre is the mean of what is passed to the kernel, and everything is returned
+    in the input's row order.
+
+    Without `query` every row is scored leave-one-out against the other rows of the split.  With `query`, a device tensor [M, D]
+    that gets the same `transform`, the query rows are appended with label -1 and scored against the reference rows only (a row
+    with label -1 is in nobody's sums); the bandwidths come from the reference rows, and the per-row outputs are those of the M
+    query rows.  `prior`: parzen_from_sums'.
+
+    Returns {'density': float64 [L, n, G], 'pred': [L, n] (values of `labels`; -1 for a row whose scores are all 0), 'margin':
+    [L, n], 'gammas', 'labels': the unique labels, 'counts'} and, where the true labels are known (leave-one-out, or `query_labels`
+    [M], values of `labels`), 'accuracy' [L], 'recall' [L, G] (nan for a label without scored rows) and 'balanced_accuracy' [L],
+    the mean of the non-nan recalls.
+
+    Read `margin` beside `pred`.  A kernel value is good to 1e-4 relative, and in high D at wide bandwidths the kernel is nearly
+    constant, so the densities of different labels differ by less than that for many rows: in the float64 CPU study of this
+    function 57 % of isotropic rows in D = 1024 at scale 0.25 had a margin below 1e-3, and 3 - 27 % of the rows of the synthetic
+    embedding tables at the default ladder.  A prediction with such a margin is decided by rounding."""
+    if prior not in ("uniform", "empirical"):
+        raise ValueError(f"kernel_probe: prior = {prior!r}; 'uniform' or 'empirical'")
+    if query is not None and labels is None and not isinstance(embeddings, trainer.EmbeddingTable):
+        raise ValueError("kernel_probe: `query` rows are scored against labelled reference rows; give `labels`")
+    x, uniq, dense, counts = _labelled_rows("kernel_probe", embeddings, labels, ops.PAIRDIST_ROWS_MAX_G)
+    G, N = len(uniq), x.shape[0]
+    true = dense
+    if query is not None:
+        if not torch.is_tensor(query) or not query.is_cuda or query.dim() != 2 or query.shape[1] != x.shape[1] or query.shape[0] < 1:
+            raise ValueError(f"kernel_probe: query must be a device tensor [M, {x.shape[1]}]")
+        true = None
+        if query_labels is not None:
+            q_np = (query_labels.detach().cpu().numpy() if torch.is_tensor(query_labels) else np.asarray(query_labels)).ravel()
+            pos = np.minimum(np.searchsorted(uniq, q_np), G - 1)
+            if q_np.shape[0] != query.shape[0] or not np.array_equal(uniq[pos], q_np):
+                raise ValueError("kernel_probe: query_labels must be one value of `labels` per query row")
+            true = pos.astype(np.int64)
+    x = x.float().contiguous()
+    if transform is not None:
+        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
+    q = None
+    if query is not None:
+        q = query.float().contiguous()
+        if transform is not None:
+            q = _transformed_rows(q, transform, TRANSFORM_ROWS)
+    gammas = rbf_gammas(x, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    R = _sorted_row_sums(x, dense, G, gammas, extra=q)
+    if q is None:
+        fit = parzen_from_sums(R, dense, counts, prior)
+    else:
+        fit = parzen_from_sums(R[:, N:], np.full(q.shape[0], -1, dtype=np.int64), counts, prior)
+    pred = fit["pred"]
+    out = {"density": fit["density"], "pred": np.where(pred >= 0, uniq[np.maximum(pred, 0)], -1), "margin": fit["margin"], "gammas": gammas,
+           "labels": uniq, "counts": counts}
+    if true is not None:
+        out.update(_probe_scores(pred, true, G))
+    return out
+
+
+def mmd_witness(embeddings, groups, pair, top_k=8, gammas=None, scales=RBF_SCALES, transform=None):
+    """Which rows make two groups different: the MMD witness function between the two labels in `pair`, evaluated at every one of
+    their rows (witness_from_sums; one pass of ops.pairdist_rbf_row_group_sums).  The rows of the two labels are pooled as
+    mmd_permutation_test pools them (one gather, `transform` applied once, the bandwidths from the pooled rows unless `gammas` is
+    given).  Returns {'witness': float64 [L, n] in pooled order, positive where pair[0]'s rows are denser, 'rows': int64 [n], the
+    pooled rows' indices in the input, 'top': {'largest', 'smallest': int64 [L, top_k]}, per bandwidth the input indices of the
+    top_k rows with the largest and with the smallest witness (the most typical rows of pair[0] and of pair[1]; the lower index
+    first on a tie), 'mmd2': [L], the unbiased MMD^2 by the identity mean over pair[0]'s rows - mean over pair[1]'s rows,
+    'gammas'}."""
+    x, g_np = _rows_and_groups(embeddings, groups)
+    a, b = pair
+    if a == b:
+        raise ValueError(f"mmd_witness: pair = {pair!r} names one label twice")
+    idx = np.flatnonzero((g_np == a) | (g_np == b))
+    lab = (g_np[idx] == b).astype(np.int64)
+    if lab.sum() < 2 or (1 - lab).sum() < 2:
+        raise ValueError(f"mmd_witness: labels {a!r} and {b!r} need at least two rows each")
+    xp = ops.gather_rows(x.float().contiguous(), torch.from_numpy(idx).to(x.device))
+    if transform is not None:
+        xp = _transformed_rows(xp, transform, TRANSFORM_ROWS)
+    gammas = rbf_gammas(xp, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    counts = np.bincount(lab, minlength=2)
+    w = witness_from_sums(_sorted_row_sums(xp, lab, 2, gammas), lab, counts, 0, 1)
+    k = max(0, min(int(top_k), len(idx)))
+    top = {"largest": np.stack([idx[np.argsort(-wl, kind="stable")[:k]] for wl in w]),
+           "smallest": np.stack([idx[np.argsort(wl, kind="stable")[:k]] for wl in w])}
+    return {"witness": w, "rows": idx, "top": top, "mmd2": w[:, lab == 0].mean(1) - w[:, lab == 1].mean(1), "gammas": gammas}
+
+
+def kernel_alignment(embeddings, labels=None, gammas=None, scales=RBF_SCALES, transform=None):
+    """The normalised HSIC (centred kernel alignment, CKA) between the RBF kernel of a split's rows and the delta kernel of a
+    labelling, per bandwidth: `mmd`'s 'hsic' on a scale in [0, 1] that does not move with the bandwidth or the representation, so
+    that raw, adapter and erased rows can be put side by side.  `embeddings`, `labels` (at most 16), `transform` and the default
+    bandwidths as in `kernel_probe`.
+
+    Two passes: ops.pairdist_rbf_row_group_sums at gamma -- the bucket sums K are segment sums of R by the rows' label (ordered
+    pairs; the diagonal buckets are halved to unordered pairs), the row sums give B --, and one ops.pairdist_rbf_group_sums call at
+    2 gamma with a single label (only the total of k^2 is needed; that pass walks half the tiles).  Returns alignment_from_sums'
+    dict plus 'gammas', 'labels', 'counts'.  Because the second pass runs at 2 gamma the kernels' preconditions are halved:
+    2 gamma_max max d^2 <= 80 and 2 gamma_max (|a|^2 + |b|^2) <= 64 for centred rows a, b.  Read 'rel_bound' with 'alignment'."""
+    x, uniq, dense, counts = _labelled_rows("kernel_alignment", embeddings, labels, ops.PAIRDIST_ROWS_MAX_G)
+    G, N = len(uniq), x.shape[0]
+    x = x.float().contiguous()
+    if transform is not None:
+        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
+    gammas = rbf_gammas(x, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    R = _sorted_row_sums(x, dense, G, gammas)
+    S = np.stack([R[:, dense == a].sum(1) for a in range(G)], axis=1)            # [L, G, G]: ordered pairs, row in a, column in b
+    K = 0.5 * (S + S.transpose(0, 2, 1))
+    d = np.arange(G)
+    K[:, d, d] = 0.5 * S[:, d, d]
+    rows = 1.0 + R.sum(2)
+    center = torch.from_numpy((_column_sums(x) / N).astype(np.float32)).to(x.device)
+    K2 = ops.pairdist_rbf_group_sums(x, torch.zeros(N, dtype=torch.int64, device=x.device), 1, center, (2.0 * gammas).tolist()).cpu().numpy()
+    out = alignment_from_sums(K, K2[:, 0, 0], (rows * rows).sum(1), counts)
+    out.update(gammas=gammas, labels=uniq, counts=counts)
+    return out
+
+
+def probe_report(train_table, val_table, test_table, transform=None, scales=RBF_SCALES):
+    """How readable the groups, and within each class the spurious attribute, are NON-linearly in a representation: {'train': r,
+    'val': r, 'test': r} with r = {'group': the leave-one-out balanced accuracy [L] of `kernel_probe` over targets_group,
+    'spurious_within_class': {class: the leave-one-out balanced accuracy [L] of targets_spurious among that class's rows, nan if
+    only one place is present}, 'spurious_alignment': `kernel_alignment`'s [L] against targets_spurious (nan if only one place is
+    present)} and, for val and test, 'spurious_from_train': the balanced accuracy [L] of the split's rows as queries against train's
+    rows and targets_spurious.  Every call takes its bandwidths from its own (reference) rows.  `transform` is applied once per
+    split, as in dependence_report: run it raw, with an adapter, and on erased_table's rows."""
+    out, nan = {}, np.full(len(scales), np.nan)
+    train_x, train_c = None, None
+    for split, table in (("train", train_table), ("val", val_table), ("test", test_table)):
+        x = _device_rows(table, transform)
+        y, c = table.targets.cpu().numpy(), table.targets_spurious.cpu().numpy()
+        within = {}
+        for cls in np.unique(y):
+            idx = np.flatnonzero(y == cls)
+            if len(np.unique(c[idx])) < 2:
+                within[int(cls)] = nan.copy()
+                continue
+            within[int(cls)] = kernel_probe(ops.gather_rows(x, torch.from_numpy(idx).to(x.device)), c[idx], scales=scales)["balanced_accuracy"]
+        both = len(np.unique(c)) >= 2
+        out[split] = {"group": kernel_probe(x, table.targets_group.cpu().numpy(), scales=scales)["balanced_accuracy"],
+                      "spurious_within_class": within,
+                      "spurious_alignment": kernel_alignment(x, c, scales=scales)["alignment"] if both else nan.copy()}
+        if split == "train":
+            train_x, train_c = x, c
+        else:
+            ok = len(np.unique(train_c)) >= 2 and np.isin(c, train_c).all()
+            out[split]["spurious_from_train"] = (kernel_probe(train_x, train_c, scales=scales, query=x, query_labels=c)["balanced_accuracy"]
+                                                 if ok else nan.copy())
+    return out
+
+
 # ---- linear concept erasure: the rows changed so that no linear classifier reads a labelling (Belrose et al. 2023, "LEACE") ---------------
 # Post-hoc debiasing of frozen embeddings, in closed form from three moments: the column sums, the scatter matrix (ops.covariance) and
 # the per-label column sums (ops.label_column_sums), each one read of the rows.  The eraser is x -> x - sum_k ((x - mean) . A_k) B_k with

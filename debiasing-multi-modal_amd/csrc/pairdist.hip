@@ -101,24 +101,31 @@ struct PairDistP {
     const unsigned* amax_bits; double gamma[RBF_MAX_L]; int L;     // RbfMap only: the split's absmax (its scale exponent), the L bandwidths
 };
 
+struct PairRowsP;                                                  // the rows kernel's parameters, below: each map names its own
+struct PairRowsRbfP;
+
 // The element maps of the tile kernel: what a pair adds to its bucket, from its d^2 >= 0 in scaled units (2^-2s of the rows' own).
 // pre() is applied once to every accumulator element, in place; val(a, coef(p, l)) is summed, once per l < n_sums(p).
 struct DistanceMap {                                               // ||x_i - x_j||: one sum per bucket, in units of 2^-s
     static constexpr int MAX_L = 1;
     static constexpr bool SCALED = true;
-    static __device__ __forceinline__ int n_sums(const PairDistP&) { return 1; }
+    using RowsP = PairRowsP;
+    template <class Params> static __device__ __forceinline__ int n_sums(const Params&) { return 1; }
     static __device__ __forceinline__ float pre(float d2) { return __builtin_sqrtf(d2); }
-    static __device__ __forceinline__ float coef(const PairDistP&, int) { return 0.f; }
+    template <class Params> static __device__ __forceinline__ float coef(const Params&, int) { return 0.f; }
     static __device__ __forceinline__ float val(float a, float) { return a; }
     static __device__ __forceinline__ float per_group(float c) { return c; }
+    static __device__ __forceinline__ float self_pair() { return 0.f; }      // the rows kernel's (i, i): a distance of 0 adds nothing
+    static __device__ __forceinline__ float self_coef(float c) { return c; }
 };
 struct RbfMap {                                                    // exp(-gamma_l ||x_i - x_j||^2), l < L: d^2 stays in the registers, L sums per bucket
     static constexpr int MAX_L = RBF_MAX_L;
     static constexpr bool SCALED = false;
-    static __device__ __forceinline__ int n_sums(const PairDistP& p) { return p.L; }
+    using RowsP = PairRowsRbfP;
+    template <class Params> static __device__ __forceinline__ int n_sums(const Params& p) { return p.L; }
     static __device__ __forceinline__ float pre(float d2) { return d2; }
     // c_l = -gamma_l log2(e) 2^(-2s), formed in float64 (|s| <= 60: either factor alone may leave fp32's range) and rounded once
-    static __device__ __forceinline__ float coef(const PairDistP& p, int l) {
+    template <class Params> static __device__ __forceinline__ float coef(const Params& p, int l) {
         const double u = (double)pow2f(-scale_exp(__uint_as_float(*p.amax_bits)));
         return (float)(-p.gamma[l] * 1.4426950408889634 * u * u);
     }
@@ -127,6 +134,11 @@ struct RbfMap {                                                    // exp(-gamma
     // the predicated path's coefficient, opaque per row group: hoisted out of that loop the 128 float64 kernel values of a lane would
     // have to live across it, and the registers go to them instead of d^2
     static __device__ __forceinline__ float per_group(float c) { asm volatile("" : "+v"(c)); return c; }
+    // the rows kernel's (i, i): d^2 = +inf, whose kernel value exp2(-inf) is an exact 0 at every bandwidth -- for a coefficient that is not
+    // a zero (0 x inf is nan): self_coef keeps it at or below the largest negative normal number, which changes no kernel value
+    // (|c d^2| < 2^-96 there: exp2 gives 1 either way)
+    static __device__ __forceinline__ float self_pair() { return __builtin_inff(); }
+    static __device__ __forceinline__ float self_coef(float c) { return fminf(c, -1.17549435e-38f); }
 };
 
 template <class Map>
@@ -377,6 +389,13 @@ extern "C" int dbmm_pairdist_rbf_group_sums(const float* x, const int64_t* group
 // A column takes its label from `groups` directly (RowInfo's NO_GROUP = 15 is a label here): labels outside [0, G) and columns >= N are in
 // no sum.  The fast path is a tile off the diagonal whose 256 columns all carry one label; every other tile takes the predicated path, once
 // per label present among its columns.
+//
+// Element maps, as for the bucket kernel: DistanceMap (the sums above) and RbfMap, R[l][i][g] = sum over j != i with group[j] == g of
+// exp(-gamma_l ||x_i - x_j||^2) for L <= 4 bandwidths (dbmm_pairdist_rbf_row_group_sums: a Parzen-window probe, the MMD witness function, the
+// row sums of a centred kernel alignment).  d^2 stays in the accumulators, the diagonal's is set to +inf (exp2(-inf) is an exact 0), and the
+// reduction above runs once per l in a runtime loop: the partials are part [C][L][N][G], the owner thread's update runs once per (l, label
+// present).  The predicated path forms the exponentials again for every label (the ring leaves no registers to keep L x 128 values), with
+// the coefficient opaque per label so that they are not hoisted and d^2 is not spilled; neither instantiation uses scratch.
 namespace {
 
 constexpr int ROWS_MAX_G = 16;                                     // labels live in a byte; 16 = the k-means kernels' K
@@ -384,9 +403,12 @@ constexpr int ROWS_NO_GROUP = 255;                                 // columns pa
 constexpr int ROWS_MAX_CHUNKS = 16;
 
 struct PairRowsP {
-    const u16* P; const RowInfo* info; const int64_t* groups; double* part;      // part [C][N][G]
+    const u16* P; const RowInfo* info; const int64_t* groups; double* part;      // part [C][L][N][G]
     long long ldp, p_total;                                        // halves per row of P (2 Dp), bytes of P
     int N, T, nb, G, C, n_units;                                   // T = Dp / 64 K tiles per plane, nb = row blocks of 256, units = nb * C
+};
+struct PairRowsRbfP : PairRowsP {                                  // RbfMap's: the distance instantiation keeps its kernel arguments
+    const unsigned* amax_bits; double gamma[RBF_MAX_L]; int L;     // as in PairDistP
 };
 
 // v[16 ii + r] (ii = 0 / 1, r < 16) of the 32 lanes with the same fh -> the sums over those lanes, one per lane: afterwards lane fr holds in
@@ -404,7 +426,8 @@ __device__ __forceinline__ void fold_fr_lanes(float (&v)[32], int fr) {
     }
 }
 
-__global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const PairRowsP p) {
+template <class Map>
+__global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const typename Map::RowsP p) {
     __shared__ __attribute__((aligned(1024))) unsigned char lds[8 * PH_HALF];      // [buffer 2][Ah0, Bh0, Bh1, Ah1] = 128 KB
     __shared__ float e_norm[512];                                  // epilogue: norms of the tile's 256 rows, then of its 256 columns
     __shared__ unsigned char e_grp[256];                           // labels of the tile's columns
@@ -492,8 +515,8 @@ __global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const PairRo
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float rn = e_norm[wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh];
-                acc[i][0][r] = __builtin_sqrtf(fmaxf(fmaf(-2.f, acc[i][0][r], rn + cn0), 0.f));
-                acc[i][1][r] = __builtin_sqrtf(fmaxf(fmaf(-2.f, acc[i][1][r], rn + cn1), 0.f));
+                acc[i][0][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][0][r], rn + cn0), 0.f));
+                acc[i][1][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][1][r], rn + cn1), 0.f));
             }
         if (diag) {                                                   // the pair (i, i) is in no sum: by index, whatever its value
 #pragma unroll
@@ -501,8 +524,8 @@ __global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const PairRo
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int lr = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                    acc[i][0][r] = lr == c0 ? 0.f : acc[i][0][r];
-                    acc[i][1][r] = lr == c0 + 1 ? 0.f : acc[i][1][r];
+                    acc[i][0][r] = lr == c0 ? Map::self_pair() : acc[i][0][r];
+                    acc[i][1][r] = lr == c0 + 1 ? Map::self_pair() : acc[i][1][r];
                 }
         }
         const int gb0 = e_grp[c0], gb1 = e_grp[c0 + 1];
@@ -515,52 +538,68 @@ __global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const PairRo
             fold_fr_lanes(v, fr);
             e_rsum[par][wc][out_row + 64 * hh] = v[0];
         };
-        auto add_label = [&](int g) {                                 // the four column waves in wave order, onto the running sum
+        // sum l of chunk ech is matrix ech * L + l of part (a one-sum map: the chunk's own number, as before there was an l)
+        auto slot = [&](int l) {
+            if constexpr (Map::MAX_L == 1) return (size_t)ech; else return (size_t)ech * Map::n_sums(p) + l;
+        };
+        auto add_label = [&](int l, int g) {                          // the four column waves in wave order, onto the running sum
             __syncthreads();
             if (owner)
-                p.part[((size_t)ech * p.N + em0 + te) * p.G + g] += (double)e_rsum[par][0][te] + (double)e_rsum[par][1][te] + (double)e_rsum[par][2][te] + (double)e_rsum[par][3][te];
+                p.part[(slot(l) * p.N + em0 + te) * p.G + g] += (double)e_rsum[par][0][te] + (double)e_rsum[par][1][te] + (double)e_rsum[par][2][te] + (double)e_rsum[par][3][te];
             par ^= 1;                                                 // the next label's sums go to the other half: one barrier per label
         };
-        if (fast) {                                                   // one label, all 256 columns: no predicates
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                float v[32];
-#pragma unroll
-                for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) v[16 * ii + r] = acc[2 * hh + ii][0][r] + acc[2 * hh + ii][1][r];
-                fold_store(v, hh);
-            }
-            add_label(__builtin_ctz(mB));
-        } else {
-            for (unsigned mb = mB & 0xffffu; mb; mb &= mb - 1) {      // once per label present among the columns
-                const int g = __builtin_ctz(mb);
-                const bool in0 = gb0 == g, in1 = gb1 == g;
+        // one reduction per sum l, the same whatever L is (a runtime loop, never unrolled: L bandwidths in one call equal L calls bit for bit);
+        // the element values are formed from the accumulators on the way into the fold, so the tile is never held twice.  A do-while whose
+        // condition is a constant for a one-sum map: written so, and with slot() above, DistanceMap's instantiation compiles to the listing the
+        // kernel had before it was a template, instruction for instruction (a for loop, or this body in a lambda, did not: other registers)
+        int l = 0;
+#pragma unroll 1
+        do {
+            const float cf = Map::self_coef(Map::coef(p, l));
+            if (fast) {                                               // one label, all 256 columns: no predicates
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     float v[32];
 #pragma unroll
                     for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) v[16 * ii + r] = (in0 ? acc[2 * hh + ii][0][r] : 0.f) + (in1 ? acc[2 * hh + ii][1][r] : 0.f);
+                        for (int r = 0; r < 16; ++r) v[16 * ii + r] = Map::val(acc[2 * hh + ii][0][r], cf) + Map::val(acc[2 * hh + ii][1][r], cf);
                     fold_store(v, hh);
                 }
-                add_label(g);
+                add_label(l, __builtin_ctz(mB));
+            } else {
+                for (unsigned mb = mB & 0xffffu; mb; mb &= mb - 1) {  // once per label present among the columns
+                    const int g = __builtin_ctz(mb);
+                    const bool in0 = gb0 == g, in1 = gb1 == g;
+                    const float cg = Map::per_group(cf);              // (RbfMap: the kernel values are formed again per label, not kept across)
+#pragma unroll
+                    for (int hh = 0; hh < 2; ++hh) {
+                        float v[32];
+#pragma unroll
+                        for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r)
+                                v[16 * ii + r] = (in0 ? Map::val(acc[2 * hh + ii][0][r], cg) : 0.f) + (in1 ? Map::val(acc[2 * hh + ii][1][r], cg) : 0.f);
+                        fold_store(v, hh);
+                    }
+                    add_label(l, g);
+                }
             }
-        }
+        } while (Map::MAX_L > 1 && ++l < Map::n_sums(p));
         __syncthreads();
         if (tid == 0) e_mask = 0u;                                    // for the next tile: its atomics come after that tile's ring barriers
     }
 }
 
-// chunk partials -> R [N][G], in chunk order; distances were taken in units of 2^-s
+// chunk partials -> R [L][N][G] (n_out = L N G values), in chunk order; amax_bits: distances were taken in units of 2^-s and are rescaled, null
+// for kernel values, which have no unit
 __global__ __launch_bounds__(256) void pairdist_rows_fold_kernel(const double* __restrict__ part, int C, long long n_out, const unsigned* __restrict__ amax_bits,
                                                                  double* __restrict__ R) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_out) return;
     double s = 0.0;
     for (int c = 0; c < C; ++c) s += part[(size_t)c * n_out + i];
-    R[i] = ldexp(s, -scale_exp(__uint_as_float(*amax_bits)));
+    R[i] = ldexp(s, amax_bits ? -scale_exp(__uint_as_float(*amax_bits)) : 0);
 }
 
 // Column chunks per row block: 1 .. min(16, nb), the count whose schedule is shortest -- rounds of the persistent grid times the tiles of the
@@ -577,25 +616,18 @@ inline int rows_chunks(long long nb) {
     return C;
 }
 
-}  // namespace
-
-// see include/dbmm.h
-extern "C" size_t dbmm_workspace_bytes_pairdist_rows(int64_t N, int64_t D, int64_t G) {
-    if (N <= 0 || D <= 0 || G < 1 || G > ROWS_MAX_G) return 0;
+// the workspace of a rows pass with L sums per (row, label): head, RowInfo, planes, the chunks' partials -- sized for 16 chunks whatever
+// rows_chunks picks: the size then grows with N
+inline size_t rows_workspace_bytes(int64_t N, int64_t D, int64_t G, int64_t L) {
     const size_t Dp = (size_t)padded_dim(D);
-    // the partials are sized for 16 chunks whatever rows_chunks picks: the size then grows with N
     return HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256) + align_up((size_t)N * 2 * Dp * 2, 256) +
-           (size_t)ROWS_MAX_CHUNKS * (size_t)N * (size_t)G * sizeof(double);
+           (size_t)ROWS_MAX_CHUNKS * (size_t)L * (size_t)N * (size_t)G * sizeof(double);
 }
 
-// see include/dbmm.h
-extern "C" int dbmm_pairdist_row_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N, int64_t D,
-                                            int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > ROWS_MAX_G) return DBMM_E_SHAPE;
-    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
-    if (!x || !groups || !center || !sums || !workspace) return DBMM_E_ARG;
-    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
-    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rows(N, D, G)) return DBMM_E_WORKSPACE;
+// absmax, split, tiles, fold for one element map; the operands have been checked.  gammas: RbfMap's L bandwidths (host), else null and L = 1
+template <class Map>
+int row_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums, int64_t N, int64_t D, int64_t G,
+             void* workspace, void* stream) {
     const long long Dp = padded_dim(D);
     char* ws = (char*)workspace;
     unsigned* amax = (unsigned*)ws;
@@ -613,19 +645,62 @@ extern "C" int dbmm_pairdist_row_group_sums(const float* x, const int64_t* group
     hipLaunchKernelGGL(pairdist_split_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
                        (int)G);
     DBMM_CHECK_LAUNCH();
-    PairRowsP p{};
+    typename Map::RowsP p{};
     p.P = P; p.info = info; p.groups = groups; p.part = part;
     p.ldp = 2 * Dp; p.p_total = (long long)N * 2 * Dp * 2;
     p.N = (int)N; p.T = (int)(Dp / 64); p.nb = (int)((N + 255) / 256); p.G = (int)G;
     p.C = rows_chunks(p.nb);
     p.n_units = p.nb * p.C;
-    e = hipMemsetAsync(part, 0, (size_t)p.C * (size_t)N * (size_t)G * sizeof(double), s);    // the units' running sums start at zero
+    if constexpr (!Map::SCALED) {
+        p.amax_bits = amax; p.L = (int)L;
+        for (int l = 0; l < L; ++l) p.gamma[l] = gammas[l];
+    }
+    const long long n_out = L * N * G;
+    e = hipMemsetAsync(part, 0, (size_t)p.C * (size_t)n_out * sizeof(double), s);            // the units' running sums start at zero
     if (e != hipSuccess) return (int)e;
     const int grid = p.n_units < MAX_WG ? p.n_units : MAX_WG;
-    hipLaunchKernelGGL(pairdist_rows_tile_kernel, dim3(grid), dim3(512), 0, s, p);
+    hipLaunchKernelGGL(pairdist_rows_tile_kernel<Map>, dim3(grid), dim3(512), 0, s, p);
     DBMM_CHECK_LAUNCH();
-    const long long n_out = N * G;
-    hipLaunchKernelGGL(pairdist_rows_fold_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, part, p.C, n_out, amax, sums);
+    hipLaunchKernelGGL(pairdist_rows_fold_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, part, p.C, n_out,
+                       Map::SCALED ? amax : (const unsigned*)nullptr, sums);
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
+}
+
+}  // namespace
+
+// see include/dbmm.h
+extern "C" size_t dbmm_workspace_bytes_pairdist_rows(int64_t N, int64_t D, int64_t G) {
+    if (N <= 0 || D <= 0 || G < 1 || G > ROWS_MAX_G) return 0;
+    return rows_workspace_bytes(N, D, G, 1);
+}
+
+// see include/dbmm.h
+extern "C" int dbmm_pairdist_row_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N, int64_t D,
+                                            int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
+    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > ROWS_MAX_G) return DBMM_E_SHAPE;
+    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
+    if (!x || !groups || !center || !sums || !workspace) return DBMM_E_ARG;
+    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
+    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rows(N, D, G)) return DBMM_E_WORKSPACE;
+    return row_sums<DistanceMap>(x, groups, center, nullptr, 1, sums, N, D, G, workspace, stream);
+}
+
+// see include/dbmm.h
+extern "C" size_t dbmm_workspace_bytes_pairdist_rbf_rows(int64_t N, int64_t D, int64_t G, int64_t L) {
+    if (N <= 0 || D <= 0 || G < 1 || G > ROWS_MAX_G || L < 1 || L > RBF_MAX_L) return 0;
+    return rows_workspace_bytes(N, D, G, L);
+}
+
+// see include/dbmm.h
+extern "C" int dbmm_pairdist_rbf_row_group_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums,
+                                                int64_t N, int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
+    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > ROWS_MAX_G || L < 1 || L > RBF_MAX_L) return DBMM_E_SHAPE;
+    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
+    if (!x || !groups || !center || !gammas || !sums || !workspace) return DBMM_E_ARG;
+    for (int l = 0; l < L; ++l)
+        if (!(gammas[l] > 0.0) || !(gammas[l] <= 1.79769313486231570e308)) return DBMM_E_ARG;      // finite and positive
+    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
+    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rbf_rows(N, D, G, L)) return DBMM_E_WORKSPACE;
+    return row_sums<RbfMap>(x, groups, center, gammas, L, sums, N, D, G, workspace, stream);
 }

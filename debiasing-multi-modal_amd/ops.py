@@ -1649,6 +1649,29 @@ def pairdist_row_group_sums(x, groups, n_groups, center):
     return out
 
 
+def pairdist_rbf_row_group_sums(x, groups, n_groups, center, gammas):
+    """R float64 [L, N, G]: R[l, i, g] = sum over j != i with groups[j] == g of exp(-gammas[l] ||x[i] - x[j]||^2), on the fused Gram
+    kernel (dbmm_pairdist_rbf_row_group_sums): pairdist_row_group_sums' pass with pairdist_rbf_group_sums' element map, L bandwidths
+    from one Gram product, no N x N matrix, float64 sums in a fixed order -- the same bits on every call, and a bandwidth's sums do
+    not depend on the others in the call.  Operands as pairdist_row_group_sums (n_groups <= 16; a row with a label outside
+    [0, n_groups) is in nobody's sums and still gets its own: a query row); gammas: 1..4 finite numbers > 0 (host values).  The
+    diagonal is left out by index: R[l, i, groups[i]] of a label's only row and the column of an empty label are exactly 0."""
+    gam = _rbf_gammas("pairdist_rbf_row_group_sums", gammas)                        # host values: refused before any device is touched
+    N, D = _rows_operand("pairdist_rbf_row_group_sums", x)
+    _ids_operand("pairdist_rbf_row_group_sums", "groups", groups, x)
+    _f32_operand("pairdist_rbf_row_group_sums", "center", center, x, D)
+    if not 1 <= n_groups <= PAIRDIST_ROWS_MAX_G:
+        raise _lib.DbmmError(f"pairdist_rbf_row_group_sums: n_groups = {n_groups} outside 1..{PAIRDIST_ROWS_MAX_G}")
+    L = _lib.lib()
+    nbytes = L.dbmm_workspace_bytes_pairdist_rbf_rows(N, D, n_groups, len(gam))
+    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # planes and partials: sized by the call, not cached
+    out = _empty((len(gam), N, n_groups), device=x.device, dtype=torch.float64)
+    rc = L.dbmm_pairdist_rbf_row_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), ctypes.addressof(gam), len(gam), out.data_ptr(),
+                                            N, D, n_groups, ws.data_ptr(), ws.numel() * 4, stream())
+    _served(rc, "pairdist_rbf_row_group_sums", f"N = {N}, D = {D}")
+    return out
+
+
 def covariance(x, center):
     """S float64 [D, D]: S[a, b] = sum_i (x[i, a] - center[a]) (x[i, b] - center[b]), about the given center exactly, on the fused
     scatter kernel (dbmm_covariance): no centred copy of x, exact fp32 products, no fp32 chain longer than 1024 rows, float64 sums

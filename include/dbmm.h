@@ -878,6 +878,25 @@ size_t dbmm_workspace_bytes_pairdist_rows(int64_t N, int64_t D, int64_t G);
 int dbmm_pairdist_row_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N,
                                  int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Per-row, per-group sums of RBF kernel values for L bandwidths in one pass (what a Parzen-window probe, the MMD witness function and a
+ * normalised HSIC / CKA need of the Gram matrix), without N x N:
+ *   sums double [L][N][G]: sums[l][i][g] = sum over j != i with groups[j] == g of exp(-gammas[l] ||x[i] - x[j]||^2).
+ * dbmm_pairdist_row_group_sums' tile kernel with dbmm_pairdist_rbf_group_sums' element map: d^2 (clamped at 0) stays in the accumulator
+ * registers and every bandwidth takes it through the hardware exp2 and the rows kernel's reduction (the fp32 tree over a wave's 64
+ * columns, then float64 over the column waves, tiles and chunks in a fixed order; no floating-point atomics), one bandwidth after the
+ * other in a runtime loop: two calls give the same bits, and a bandwidth's sums do not depend on L or on its position.  The pair (i, i)
+ * is excluded by index (its d^2 is set to +inf: an exact 0 at every bandwidth), so a label's sum for the label's only row and the sums
+ * of an empty label are exactly 0.  A column j >= N or with a label outside [0, G) -- compared as 64-bit values -- is in no sum; a row
+ * with such a label still gets its L x G sums (query rows scored against the labelled ones).
+ * gammas: a HOST array of L finite doubles > 0, read at call time (else DBMM_E_ARG).  L outside 1..4, G outside 1..16, N outside
+ * 1..2^23: DBMM_E_SHAPE; D % 64 != 0 or D > 4096: DBMM_E_UNSUPPORTED; x, center and the workspace 16-byte aligned.  Four launches and
+ * two memsets on `stream`.  The workspace is dbmm_workspace_bytes_pairdist_rows' with L times the partials: 16 x L x N x G float64
+ * (0 for G outside 1..16 or L outside 1..4). */
+size_t dbmm_workspace_bytes_pairdist_rbf_rows(int64_t N, int64_t D, int64_t G, int64_t L);
+int dbmm_pairdist_rbf_row_group_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L,
+                                     double* sums, int64_t N, int64_t D, int64_t G, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+
 /* PCA of an embedding split: the scatter matrix without a centred copy of the rows (the deterministic map that stands in for the
  * UMAP / MDS projection of plot_umap, demo/visualizer.py:311-408; classical MDS of the distances dbmm_pairdist_group_sums reports):
  *   scatter double [D][D]: scatter[a][b] = sum_i (x[i][a] - center[a]) (x[i][b] - center[b]), about the GIVEN center exactly.
