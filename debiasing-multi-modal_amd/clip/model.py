@@ -120,6 +120,23 @@ def _fold_bn(conv_w, bn):
     return w, b
 
 
+def _mark_plan(plan):
+    """hand the tensors a freshly built plan owns to ops.mark_static: their device, contiguity, dtype and shape are settled once here, not
+    at each of the launches that read them.  Module parameters are left out (a parameter's `.data` can be replaced under the same object)."""
+    def walk(v):
+        if isinstance(v, torch.Tensor):
+            if not isinstance(v, nn.Parameter):
+                yield v
+        elif isinstance(v, dict):
+            for x in v.values():
+                yield from walk(x)
+        elif isinstance(v, (tuple, list)):
+            for x in v:
+                yield from walk(x)
+    ops.mark_static(*walk(plan))
+    return plan
+
+
 def _conv_bn(conv, bn):
     """operands of one conv + eval-mode BatchNorm (see _pack_conv)"""
     w, b = _fold_bn(conv.weight, bn)
@@ -268,7 +285,7 @@ class ModifiedResNet(nn.Module):
             wkv=torch.cat([ap.k_proj.weight, ap.v_proj.weight], 0).detach().float().contiguous(),
             bkv=torch.cat([ap.k_proj.bias, ap.v_proj.bias], 0).detach().float().contiguous(),
             wc=ap.c_proj.weight.detach().float().contiguous(), bc=ap.c_proj.bias.detach().float().contiguous())
-        self._plan = P
+        self._plan = _mark_plan(P)
         self._plan_key = self._param_key()
         return P
 
@@ -315,7 +332,7 @@ class ModifiedResNet(nn.Module):
         P["attn"] = dict(pos=f(ap.positional_embedding), wq=f(ap.q_proj.weight), bq=f(ap.q_proj.bias),
                          wkv=f(torch.cat([ap.k_proj.weight, ap.v_proj.weight], 0)), bkv=f(torch.cat([ap.k_proj.bias, ap.v_proj.bias], 0)),
                          wc=f(ap.c_proj.weight), bc=f(ap.c_proj.bias))
-        self._plan16 = (self._param_key(), P)
+        self._plan16 = (self._param_key(), _mark_plan(P))
         return P
 
     @torch.no_grad()
@@ -561,8 +578,8 @@ class Transformer(nn.Module):
             if _opt["conv_split"] == "bf16":
                 return dict(w_planes=ops.split_planes(w))
             return {}
-        self._planes = [tuple(one(w) for w in (b.attn.in_proj_weight, b.attn.out_proj.weight, b.mlp.c_fc.weight,
-                                                b.mlp.c_proj.weight)) for b in self.resblocks]
+        self._planes = _mark_plan([tuple(one(w) for w in (b.attn.in_proj_weight, b.attn.out_proj.weight, b.mlp.c_fc.weight,
+                                                           b.mlp.c_proj.weight)) for b in self.resblocks])
         self._planes_key = self._weight_key()
         return self._planes
 
@@ -581,7 +598,7 @@ class Transformer(nn.Module):
                                  w_out=h(b.attn.out_proj.weight), b_out=f(b.attn.out_proj.bias),
                                  w_fc=h(b.mlp.c_fc.weight), b_fc=f(b.mlp.c_fc.bias),
                                  w_proj=h(b.mlp.c_proj.weight), b_proj=f(b.mlp.c_proj.bias)))
-            self._f16 = (key, plan)
+            self._f16 = (key, _mark_plan(plan))
         return self._f16[1]
 
     @torch.no_grad()
@@ -659,9 +676,9 @@ class VisionTransformer(nn.Module):
             w1 = torch.zeros((W, Kp), device=x.device, dtype=torch.float16)
             w1[:, :K] = self.conv1.weight.detach().reshape(W, K).to(torch.float16)
             f = lambda t: t.detach().float().contiguous()
-            self._f16 = (key, dict(w1=w1, proj_t=self.proj.detach().t().to(torch.float16).contiguous(), cls=f(self.class_embedding),
-                                   pos=f(self.positional_embedding), ln_pre=(f(self.ln_pre.weight), f(self.ln_pre.bias)),
-                                   ln_post=(f(self.ln_post.weight), f(self.ln_post.bias))))
+            self._f16 = (key, _mark_plan(dict(w1=w1, proj_t=self.proj.detach().t().to(torch.float16).contiguous(), cls=f(self.class_embedding),
+                                              pos=f(self.positional_embedding), ln_pre=(f(self.ln_pre.weight), f(self.ln_pre.bias)),
+                                              ln_post=(f(self.ln_post.weight), f(self.ln_post.bias)))))
         e = self._f16[1]
         cols = ops.im2col_patch_f16(x, self.patch_size, Kp)                       # [B*g*g, Kp]
         patches = ops.gemm_f16(cols, e["w1"])                                      # conv1 has no bias
@@ -687,6 +704,7 @@ class VisionTransformer(nn.Module):
             if getattr(self, "_conv1_planes", (None,))[0] != key:
                 ph, we, _ = ops.split_planes_f16(w1.detach().contiguous(), allow_single=True)
                 self._conv1_planes = (key, ph, we)
+                ops.mark_static(ph)
             x_am = torch.zeros(1, device=x.device, dtype=torch.float32)   # max|x|, left there by the im2col kernel
             kw = dict(w_planes_f16=self._conv1_planes[1], w_exp=self._conv1_planes[2], a_absmax=x_am)
         cols = ops.im2col_patch(x, self.patch_size, out_absmax=x_am)      # [B*g*g, 3*P*P]

@@ -5,6 +5,7 @@ Every function requires HIP tensors -- there is no CPU path here.
 import ctypes
 import math
 import os
+import weakref
 from collections import namedtuple
 
 import numpy as np
@@ -148,17 +149,99 @@ def _f32c(t, name=None):
     return t
 
 
+# id(tensor) -> (weak reference, dtype, shape, element count) of the operands a compiled plan keeps for its lifetime (mark_static)
+_static = {}
+
+
+def mark_static(*tensors):
+    """A plan builder (clip/model.py) hands over the tensors its plan owns and never replaces -- planes, packed weights, BatchNorm scales,
+    biases, ratios, positional tables: device and contiguity are checked here, once, and their dtype and shape recorded, so that the
+    wrappers compare only those two per launch (about 60 launches per RN50 step read the same few hundred tensors).  Only tensors that
+    pass are recorded; anything else, and every tensor not handed over, gets the whole check at each launch.  An entry goes when its
+    tensor does.  Not for module parameters: `.data` of a parameter can be replaced under the same object."""
+    for t in tensors:
+        if t is None:
+            continue
+        try:
+            require_cuda(t)
+        except _lib.DbmmError:
+            continue
+        if t.is_contiguous():
+            key = id(t)
+            _static[key] = (weakref.ref(t, lambda _, key=key: _static.pop(key, None)), t.dtype, tuple(t.shape), t.numel())
+
+
+def _name(name):
+    """operand names are put together only when an error needs them: a string or a tuple of parts"""
+    return name if isinstance(name, str) else " ".join(name)
+
+
 def _operand(name, t, dtype, shape):
     """an operand the library only sees as a pointer: on the device, contiguous, of the dtype the kernel reads and of exactly the
     shape (a tuple) or element count (an int) it will index -- an int32 tensor read as int64, or a short one, is a stray read,
     not an error the library can see"""
+    m = _static.get(id(t))
+    if m is not None and m[1] == dtype and (m[3] if shape.__class__ is int else m[2]) == shape and m[0]() is t:
+        return t
+    if t is None:
+        raise _lib.DbmmError(f"{_name(name)}: the kernel reads this operand, got None")
     require_cuda(t)
     fits = t.numel() == shape if isinstance(shape, int) else tuple(t.shape) == tuple(shape)
     if t.dtype != dtype or not t.is_contiguous() or not fits:
         want = f"{shape} elements" if isinstance(shape, int) else f"shape {tuple(shape)}"
-        raise _lib.DbmmError(f"{name}: expected a contiguous {dtype} tensor of {want}, got {t.dtype} {tuple(t.shape)} "
+        raise _lib.DbmmError(f"{_name(name)}: expected a contiguous {dtype} tensor of {want}, got {t.dtype} {tuple(t.shape)} "
                              f"contiguous={t.is_contiguous()}")
     return t
+
+
+def _optional(name, t, dtype, shape):
+    """_operand for an argument the entry takes as NULL when it is None"""
+    return None if t is None else _operand(name, t, dtype, shape)
+
+
+def _absmax(name, t, required=False):
+    """a one-element float32 device scalar (the *_absmax arguments; one element is always contiguous); None is NULL unless the entry
+    needs the scalar"""
+    if t is None and required:
+        raise _lib.DbmmError(f"{_name(name)}: the kernel reads this scalar, got None")
+    if t is not None:
+        require_cuda(t)
+        if t.dtype != torch.float32 or t.numel() != 1:
+            raise _lib.DbmmError(f"{_name(name)}: expected one float32 element, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _spans(name, t, dtype, n):
+    """an operand addressed through a leading dimension: on the device, contiguous, of the dtype the kernel reads, and at least the
+    n elements the entry will index from its first one"""
+    require_cuda(t)
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < n:
+        raise _lib.DbmmError(f"{name}: expected a contiguous {dtype} tensor of at least {n} elements, got {t.dtype} {tuple(t.shape)} "
+                             f"contiguous={t.is_contiguous()}")
+    return t
+
+
+def _rank(name, t, nd):
+    """the shape of `t` is about to be read by index: it has nd dimensions"""
+    if t.dim() != nd:
+        raise _lib.DbmmError(f"{name}: a tensor of {nd} dimensions is expected, got shape {tuple(t.shape)}")
+    return t
+
+
+def _plane(name, c, N, K):
+    """the operands of a plan entry (clip/model.py _pack_conv) the chain kernels read: one exact fp16 plane [1][N][K] and the
+    BatchNorm scale / bias per output channel"""
+    _operand((name, "plane"), c["ph"], torch.float16, (1, N, K))
+    _operand((name, "scale"), c["sc"], torch.float32, N)
+    _operand((name, "bias"), c["b"], torch.float32, N)
+
+
+def _conv_f16(name, c, N, K):
+    """the (w f16 [N][K], scale f32 [N], bias f32 [N]) triple of an fp16-mode 1x1 conv"""
+    w, s, b = c
+    _operand((name, "weight"), w, torch.float16, (N, K))
+    _operand((name, "scale"), s, torch.float32, N)
+    _operand((name, "bias"), b, torch.float32, N)
 
 
 def _patch_image_check(name, x, P, Kp=None):
@@ -176,6 +259,8 @@ def split_planes(w):
     """fp32 [N][K] weight -> three bf16 planes [3][N][K] (hi, mid, lo) for the split-precision kernels"""
     require_cuda(w)
     _f32c(w)
+    if w.dim() < 2:
+        raise _lib.DbmmError(f"split planes of a weight [N][K] (or [Cout][Cin][kh][kw]), got shape {tuple(w.shape)}")
     N, K = w.shape[0], w.numel() // w.shape[0]
     planes = _empty((3, N, K), device=w.device, dtype=torch.bfloat16)
     check(_lib.lib().dbmm_split_weight_planes(ptr(w), ptr(planes), N, K, stream()), "split_weight_planes")
@@ -190,6 +275,8 @@ def split_planes_f16(w, allow_single=False):
     reference's build_model, which stores them in fp16 -- and K is a multiple of 32."""
     require_cuda(w)
     _f32c(w)
+    if w.dim() < 2:
+        raise _lib.DbmmError(f"split planes of a weight [N][K] (or [Cout][Cin][kh][kw]), got shape {tuple(w.shape)}")
     N, K = w.shape[0], w.numel() // w.shape[0]
     m = float(w.abs().max())
     w_exp = 0 if not (m > 0.0 and math.isfinite(m)) else max(-40, min(40, 13 - math.frexp(m)[1] + 1))
@@ -210,11 +297,11 @@ def gemm(a, w, bias=None, residual=None, act=ACT_NONE, alpha=1.0, trans_a=False,
     w_planes: bf16 triple; w_planes_f16 / w_exp + a_absmax: fp16-pair kernel (split_planes_f16);
     c_absmax (1-element device tensor, zeroed by the caller) receives max|c|."""
     require_cuda(a, w)
-    _f32c(w)
+    _f32c(_rank("gemm w", w, 2))
     if a.dtype != torch.float32:
         raise _lib.DbmmError("gemm needs float32")
+    _f32c(a, "gemm a")
     if lda is None:
-        _f32c(a)
         lda = a.shape[-1]
     if M is None:
         M = a.shape[-1] if trans_a else a.numel() // a.shape[-1]
@@ -224,15 +311,25 @@ def gemm(a, w, bias=None, residual=None, act=ACT_NONE, alpha=1.0, trans_a=False,
         N = w.shape[1] if trans_w else w.shape[0]
     if out is None:
         out = _empty((M, N), device=a.device, dtype=torch.float32)
+    else:
+        require_cuda(out)
+        _f32c(out, "gemm out")
     ldr = residual.shape[-1] if residual is not None else 0
-    # the library sees raw pointers and leading dimensions: what it will index must be there
-    if w.numel() != N * K or (not trans_a and a.numel() < (M - 1) * lda + K) or out.numel() < (M - 1) * out.shape[-1] + N:
+    # the library sees raw pointers and leading dimensions: what it will index must be there (a [K][lda] with trans_a, else [M][lda])
+    a_span = (K - 1) * lda + M if trans_a else (M - 1) * lda + K
+    if w.numel() != N * K or a.numel() < a_span or out.shape[-1] < N or out.numel() < (M - 1) * out.shape[-1] + N:
         raise RuntimeError(f"gemm: operands {tuple(a.shape)}, {tuple(w.shape)}, out {tuple(out.shape)} do not hold an M = {M}, N = {N}, K = {K} product")
-    _sized("gemm bias", bias, N)
-    if residual is not None and (ldr < N or residual.numel() < (M - 1) * ldr + N):
-        raise RuntimeError(f"gemm: residual {tuple(residual.shape)} for an [{M}, {N}] output")
-    if w_planes_f16 is not None and tuple(w_planes_f16.shape[1:]) != (N, K):
-        raise RuntimeError(f"gemm: weight planes {tuple(w_planes_f16.shape)} for a [{N}, {K}] weight")
+    _optional("gemm bias", bias, torch.float32, N)
+    if residual is not None:
+        if ldr < N:
+            raise RuntimeError(f"gemm: residual {tuple(residual.shape)} for an [{M}, {N}] output")
+        _spans("gemm residual", residual, torch.float32, (M - 1) * ldr + N)
+    if w_planes_f16 is not None:
+        if w_planes_f16.dim() != 3 or w_planes_f16.shape[0] not in (1, 2):
+            raise RuntimeError(f"gemm: weight planes {tuple(w_planes_f16.shape)} for a [{N}, {K}] weight")
+        _operand("gemm w_planes_f16", w_planes_f16, torch.float16, (w_planes_f16.shape[0], N, K))
+    _optional("gemm w_planes", w_planes, torch.bfloat16, (3, N, K))
+    _absmax("gemm a_absmax", a_absmax); _absmax("gemm c_absmax", c_absmax)
     ws = igemm_workspace(a.device)
     # algorithmic bytes: A and the residual read once, C written once, W once in the form the kernel reads it
     nby = 4 * (M * K + M * N * (2 if residual is not None else 1)) + \
@@ -299,11 +396,14 @@ def conv_bn_act(x, w, bias, residual, kh, kw, stride, pad, act, w_layout=WL_TAP_
         raise _lib.DbmmError("conv_bn_act: pool must be 1 or 2")
     if w.numel() != Cout * kh * kw * Cin:
         raise RuntimeError(f"conv_bn_act: packed weight {tuple(w.shape)} for a {kh} x {kw} conv over {Cin} channels")
-    _sized("conv_bn_act bias", bias, Cout); _sized("conv_bn_act out_scale", out_scale, Cout)
-    if residual is not None and tuple(residual.shape) != (B, Ho, Wo, Cout):
-        raise RuntimeError(f"conv_bn_act: residual {tuple(residual.shape)} for a {(B, Ho, Wo, Cout)} output")
-    if w_planes_f16 is not None and w_planes_f16.numel() != w_planes_f16.shape[0] * w.numel():
-        raise RuntimeError(f"conv_bn_act: weight planes {tuple(w_planes_f16.shape)} for a packed weight {tuple(w.shape)}")
+    _optional("conv_bn_act bias", bias, torch.float32, Cout); _optional("conv_bn_act out_scale", out_scale, torch.float32, Cout)
+    _optional("conv_bn_act residual", residual, torch.float32, (B, Ho, Wo, Cout))
+    if w_planes_f16 is not None:
+        if w_planes_f16.dim() < 2 or w_planes_f16.shape[0] not in (1, 2):
+            raise RuntimeError(f"conv_bn_act: weight planes {tuple(w_planes_f16.shape)} for a packed weight {tuple(w.shape)}")
+        _operand("conv_bn_act w_planes_f16", w_planes_f16, torch.float16, w_planes_f16.shape[0] * w.numel())
+    _optional("conv_bn_act w_planes", w_planes, torch.bfloat16, 3 * w.numel())
+    _absmax("conv_bn_act x_absmax", x_absmax); _absmax("conv_bn_act y_absmax", y_absmax)
     plain = kh == 1 and kw == 1 and stride == 1 and pad == 0
     split = w_planes_f16 is not None or y_absmax is not None or out_scale is not None
     # algorithmic bytes: input map and residual read once, output(s) written once, weights once
@@ -313,7 +413,7 @@ def conv_bn_act(x, w, bias, residual, kh, kw, stride, pad, act, w_layout=WL_TAP_
     nby = 4 * (x.numel() + (residual.numel() if residual is not None else 0) + oel) + wby
     # the 32-channel stem convs: persistent patch kernel (csrc/conv_patch.hip); option conv_patch = 0 disables
     if (Cin == 32 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and act == ACT_RELU and residual is None and not keep_full
-            and w_planes_f16 is not None and w_planes_f16.shape[0] == 1 and out_scale is not None and x_absmax is not None
+            and w_planes_f16 is not None and w_planes_f16.shape[0] == 1 and out_scale is not None and x_absmax is not None and bias is not None
             and Cout in (32, 64) and H % 4 == 0 and W % 28 == 0 and (pool == 1 or (H % 2 == 0 and W % 2 == 0))
             and w_layout in (WL_TAP_MAJOR, WL_CHUNK32_MAJOR) and get_option("conv_patch")):
         y = _empty((B, H // pool, W // pool, Cout), device=x.device, dtype=torch.float32)
@@ -379,9 +479,13 @@ def gemm_dual(a, a_absmax, w_plane, w_exp, out_scale, a2, a2_absmax, w2_plane, r
     require_cuda(a, a2)
     _f32c(a); _f32c(a2)
     K, K2 = a.shape[-1], a2.shape[-1]
-    M, N = a.numel() // K, w_plane.shape[1]
+    M, N = a.numel() // K, _rank("gemm_dual w_plane", w_plane, 3).shape[1]
     if a2.numel() // K2 != M:
         raise _lib.DbmmError("gemm_dual: operand row counts differ")
+    _operand("gemm_dual w_plane", w_plane, torch.float16, (1, N, K)); _operand("gemm_dual w2_plane", w2_plane, torch.float16, (1, N, K2))
+    _operand("gemm_dual out_scale", out_scale, torch.float32, N); _operand("gemm_dual ratio", ratio, torch.float32, N)
+    _operand("gemm_dual bias", bias, torch.float32, N)
+    _absmax("gemm_dual a_absmax", a_absmax, True); _absmax("gemm_dual a2_absmax", a2_absmax, True); _absmax("gemm_dual c_absmax", c_absmax)
     c = _empty(tuple(a.shape[:-1]) + (N,), device=a.device, dtype=torch.float32)
     ws = igemm_workspace(a.device)
     t = _Timed(M, N, K + K2, 0, 0, 4 * (M * K + M * K2 + M * N) + 2 * (N * K + N * K2))
@@ -404,7 +508,7 @@ def bottleneck_chain(y2, y2_absmax, c3, residual, c1, x_absmax=None, y1_absmax=N
     require_cuda(y2, residual)
     _f32c(y2); _f32c(residual)
     B, H, W, K = y2.shape
-    N, P = c3["ph"].shape[1], c1["ph"].shape[1]
+    N, P = _rank("bottleneck_chain c3 plane", c3["ph"], 3).shape[1], _rank("bottleneck_chain c1 plane", c1["ph"], 3).shape[1]
     if c3["ph"].shape[0] != 1 or c1["ph"].shape[0] != 1 or tuple(residual.shape) != (B, H, W, N):
         return None
     chain8 = K == 256 and P == 256 and not pooled and get_option("chain8")       # the layer-3 geometry: eight-wave kernel
@@ -412,6 +516,9 @@ def bottleneck_chain(y2, y2_absmax, c3, residual, c1, x_absmax=None, y1_absmax=N
         return None
     if N % 64 or (pooled and (H % 2 or W % 2)):
         return None
+    _plane("bottleneck_chain c3", c3, N, K); _plane("bottleneck_chain c1", c1, P, N)
+    _absmax("bottleneck_chain y2_absmax", y2_absmax, True); _absmax("bottleneck_chain x_absmax", x_absmax)
+    _absmax("bottleneck_chain y1_absmax", y1_absmax)
     dev = y2.device
     full = keep_full or not pooled
     x = _empty((B, H, W, N), device=dev, dtype=torch.float32) if full else None
@@ -444,7 +551,7 @@ def bottleneck_block_chain(y1, y1_absmax, c2, c3, c1, residual=None, dual=None, 
     require_cuda(y1)
     _f32c(y1)
     B, H, W, K = y1.shape
-    N, P = c3["ph"].shape[1], c1["ph"].shape[1]
+    N, P = _rank("bottleneck_block_chain c3 plane", c3["ph"], 3).shape[1], _rank("bottleneck_block_chain c1 plane", c1["ph"], 3).shape[1]
     M = B * H * W
     if (c2["ph"] is None or c2["ph"].shape[0] != 1 or c2["wl"] != WL_CHUNK32_MAJOR or tuple(c2["ph"].shape[1:]) != (K, 9 * K)
             or c3["ph"].shape[0] != 1 or c1["ph"].shape[0] != 1 or N % 64 or M % 4):
@@ -454,6 +561,20 @@ def bottleneck_block_chain(y1, y1_absmax, c2, c3, c1, residual=None, dual=None, 
             return None
     elif (K, P) != (64, 64) or dual["ds"]["ph"].shape[0] != 1 or tuple(dual["a2"].shape) != (B, H, W, 64):
         return None
+    _plane("bottleneck_block_chain c2", c2, K, 9 * K); _plane("bottleneck_block_chain c1", c1, P, N)
+    _absmax("bottleneck_block_chain y1_absmax", y1_absmax, True); _absmax("bottleneck_block_chain x_absmax", x_absmax)
+    _absmax("bottleneck_block_chain y1n_absmax", y1n_absmax)
+    if dual is None:
+        _plane("bottleneck_block_chain c3", c3, N, K)
+        _operand("bottleneck_block_chain residual", residual, torch.float32, (B, H, W, N))
+    else:
+        _operand("bottleneck_block_chain c3 plane", c3["ph"], torch.float16, (1, N, K))
+        _operand("bottleneck_block_chain c3 scale", c3["sc"], torch.float32, N)
+        _operand("bottleneck_block_chain dual a2", dual["a2"], torch.float32, (B, H, W, 64))
+        _absmax("bottleneck_block_chain dual a2_absmax", dual["a2_absmax"], True)
+        _operand("bottleneck_block_chain dual ds plane", dual["ds"]["ph"], torch.float16, (1, N, 64))
+        _operand("bottleneck_block_chain dual ratio", dual["ratio"], torch.float32, N)
+        _operand("bottleneck_block_chain dual bias", dual["bias"], torch.float32, N)
     x = _empty((B, H, W, N), device=y1.device, dtype=torch.float32)
     y1n = _empty((B, H, W, P), device=y1.device, dtype=torch.float32)
     global _chain_tag
@@ -482,11 +603,18 @@ def bottleneck_chain_dual(y2, y2_absmax, c3, a2, a2_absmax, ds, ratio, bias, c1,
     require_cuda(y2, a2)
     _f32c(y2); _f32c(a2)
     K, K2 = y2.shape[-1], a2.shape[-1]
-    N, P = c3["ph"].shape[1], c1["ph"].shape[1]
+    N, P = _rank("bottleneck_chain_dual c3 plane", c3["ph"], 3).shape[1], _rank("bottleneck_chain_dual c1 plane", c1["ph"], 3).shape[1]
     M = y2.numel() // K
     if (c3["ph"].shape[0] != 1 or ds["ph"].shape[0] != 1 or c1["ph"].shape[0] != 1 or a2.numel() // K2 != M
             or K != 64 or K2 != 64 or N % 64 or P not in (64, 128) or M % 4):
         return None
+    _operand("bottleneck_chain_dual c3 plane", c3["ph"], torch.float16, (1, N, K))
+    _operand("bottleneck_chain_dual c3 scale", c3["sc"], torch.float32, N)
+    _operand("bottleneck_chain_dual ds plane", ds["ph"], torch.float16, (1, N, K2))
+    _operand("bottleneck_chain_dual ratio", ratio, torch.float32, N); _operand("bottleneck_chain_dual bias", bias, torch.float32, N)
+    _plane("bottleneck_chain_dual c1", c1, P, N)
+    _absmax("bottleneck_chain_dual y2_absmax", y2_absmax, True); _absmax("bottleneck_chain_dual a2_absmax", a2_absmax, True)
+    _absmax("bottleneck_chain_dual x_absmax", x_absmax); _absmax("bottleneck_chain_dual y1_absmax", y1_absmax)
     x = _empty(tuple(y2.shape[:-1]) + (N,), device=y2.device, dtype=torch.float32)
     y1 = _empty(tuple(y2.shape[:-1]) + (P,), device=y2.device, dtype=torch.float32)
     global _chain_tag
@@ -511,6 +639,8 @@ def conv_stem_s2(x_nchw, w, bias, y_absmax=None):
     if C != 3:
         raise _lib.DbmmError("stem conv expects 3 input channels")
     Cout = w.shape[-1]
+    _operand("conv_stem_s2 weight", w, torch.float32, (3, 3, 3, Cout)); _operand("conv_stem_s2 bias", bias, torch.float32, Cout)
+    _absmax("conv_stem_s2 y_absmax", y_absmax)
     y = _empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cout), device=x_nchw.device, dtype=torch.float32)
     check(_lib.lib().dbmm_conv_stem_s2(ptr(x_nchw), ptr(w), ptr(bias), ptr(y), ptr(y_absmax), B, H, W, Cout, stream()),
           "conv_stem_s2")
@@ -535,7 +665,7 @@ def attnpool(x, pos, wq, bq, wkv, bkv, wc, bc, heads):
         raise _lib.DbmmError("attnpool: expected a contiguous tensor")
     B, H, W, C = x.shape
     HW = H * W
-    Dout = wc.shape[0]
+    Dout = _rank("attnpool wc", wc, 2).shape[0]
     # the library sees raw pointers: the operand shapes are checked here.  A feature map of another resolution than the positional table
     # was built for fails like the reference's `x + self.positional_embedding[:, None, :]` (clip/model.py:72), not as a stray read
     if tuple(pos.shape) != (HW + 1, C):
@@ -556,15 +686,16 @@ def attnpool(x, pos, wq, bq, wkv, bkv, wc, bc, heads):
 
 
 def layernorm(x, gamma, beta, rows=None, ldx=None, eps=1e-5, y_absmax=None):
-    require_cuda(x)
     E = gamma.numel()
     if rows is None:
         rows = x.numel() // E
     if ldx is None:
         ldx = E
-    _sized("layernorm beta", beta, E)
-    if ldx < E or x.numel() < (rows - 1) * ldx + E:
+    _operand("layernorm gamma", gamma, torch.float32, E); _operand("layernorm beta", beta, torch.float32, E)
+    if ldx < E:
         raise RuntimeError(f"layernorm: input {tuple(x.shape)} for {rows} rows of {E} at pitch {ldx}")
+    _spans("layernorm input", x, torch.float32, (rows - 1) * ldx + E)
+    _absmax("layernorm y_absmax", y_absmax)
     y = _empty((rows, E), device=x.device, dtype=torch.float32)
     check(_lib.lib().dbmm_layernorm(ptr(x), ldx, ptr(gamma), ptr(beta), ptr(y), E, rows, E, eps, ptr(y_absmax), stream()),
           "layernorm")
@@ -576,6 +707,7 @@ def mha_core(qkv, B, L, E, heads, causal, qkv_absmax=None):
     fp16-pair kernel runs (16-bit matrix cores, three partial products, fp32 accuracy); without it, or with
     option mha_x2 = 0, the fp32-input-MFMA kernel."""
     require_cuda(qkv)
+    _f32c(qkv, "mha_core qkv"); _absmax("mha_core qkv_absmax", qkv_absmax)
     if qkv.numel() != B * L * 3 * E or E != heads * 64:
         raise RuntimeError(f"mha_core: qkv {tuple(qkv.shape)} for B = {B}, L = {L}, E = {E}, {heads} heads of 64")
     out = _empty((B * L, E), device=qkv.device, dtype=torch.float32)
@@ -654,7 +786,7 @@ def _gather_eot_check(name, tokens_i32, x, dtype):
     if x.dim() != 3 or x.dtype != dtype or not x.is_contiguous():
         raise _lib.DbmmError(f"{name} x: expected a contiguous {dtype} tensor [n, L, W], got {x.dtype} {tuple(x.shape)} "
                              f"contiguous={x.is_contiguous()}")
-    _operand(f"{name} tokens", tokens_i32, torch.int32, x.shape[:2])
+    _operand((name, "tokens"), tokens_i32, torch.int32, x.shape[:2])
 
 
 def gather_eot(tokens_i32, x):
@@ -679,8 +811,9 @@ def l2norm_rows(x):
     """x / x.norm(dim=1, keepdim=True) for fp32 [B, D] (CLIP.forward, clip/model.py:362-363)"""
     require_cuda(x)
     _f32c(x)
-    y = _empty(tuple(x.shape), device=x.device, dtype=torch.float32)
-    check(_lib.lib().dbmm_l2norm_rows(ptr(x), ptr(y), x.shape[0], x.shape[1], stream()), "l2norm_rows")
+    B, D = x.shape
+    y = _empty((B, D), device=x.device, dtype=torch.float32)
+    check(_lib.lib().dbmm_l2norm_rows(ptr(x), ptr(y), B, D, stream()), "l2norm_rows")
     return y
 
 
@@ -688,8 +821,9 @@ def colsum(x):
     """x.sum(0) of fp32 [B, N] (N % 4 == 0) in a fixed order"""
     require_cuda(x)
     _f32c(x)
-    out = _empty((x.shape[1],), device=x.device, dtype=torch.float32)
-    check(_lib.lib().dbmm_colsum(ptr(x), ptr(out), x.shape[0], x.shape[1], stream()), "colsum")
+    B, N = x.shape
+    out = _empty((N,), device=x.device, dtype=torch.float32)
+    check(_lib.lib().dbmm_colsum(ptr(x), ptr(out), B, N, stream()), "colsum")
     return out
 
 
@@ -1899,14 +2033,14 @@ def gemm_f16(a, w, bias=None, residual=None, act=ACT_NONE, M=None, lda=None):
     if a.dtype != torch.float16:
         raise _lib.DbmmError("gemm_f16 needs float16 activations")
     N, K = w.shape
+    _f16c(a)
     if lda is None:
-        _f16c(a)
         lda = a.shape[-1]
     if M is None:
         M = a.numel() // a.shape[-1]
     if a.numel() < (M - 1) * lda + K or lda < K:
         raise RuntimeError(f"gemm_f16: activations {tuple(a.shape)} (row pitch {lda}) for M = {M}, K = {K}")
-    _sized("gemm_f16 bias", bias, N); _sized("gemm_f16 residual", residual, M * N)
+    _optional("gemm_f16 bias", bias, torch.float32, N); _optional("gemm_f16 residual", residual, torch.float16, M * N)
     c = _empty((M, N), device=a.device, dtype=torch.float16)
     deep = N % 256 == 0 and K % 128 == 0 and M >= 16384 and get_option("f16_8ph")   # dbmm_gemm_f16's own rule
     with _TimedTag(f"gemm_f16_8ph_kernel<{act}, {int(residual is not None)}>" if deep else _gemm_f16_tag(M, N), 2.0 * M * N * K,
@@ -1929,15 +2063,15 @@ def mha_core_f16(qkv, B, L, E, heads, causal):
 
 
 def layernorm_f16(x, gamma, beta, rows=None, ldx=None, eps=1e-5):
-    require_cuda(x)
     E = gamma.numel()
     if rows is None:
         rows = x.numel() // E
     if ldx is None:
         ldx = E
-    _sized("layernorm_f16 beta", beta, E)
-    if ldx < E or x.numel() < (rows - 1) * ldx + E:
+    _operand("layernorm_f16 gamma", gamma, torch.float32, E); _operand("layernorm_f16 beta", beta, torch.float32, E)
+    if ldx < E:
         raise RuntimeError(f"layernorm_f16: input {tuple(x.shape)} for {rows} rows of {E} at pitch {ldx}")
+    _spans("layernorm_f16 input", x, torch.float16, (rows - 1) * ldx + E)
     y = _empty((rows, E), device=x.device, dtype=torch.float16)
     check(_lib.lib().dbmm_layernorm_f16(ptr(x), ldx, ptr(gamma), ptr(beta), ptr(y), E, rows, E, eps, stream()), "layernorm_f16")
     return y
@@ -1996,7 +2130,8 @@ def conv1x1_f16(x, w, scale, bias, residual=None, act=ACT_RELU):
     if x.shape[-1] != Cin:
         raise RuntimeError(f"conv1x1_f16: {x.shape[-1]} input channels against a weight {tuple(w.shape)}")
     M = x.numel() // Cin
-    _sized("conv1x1_f16 scale", scale, Cout); _sized("conv1x1_f16 bias", bias, Cout); _sized("conv1x1_f16 residual", residual, M * Cout)
+    _operand("conv1x1_f16 scale", scale, torch.float32, Cout); _operand("conv1x1_f16 bias", bias, torch.float32, Cout)
+    _optional("conv1x1_f16 residual", residual, torch.float16, M * Cout)
     y = _empty(tuple(x.shape[:-1]) + (Cout,), device=x.device, dtype=torch.float16)
     deep = Cout % 256 == 0 and Cin % 128 == 0 and M >= 16384                            # what dbmm_gemm_f16 gives the eight-phase kernel
     mode = get_option("conv1x1_stream")
@@ -2027,11 +2162,15 @@ def conv1x1_res_pool_f16(x, c3, residual):
     require_cuda(x, residual)
     _f16c(x); _f16c(residual)
     w, scale, bias = c3
-    Cout, Cin = w.shape
+    Cout, Cin = _rank("conv1x1_res_pool_f16 weight", w, 2).shape
     if x.dim() != 4 or x.shape[1] % 2 or x.shape[2] % 2:
         return None
     B, H, W = x.shape[:3]
     M = B * H * W
+    if x.shape[3] != Cin:
+        raise RuntimeError(f"conv1x1_res_pool_f16: {x.shape[3]} input channels against a weight {tuple(w.shape)}")
+    _conv_f16("conv1x1_res_pool_f16 c3", c3, Cout, Cin)
+    _operand("conv1x1_res_pool_f16 residual", residual, torch.float16, M * Cout)
     y = _empty((B, H, W, Cout), device=x.device, dtype=torch.float16)
     yp = _empty((B, H // 2, W // 2, Cout), device=x.device, dtype=torch.float16)
     t = _TimedTag(f"conv1x1_res_stream_f16_kernel<{Cin}, 1>", 2.0 * M * Cout * Cin, 2 * (M * Cin + Cout * Cin + 2 * M * Cout + M // 4 * Cout))
@@ -2051,12 +2190,16 @@ def chain_f16(y2, c3, residual, c1, pooled=False, keep_full=True):
     require_cuda(y2, residual)
     _f16c(y2); _f16c(residual)
     (w3, s3, b3), (w1, s1, b1) = c3, c1
-    N, K = w3.shape
-    P = w1.shape[0]
+    N, K = _rank("chain_f16 c3 weight", w3, 2).shape
+    P = _rank("chain_f16 c1 weight", w1, 2).shape[0]
     M = y2.numel() // K
     full = keep_full or not pooled
     if pooled and (y2.dim() != 4 or y2.shape[1] % 2 or y2.shape[2] % 2):
         return None
+    if y2.shape[-1] != K:
+        raise RuntimeError(f"chain_f16: {y2.shape[-1]} input channels against a conv3 weight {tuple(w3.shape)}")
+    _conv_f16("chain_f16 c3", c3, N, K); _conv_f16("chain_f16 c1", c1, P, N)
+    _operand("chain_f16 residual", residual, torch.float16, M * N)
     x = _empty(tuple(y2.shape[:-1]) + (N,), device=y2.device, dtype=torch.float16) if full else None
     y1 = _empty(tuple(y2.shape[:-1]) + (P,), device=y2.device, dtype=torch.float16)
     xp = _empty((y2.shape[0], y2.shape[1] // 2, y2.shape[2] // 2, N), device=y2.device, dtype=torch.float16) if pooled else None
@@ -2077,16 +2220,28 @@ def chain_f16(y2, c3, residual, c1, pooled=False, keep_full=True):
     return (x, xp, y1) if pooled else (x, y1)
 
 
+def _dual_f16(name, y2, w3, scale3, xp, wd, ratio, bias, M, N, K, K2):
+    """the operands of the fp16 dual-source 1x1 conv: y2 [M][K] and xp [M][K2] against w3 [N][K] and wd [N][K2], three [N] vectors"""
+    if y2.shape[-1] != K or xp.shape[-1] != K2 or xp.numel() != M * K2:
+        raise RuntimeError(f"{name}: inputs {tuple(y2.shape)}, {tuple(xp.shape)} against weights {tuple(w3.shape)}, {tuple(wd.shape)}")
+    require_cuda(w3)
+    _operand((name, "wd"), wd, torch.float16, (N, K2))
+    _operand((name, "scale3"), scale3, torch.float32, N); _operand((name, "ratio"), ratio, torch.float32, N)
+    _operand((name, "bias"), bias, torch.float32, N)
+
+
 def chain_dual_f16(y2, w3, scale3, xp, wd, ratio, bias, c1):
     """fp16 mode: the first block of a stage -- x' = relu(conv3(y2) * scale3 + conv_d(xp) * scale_d + bias) (conv1x1_dual_f16's arguments) and
     y1' = relu(conv1'(x') * s1 + b1) in one launch (dbmm_bottleneck_chain_dual_f16).  Returns (x', y1') or None."""
     require_cuda(y2, xp)
     _f16c(y2); _f16c(xp); _f16c(w3); _f16c(wd)
     w1, s1, b1 = c1
-    N, K = w3.shape
-    K2 = wd.shape[1]
-    P = w1.shape[0]
+    N, K = _rank("chain_dual_f16 w3", w3, 2).shape
+    K2 = _rank("chain_dual_f16 wd", wd, 2).shape[1]
+    P = _rank("chain_dual_f16 c1 weight", w1, 2).shape[0]
     M = y2.numel() // K
+    _dual_f16("chain_dual_f16", y2, w3, scale3, xp, wd, ratio, bias, M, N, K, K2)
+    _conv_f16("chain_dual_f16 c1", c1, P, N)
     x = _empty(tuple(y2.shape[:-1]) + (N,), device=y2.device, dtype=torch.float16)
     y1 = _empty(tuple(y2.shape[:-1]) + (P,), device=y2.device, dtype=torch.float16)
     t = _TimedTag(f"chain_f16_kernel<{K}, {P}, 1>", 2.0 * M * N * (K + K2 + P), 2 * (M * (K + K2 + N + P) + N * (K + K2 + P)))
@@ -2105,9 +2260,10 @@ def conv1x1_dual_f16(y2, w3, scale3, xp, wd, ratio, bias, act=ACT_RELU):
     ratio = scale_d / scale3, bias = both BatchNorm biases.  None when the library has no kernel for the shape."""
     require_cuda(y2, xp)
     _f16c(y2); _f16c(xp); _f16c(w3); _f16c(wd)
-    Cout, K = w3.shape
-    K2 = wd.shape[1]
+    Cout, K = _rank("conv1x1_dual_f16 w3", w3, 2).shape
+    K2 = _rank("conv1x1_dual_f16 wd", wd, 2).shape[1]
     M = y2.numel() // K
+    _dual_f16("conv1x1_dual_f16", y2, w3, scale3, xp, wd, ratio, bias, M, Cout, K, K2)
     out = _empty(tuple(y2.shape[:-1]) + (Cout,), device=y2.device, dtype=torch.float16)
     t = _TimedTag("gemm_f16_8ph_kernel<dual>", 2.0 * M * Cout * (K + K2), 2 * (M * (K + K2) + Cout * (K + K2) + M * Cout))
     t.__enter__()
@@ -2129,7 +2285,7 @@ def conv3x3_f16(x, w, scale, bias, pool=1):
     Cout = w.shape[0]
     if w.numel() != Cout * 9 * Cin:
         raise RuntimeError(f"conv3x3_f16: packed weight {tuple(w.shape)} for a 3 x 3 conv over {Cin} channels")
-    _sized("conv3x3_f16 scale", scale, Cout); _sized("conv3x3_f16 bias", bias, Cout)
+    _operand("conv3x3_f16 scale", scale, torch.float32, Cout); _operand("conv3x3_f16 bias", bias, torch.float32, Cout)
     y = _empty((B, H // pool, W // pool, Cout), device=x.device, dtype=torch.float16)
     geo = "2, 2, 2" if Cout > 64 else ("4, 1, 2" if Cout > 32 else "4, 1, 1")
     deep = Cout % 256 == 0 and B * H * W >= 16384 and get_option("f16_conv_8ph")     # dbmm_conv3x3_bn_relu_f16's own routing rule
@@ -2157,6 +2313,8 @@ def conv_stem_s2_f16(x_nchw, w, bias, scale=None):
     if C != 3:
         raise _lib.DbmmError("stem conv expects 3 input channels")
     Cout = w.shape[-1]
+    _operand("conv_stem_s2_f16 weight", w, torch.float32, (3, 3, 3, Cout)); _operand("conv_stem_s2_f16 bias", bias, torch.float32, Cout)
+    _optional("conv_stem_s2_f16 scale", scale, torch.float32, Cout)
     y = _empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cout), device=x_nchw.device, dtype=torch.float16)
     mfma = scale is not None and get_option("stem_mfma")
     with _TimedTag("stem_s2_f16_mfma_kernel" if mfma else "stem_s2_f16_kernel", 2.0 * y.numel() * 27,

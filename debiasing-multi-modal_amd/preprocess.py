@@ -101,6 +101,18 @@ def plan(H, W, n_px, device):
 
 _F3 = _lib.ctypes.c_float * 3
 
+# every output / workspace of this module comes from here, like ops._empty (tests swap in an allocator that records each tensor)
+_empty = torch.empty
+
+
+def _out_operand(name, out, shape):
+    """a caller-supplied output: the library sees the pointer only and writes float32 `shape` there"""
+    require_cuda(out)
+    if out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise _lib.DbmmError(f"{name}: `out` must be a contiguous float32 tensor of shape {tuple(shape)}, got {out.dtype} {tuple(out.shape)} "
+                             f"contiguous={out.is_contiguous()}")
+    return out
+
 
 def preprocess_u8(img_hwc, n_px, out=None, return_u8=False):
     """img_hwc: uint8 [H, W, 3] RGB tensor on the GPU -> float32 [3, n_px, n_px] (what the
@@ -111,9 +123,11 @@ def preprocess_u8(img_hwc, n_px, out=None, return_u8=False):
     H, W = int(img_hwc.shape[0]), int(img_hwc.shape[1])
     p = plan(H, W, n_px, img_hwc.device)
     if out is None:
-        out = torch.empty((3, n_px, n_px), device=img_hwc.device, dtype=torch.float32)
-    u8 = torch.empty((n_px, n_px, 3), device=img_hwc.device, dtype=torch.uint8) if return_u8 else None
-    ws = torch.empty(p["nrows"] * n_px * 3, device=img_hwc.device, dtype=torch.uint8)
+        out = _empty((3, n_px, n_px), device=img_hwc.device, dtype=torch.float32)
+    else:
+        _out_operand("preprocess_u8", out, (3, n_px, n_px))
+    u8 = _empty((n_px, n_px, 3), device=img_hwc.device, dtype=torch.uint8) if return_u8 else None
+    ws = _empty(p["nrows"] * n_px * 3, device=img_hwc.device, dtype=torch.uint8)
     check(_lib.lib().dbmm_resize_crop_normalize_u8(
         ptr(img_hwc), H, W, ptr(p["hb"]), ptr(p["hk"]), p["hk"].shape[1], ptr(p["vb"]), ptr(p["vk"]), p["vk"].shape[1],
         p["row0"], p["nrows"], n_px, _F3(*CLIP_MEAN), _F3(*CLIP_STD), ptr(out), ptr(u8), ptr(ws), ws.numel(), stream()),
@@ -130,8 +144,10 @@ def preprocess_uniform(images_bhwc, n_px, out=None):
     B, H, W = (int(v) for v in images_bhwc.shape[:3])
     p = plan(H, W, n_px, images_bhwc.device)
     if out is None:
-        out = torch.empty((B, 3, n_px, n_px), device=images_bhwc.device, dtype=torch.float32)
-    ws = torch.empty(B * p["nrows"] * n_px * 3, device=images_bhwc.device, dtype=torch.uint8)
+        out = _empty((B, 3, n_px, n_px), device=images_bhwc.device, dtype=torch.float32)
+    else:
+        _out_operand("preprocess_uniform", out, (B, 3, n_px, n_px))
+    ws = _empty(B * p["nrows"] * n_px * 3, device=images_bhwc.device, dtype=torch.uint8)
     check(_lib.lib().dbmm_resize_crop_normalize_u8_batch(
         ptr(images_bhwc), B, H, W, ptr(p["hb"]), ptr(p["hk"]), p["hk"].shape[1], ptr(p["vb"]), ptr(p["vk"]), p["vk"].shape[1],
         p["row0"], p["nrows"], n_px, _F3(*CLIP_MEAN), _F3(*CLIP_STD), ptr(out), None, ptr(ws), ws.numel(), stream()),
