@@ -73,10 +73,10 @@ def kernel_source_hash(kernel_name):
 
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -> libdbmm_hip.so (in-tree, so it travels with the repo).  Incremental: a source
-    is recompiled when it, a shared header or include/dbmm.h is newer than its object; `force` recompiles all.
+    is recompiled when it, a shared header or a header under include/ is newer than its object; `force` recompiles all.
     Returns the library path; `build.last` lists the sources compiled by the most recent call."""
     srcs = sources()
-    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [os.path.join(INCLUDE, "dbmm.h")]
+    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(INCLUDE, "*.h"))
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(os.path.join(_HERE, "build"), exist_ok=True)
     objs, procs = [], []
@@ -276,6 +276,15 @@ _RESTYPES = {
 
 EXPORTS = tuple(_SIGS)
 
+# the entries include/dbmm_kernel_ops.h declares, bound beside the first table (that header says why there are two)
+_SIGS_KERNEL_OPS = {
+    "dbmm_workspace_bytes_pairdist_rbf_matvec": [_L, _L, _L],
+    "dbmm_pairdist_rbf_matvec": [_P, _P, _P, c_double, _P, _L, _L, _L, _P, _Z, _P],
+}
+_RESTYPES_KERNEL_OPS = {
+    "dbmm_workspace_bytes_pairdist_rbf_matvec": c_size_t,
+}
+
 
 def lib():
     """The loaded library; raises (never falls back) when it is not built."""
@@ -286,10 +295,11 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback for the dbmm_amd hot path.")
         L = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in _SIGS.items():
-            fn = getattr(L, name)          # AttributeError if the symbol is not exported
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, c_int)
+        for sigs, restypes in ((_SIGS, _RESTYPES), (_SIGS_KERNEL_OPS, _RESTYPES_KERNEL_OPS)):
+            for name, argtypes in sigs.items():
+                fn = getattr(L, name)          # AttributeError if the symbol is not exported
+                fn.argtypes = argtypes
+                fn.restype = restypes.get(name, c_int)
         _lib = L
     return _lib
 

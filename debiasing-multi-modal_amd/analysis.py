@@ -886,9 +886,10 @@ def alignment_from_sums(K, K2_total, row_sq, counts):
     return {"alignment": alignment, "hsic": hsic, "hsic_kk": hsic_kk, "hsic_ll": float(hsic_ll), "rel_bound": rel_bound}
 
 
-def _labelled_rows(what, embeddings, labels, max_labels):
+def _labelled_rows(what, embeddings, labels, max_labels, device=True):
     """(x, unique labels, dense ids [N], counts): the labels are counted and refused BEFORE the rows are looked at (more than
-    `max_labels`: DbmmUnsupported, fewer than two: ValueError), the rows must be device-resident"""
+    `max_labels`: DbmmUnsupported, fewer than two: ValueError), the rows must be device-resident (device=False leaves that check
+    to a caller that has refusals of its own to make first)"""
     if isinstance(embeddings, trainer.EmbeddingTable):
         x = embeddings.embeddings
         labels = embeddings.targets_group if labels is None else labels
@@ -906,7 +907,7 @@ def _labelled_rows(what, embeddings, labels, max_labels):
         raise ops.DbmmUnsupported(f"{what}: {len(uniq)} labels; the kernel sums at most {max_labels}")
     if len(uniq) < 2:
         raise ValueError(f"{what} needs at least two labels with rows, got {len(uniq)}")
-    if not x.is_cuda:
+    if device and not x.is_cuda:
         raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
     return x, uniq, dense.reshape(-1).astype(np.int64), counts
 
@@ -1094,6 +1095,278 @@ def probe_report(train_table, val_table, test_table, transform=None, scales=RBF_
             ok = len(np.unique(train_c)) >= 2 and np.isin(c, train_c).all()
             out[split]["spurious_from_train"] = (kernel_probe(train_x, train_c, scales=scales, query=x, query_labels=c)["balanced_accuracy"]
                                                  if ok else nan.copy())
+    return out
+
+
+# ---- kernel ridge regression: the trained non-linear probe ------------------------------------------------------------------------------
+# The Parzen probe above sees kernel densities only, and misses a labelling whose classes share their means and their density scale (the
+# radius of a ring, an XOR of two coordinates).  Kernel ridge regression on the same RBF kernel reads those: alpha = (K + lam I)^-1 T for
+# the centred one-hot targets T, convex and exact, no learning rate, stopped at a residual.  The one primitive it needs of the device is the
+# product of the kernel matrix with a few dense columns without the N x N matrix (ops.pairdist_rbf_matvec); the solver is conjugate
+# gradients on the host's side of that product, in float64 torch on the device.  Every step but the product runs anywhere.
+
+RIDGE_LAMS = (0.1, 1.0)
+RIDGE_MAX_COLUMNS = 16    # ops.PAIRDIST_MATVEC_MAX_C: the (lam, label) pairs of one fit are the columns of one product
+
+
+def cg_solve(matvec, B, shifts, tol=1e-5, max_iter=256):
+    """Conjugate gradients on (M + shifts[c] I) X[:, c] = B[:, c] for all columns together, M symmetric positive semi-definite and
+    known only through matvec(V) -> M V (float64 [n, C] in, float64 [n, C] out).  Float64 torch on B's device; ONE product per
+    iteration, shared by all columns; every column has its own step lengths and stops on its own: once its recurrence residual is
+    at most tol ||B[:, c]|| the column is frozen -- its iterate stays, its search direction is handed to matvec as zeros (which
+    ops.pairdist_rbf_matvec skips).  A zero right-hand side gives exact zeros, a zero curvature freezes the column.  After the
+    loop the TRUE residual B - (M + shift) X is formed with one more product.  Returns {'x': float64 [n, C], 'iterations': the
+    products of the loop, 'residual': float64 [C], the true residual's norm over ||B[:, c]|| (0 for a zero column), 'converged':
+    bool [C], the recurrence residual reached tol within max_iter}.  No random numbers, no atomics: the same bits on every call
+    if matvec gives the same bits."""
+    if not torch.is_tensor(B) or B.dim() != 2:
+        raise ValueError("cg_solve: B must be a tensor [n, C]")
+    B = B.double()
+    shifts = torch.as_tensor(np.asarray(shifts, dtype=np.float64).ravel(), device=B.device)
+    if shifts.shape[0] != B.shape[1]:
+        raise ValueError(f"cg_solve: {shifts.shape[0]} shifts for {B.shape[1]} columns")
+    if not (tol > 0 and max_iter >= 0):
+        raise ValueError(f"cg_solve: tol = {tol!r}, max_iter = {max_iter!r}")
+    apply = lambda V: matvec(V).double() + shifts * V
+    bnorm = B.norm(dim=0)
+    X = torch.zeros_like(B)
+    R = B.clone()
+    rs = (R * R).sum(0)
+    active = rs.sqrt() > tol * bnorm                                   # a zero column is converged at the start
+    P = torch.where(active, R, torch.zeros_like(R))
+    it = 0
+    while it < max_iter and bool(active.any()):
+        Q = apply(P)
+        pq = (P * Q).sum(0)
+        step = active & (pq > 0)
+        a = torch.where(step, rs / torch.where(step, pq, torch.ones_like(pq)), torch.zeros_like(pq))
+        X += a * P
+        R -= a * Q
+        rs_new = (R * R).sum(0)
+        go = step & (rs_new.sqrt() > tol * bnorm)
+        beta = torch.where(go, rs_new / torch.where(go, rs, torch.ones_like(rs)), torch.zeros_like(rs))
+        P = torch.where(go, R + beta * P, torch.zeros_like(R))
+        rs = torch.where(active, rs_new, rs)
+        active = go
+        it += 1
+    converged = rs.sqrt() <= tol * bnorm
+    true = (B - apply(X)).norm(dim=0)
+    residual = torch.where(bnorm > 0, true / torch.where(bnorm > 0, bnorm, torch.ones_like(bnorm)), torch.zeros_like(bnorm))
+    return {"x": X, "iterations": it, "residual": residual, "converged": converged}
+
+
+def _ridge_lams(what, lams, G):
+    """float64 [n_lam], every value finite and > 0 (else ValueError), n_lam * G columns at most RIDGE_MAX_COLUMNS (else DbmmUnsupported)"""
+    lams = np.asarray(lams, dtype=np.float64).ravel()
+    if lams.size == 0 or not (np.isfinite(lams).all() and (lams > 0).all()):
+        raise ValueError(f"{what}: lams = {lams.tolist()}; at least one ridge, every one finite and > 0")
+    if G is not None and lams.size * G > RIDGE_MAX_COLUMNS:
+        raise ops.DbmmUnsupported(f"{what}: {lams.size} ridges x {G} labels = {lams.size * G} columns; one product carries at most {RIDGE_MAX_COLUMNS}")
+    return lams
+
+
+def _ridge_from_operator(product, dense, G, gammas, lams, tol, max_iter, device):
+    """The host step of `kernel_ridge_fit`: product(gamma, V) -> K0 V, float64 [N, C], for the kernel matrix with a ZERO diagonal (what
+    ops.pairdist_rbf_matvec gives; a dense float64 matrix serves as well).  Targets: the one-hot columns of the dense labels minus
+    the label frequencies; one cg_solve per bandwidth on (K0 + (1 + lam) I) alpha = T with the (lam, label) pairs as columns.
+    Returns (alpha float64 [L, n_lam, N, G], iterations int64 [L], residual [L, n_lam, G], converged bool [L, n_lam, G], frequencies
+    float64 [G])."""
+    dense_t = torch.as_tensor(dense, device=device)
+    N, n_lam = dense_t.shape[0], len(lams)
+    freq = np.bincount(dense, minlength=G).astype(np.float64) / N
+    T = (dense_t.unsqueeze(1) == torch.arange(G, device=device).unsqueeze(0)).double() - torch.as_tensor(freq, device=device)
+    B = T.repeat(1, n_lam)                                              # column a * G + g: ridge a, label g
+    shifts = np.repeat(1.0 + np.asarray(lams, dtype=np.float64), G)
+    alpha, its, res, conv = [], [], [], []
+    for gam in gammas:
+        sol = cg_solve(lambda V: product(float(gam), V), B, shifts, tol, max_iter)
+        alpha.append(sol["x"].reshape(N, n_lam, G).permute(1, 0, 2))
+        its.append(sol["iterations"])
+        res.append(sol["residual"].reshape(n_lam, G).cpu().numpy())
+        conv.append(sol["converged"].reshape(n_lam, G).cpu().numpy())
+    return torch.stack(alpha).contiguous(), np.asarray(its, dtype=np.int64), np.stack(res), np.stack(conv), freq
+
+
+def _ridge_product(x, center):
+    """product(gamma, V) on the device: the float64 iterate rounded to fp32, one pass of ops.pairdist_rbf_matvec"""
+    return lambda gam, V: ops.pairdist_rbf_matvec(x, V.float().contiguous(), center, gam)
+
+
+def kernel_ridge_fit(embeddings, labels=None, gammas=None, scales=RBF_SCALES, lams=RIDGE_LAMS, transform=None, tol=1e-5, max_iter=256):
+    """Kernel ridge regression of a labelling on a split's rows, RBF kernel: alpha = (K + lam I)^-1 T per bandwidth and ridge, K the
+    kernel matrix with its unit diagonal, T the one-hot label columns minus the label frequencies (the frequencies are the
+    intercept of the scores).  Nothing N x N is stored: conjugate gradients (`cg_solve`) on ops.pairdist_rbf_matvec, one product
+    per iteration for all (lam, label) columns of a bandwidth, the weights handed to the kernel being the float64 iterate rounded to
+    fp32.  `embeddings`, `labels`, `transform` and the default bandwidths as in `kernel_probe` (at most 16 labels: more raise
+    DbmmUnsupported, fewer than two ValueError); every `lam` > 0 (else ValueError) and len(lams) * labels <= 16 (else
+    DbmmUnsupported) -- all of it before anything is launched.  The rows keep the input's order; the centre is their mean.
+
+    Returns {'alpha': float64 [L, n_lam, N, G] on the device, 'rows': the fp32 rows as given to the kernel, 'center', 'gammas',
+    'lams', 'labels': the unique labels, 'counts', 'intercept': float64 [G], 'iterations': int64 [L], 'residual' and 'converged':
+    [L, n_lam, G] -- the TRUE relative residual ||(K + lam I) alpha - T|| / ||T|| formed with one more product, and whether the
+    recurrence reached `tol` within `max_iter`; non-convergence is reported, never raised --, 'transform', 'tol'}.  In the
+    float64 study of this function CG took 5 - 50 iterations at lam in {0.1, 1} and up to 210 at lam = 1e-3."""
+    lams = _ridge_lams("kernel_ridge_fit", lams, None)
+    x, uniq, dense, counts = _labelled_rows("kernel_ridge_fit", embeddings, labels, RIDGE_MAX_COLUMNS, device=False)
+    G = len(uniq)
+    _ridge_lams("kernel_ridge_fit", lams, G)
+    if not x.is_cuda:
+        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+    x = x.float().contiguous()
+    if transform is not None:
+        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
+    gammas = rbf_gammas(x, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    if gammas.size == 0 or not (np.isfinite(gammas).all() and (gammas > 0).all()):
+        raise ValueError(f"kernel_ridge_fit: gammas = {gammas.tolist()}; at least one bandwidth, every one finite and > 0")
+    center = torch.from_numpy((_column_sums(x) / x.shape[0]).astype(np.float32)).to(x.device)
+    alpha, its, res, conv, freq = _ridge_from_operator(_ridge_product(x, center), dense, G, gammas, lams, tol, max_iter, x.device)
+    return {"alpha": alpha, "rows": x, "center": center, "gammas": gammas, "lams": lams, "labels": uniq, "counts": counts, "intercept": freq,
+            "iterations": its, "residual": res, "converged": conv, "transform": transform, "tol": tol}
+
+
+def _ridge_scores(product, alpha, intercept, gammas, M):
+    """The host step of `kernel_ridge_predict`: product(gamma, W) on the rows [train; query] with the weights W = [alpha; 0], the query
+    rows of the result plus the intercept.  scores float64 [L, n_lam, M, G] (host), pred int64 [L, n_lam, M] (dense: the first
+    maximum), margin [L, n_lam, M]: the gap between the two highest scores."""
+    L, n_lam, N, G = alpha.shape
+    scores = []
+    for l, gam in enumerate(gammas):
+        W = torch.cat([alpha[l].permute(1, 0, 2).reshape(N, n_lam * G), torch.zeros(M, n_lam * G, dtype=alpha.dtype, device=alpha.device)])
+        scores.append(product(float(gam), W)[N:].reshape(M, n_lam, G).permute(1, 0, 2))
+    scores = torch.stack(scores).cpu().numpy() + np.asarray(intercept, dtype=np.float64)
+    top = np.sort(scores, axis=3)
+    return scores, scores.argmax(axis=3).astype(np.int64), top[..., -1] - top[..., -2]
+
+
+def kernel_ridge_predict(fit, query):
+    """The scores of the query rows under a `kernel_ridge_fit`: s[l, a, q, g] = sum_j k_l(query[q], x_j) alpha[l, a, j, g] +
+    intercept[g].  `query`: a device tensor [M, D]; the fit's `transform` is applied.  One product per bandwidth on the rows
+    [train; query] with the weights [alpha; 0]: the query rows carry zero weights, so their column blocks are skipped, and the
+    query rows of the result are the scores.  The train-against-train tiles of that pass are wasted work (N / (N + M) of the
+    tiles that carry weight); a rectangular pass is a later change.  Returns {'scores': float64 [L, n_lam, M, G], 'pred':
+    [L, n_lam, M] as values of the fit's `labels`, 'pred_dense': the same as indices into `labels`, 'margin': [L, n_lam, M], the
+    gap between the two highest scores}."""
+    x = fit["rows"]
+    if not torch.is_tensor(query) or not query.is_cuda or query.dim() != 2 or query.shape[0] < 1:
+        raise ValueError("kernel_ridge_predict: query must be a device tensor [M, D]")
+    q = query.float().contiguous()
+    if fit["transform"] is not None:
+        q = _transformed_rows(q, fit["transform"], TRANSFORM_ROWS)
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"kernel_ridge_predict: query rows have {q.shape[1]} columns, the fit's {x.shape[1]}")
+    rows = torch.cat([x, q])
+    scores, pred, margin = _ridge_scores(_ridge_product(rows, fit["center"]), fit["alpha"], fit["intercept"], fit["gammas"], q.shape[0])
+    return {"scores": scores, "pred": fit["labels"][pred], "pred_dense": pred, "margin": margin}
+
+
+def stratified_holdout(dense, holdout, seed):
+    """(fit rows, held-out rows), both sorted int64: a `holdout` share of every label's rows, rounded to the nearest count but at
+    least one row of the label on each side (a label's only row stays with the fit), drawn label by label from a private
+    np.random.RandomState(seed).  `holdout` outside (0, 1) raises ValueError."""
+    if not (isinstance(holdout, (int, float)) and 0.0 < holdout < 1.0):
+        raise ValueError(f"holdout = {holdout!r}; a share in (0, 1)")
+    dense = np.asarray(dense).ravel()
+    rng = np.random.RandomState(seed)
+    held = []
+    for g in np.unique(dense):
+        idx = np.flatnonzero(dense == g)
+        k = min(max(int(round(holdout * len(idx))), 1), len(idx) - 1)
+        held.append(idx[rng.permutation(len(idx))[:k]])
+    held = np.sort(np.concatenate(held)).astype(np.int64)
+    return np.setdiff1d(np.arange(len(dense), dtype=np.int64), held), held
+
+
+def _ridge_best(bal, gammas, lams):
+    """the (bandwidth, ridge) of highest balanced accuracy, ties toward the smaller gamma and then the larger lam"""
+    best = None
+    for l in np.argsort(gammas, kind="stable"):
+        for a in np.argsort(-np.asarray(lams), kind="stable"):
+            if best is None or bal[l, a] > bal[best]:
+                best = (int(l), int(a))
+    return {"index": best, "gamma": float(gammas[best[0]]), "lam": float(lams[best[1]]), "balanced_accuracy": float(bal[best])}
+
+
+def kernel_ridge_probe(embeddings, labels=None, query=None, query_labels=None, holdout=0.25, seed=0, **fit_kw):
+    """The kernel ridge probe: how well a labelling is read off a split's rows by kernel ridge regression, as held-out accuracy.
+    With `query` (a device tensor [M, D]) and `query_labels` [M] (values of `labels`): fit on the rows, score the query rows.
+    Without: a stratified `holdout` share of every label is held out (`stratified_holdout`, deterministic in `seed`), the fit
+    runs on the rest and the held-out rows are scored.  `fit_kw`: kernel_ridge_fit's gammas, scales, lams, transform, tol, max_iter.
+
+    Returns {'accuracy', 'balanced_accuracy': [L, n_lam], 'recall': [L, n_lam, G] (nan for a label without scored rows), 'best':
+    {'index': (l, a), 'gamma', 'lam', 'balanced_accuracy'}, the (bandwidth, ridge) of highest balanced accuracy, ties toward the
+    smaller gamma and then the larger lam, 'pred': [L, n_lam, M] (values of `labels`), 'scores', 'margin', 'held_out': the
+    held-out rows' indices (None with `query`), and the fit's 'gammas', 'lams', 'labels', 'counts', 'iterations', 'residual',
+    'converged'}.  Read 'converged' and 'residual' beside the accuracies."""
+    if query is None:
+        if not (isinstance(holdout, (int, float)) and 0.0 < holdout < 1.0):
+            raise ValueError(f"kernel_ridge_probe: holdout = {holdout!r}; a share in (0, 1)")
+        x, _, dense, _ = _labelled_rows("kernel_ridge_probe", embeddings, labels, RIDGE_MAX_COLUMNS, device=False)
+        l_np = (embeddings.targets_group if labels is None else labels) if isinstance(embeddings, trainer.EmbeddingTable) else labels
+        l_np = (l_np.detach().cpu().numpy() if torch.is_tensor(l_np) else np.asarray(l_np)).ravel()
+        _ridge_lams("kernel_ridge_probe", fit_kw.get("lams", RIDGE_LAMS), len(np.unique(dense)))
+        if not x.is_cuda:
+            raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+        keep, held = stratified_holdout(dense, holdout, seed)
+        x = x.float().contiguous()
+        fit = kernel_ridge_fit(ops.gather_rows(x, torch.from_numpy(keep).to(x.device)), l_np[keep], **fit_kw)
+        query, query_labels = ops.gather_rows(x, torch.from_numpy(held).to(x.device)), l_np[held]
+    else:
+        if query_labels is None:
+            raise ValueError("kernel_ridge_probe: `query` rows need their `query_labels`")
+        held = None
+        fit = kernel_ridge_fit(embeddings, labels, **fit_kw)
+    uniq, G = fit["labels"], len(fit["labels"])
+    q_np = (query_labels.detach().cpu().numpy() if torch.is_tensor(query_labels) else np.asarray(query_labels)).ravel()
+    pos = np.minimum(np.searchsorted(uniq, q_np), G - 1)
+    if q_np.shape[0] != query.shape[0] or not np.array_equal(uniq[pos], q_np):
+        raise ValueError("kernel_ridge_probe: query_labels must be one value of `labels` per query row")
+    out = kernel_ridge_predict(fit, query)
+    L, n_lam = len(fit["gammas"]), len(fit["lams"])
+    sc = _probe_scores(out["pred_dense"].reshape(L * n_lam, -1), pos.astype(np.int64), G)
+    res = {"accuracy": sc["accuracy"].reshape(L, n_lam), "recall": sc["recall"].reshape(L, n_lam, G),
+           "balanced_accuracy": sc["balanced_accuracy"].reshape(L, n_lam)}
+    res["best"] = _ridge_best(res["balanced_accuracy"], fit["gammas"], fit["lams"])
+    res.update(pred=out["pred"], scores=out["scores"], margin=out["margin"], held_out=held)
+    res.update({k: fit[k] for k in ("gammas", "lams", "labels", "counts", "iterations", "residual", "converged")})
+    return res
+
+
+def ridge_report(train_table, val_table, test_table, transform=None, **kw):
+    """How readable the spurious attribute is to a TRAINED non-linear probe: `kernel_ridge_fit` on train's rows for targets_spurious,
+    and for targets_spurious among each class's rows, scored on val and on test (`kernel_ridge_predict`).  {'val': r, 'test': r}
+    with r = {'spurious': the balanced accuracy [L, n_lam] of the split's rows, 'spurious_within_class': {class: the same among
+    that class's rows}, 'best': kernel_ridge_probe's 'best' for 'spurious'}; nan where train has one place only (or none of the
+    class) or the split has a place train has not.  `transform` is applied once per split, `kw` goes to kernel_ridge_fit: run it
+    raw, with an adapter as `transform=`, and on erased_table's rows."""
+    xs = [_device_rows(t, transform) for t in (train_table, val_table, test_table)]
+    ys = [t.targets.cpu().numpy() for t in (train_table, val_table, test_table)]
+    cs = [t.targets_spurious.cpu().numpy() for t in (train_table, val_table, test_table)]
+    L = len(kw["gammas"]) if kw.get("gammas") is not None else len(kw.get("scales", RBF_SCALES))
+    nan = np.full((L, len(np.asarray(kw.get("lams", RIDGE_LAMS)).ravel())), np.nan)
+    out = {"val": {"spurious_within_class": {}}, "test": {"spurious_within_class": {}}}
+
+    def scored(rows_of):
+        """per split the balanced accuracy (and best) of a fit on train's selected rows"""
+        tr = rows_of(0)
+        res = {}
+        for k, split in ((1, "val"), (2, "test")):
+            q = rows_of(k)
+            ok = len(tr) and len(q) and len(np.unique(cs[0][tr])) >= 2 and np.isin(cs[k][q], cs[0][tr]).all()
+            if not ok:
+                res[split] = None
+                continue
+            sub = lambda j, idx: ops.gather_rows(xs[j], torch.from_numpy(idx).to(xs[j].device))
+            res[split] = kernel_ridge_probe(sub(0, tr), cs[0][tr], query=sub(k, q), query_labels=cs[k][q], **kw)
+        return res
+
+    whole = scored(lambda k: np.arange(len(ys[k]), dtype=np.int64))
+    for split in out:
+        out[split]["spurious"] = nan.copy() if whole[split] is None else whole[split]["balanced_accuracy"]
+        out[split]["best"] = None if whole[split] is None else whole[split]["best"]
+    for cls in np.unique(ys[0]):
+        within = scored(lambda k: np.flatnonzero(ys[k] == cls))
+        for split in out:
+            out[split]["spurious_within_class"][int(cls)] = nan.copy() if within[split] is None else within[split]["balanced_accuracy"]
     return out
 
 

@@ -33,6 +33,7 @@
 // one text; the workspace grows by 512 bytes per workgroup and bandwidth.
 #include <stdlib.h>
 #include "persistent_tiles.h"
+#include "../../include/dbmm_kernel_ops.h"
 
 namespace {
 
@@ -61,7 +62,9 @@ __global__ __launch_bounds__(256) void pairdist_absmax_kernel(const float* __res
     }
 }
 
-// one wave per row: centre, scale, split; P[row] = hi[0 .. Dp) | lo[0 .. Dp), info[row] = {sum (hi + lo)^2, group}
+// one wave per row: centre, scale, split; P[row] = hi[0 .. Dp) | lo[0 .. Dp), info[row] = {sum (hi + lo)^2, group}; without LABELS g is
+// not read and every row is in no group (the weighted rows pass has no labels)
+template <bool LABELS>
 __global__ __launch_bounds__(256) void pairdist_split_kernel(const float* __restrict__ x, const float* __restrict__ c, const int64_t* __restrict__ g,
                                                              const unsigned* __restrict__ amax_bits, u16* __restrict__ P, RowInfo* __restrict__ info,
                                                              int N, int D, int Dp, int G) {
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(256) void pairdist_split_kernel(const float* __rest
     }
     nrm = wave_sum(nrm);
     if (lane == 0) {
-        const int64_t gv = g[row];
+        const int64_t gv = LABELS ? g[row] : -1;
         info[row] = RowInfo{nrm, (gv >= 0 && gv < G) ? (int)gv : NO_GROUP};
     }
 }
@@ -103,12 +106,14 @@ struct PairDistP {
 
 struct PairRowsP;                                                  // the rows kernel's parameters, below: each map names its own
 struct PairRowsRbfP;
+struct PairRowsMatvecP;
 
 // The element maps of the tile kernel: what a pair adds to its bucket, from its d^2 >= 0 in scaled units (2^-2s of the rows' own).
 // pre() is applied once to every accumulator element, in place; val(a, coef(p, l)) is summed, once per l < n_sums(p).
 struct DistanceMap {                                               // ||x_i - x_j||: one sum per bucket, in units of 2^-s
     static constexpr int MAX_L = 1;
     static constexpr bool SCALED = true;
+    static constexpr bool WEIGHTED = false;
     using RowsP = PairRowsP;
     template <class Params> static __device__ __forceinline__ int n_sums(const Params&) { return 1; }
     static __device__ __forceinline__ float pre(float d2) { return __builtin_sqrtf(d2); }
@@ -121,6 +126,7 @@ struct DistanceMap {                                               // ||x_i - x_
 struct RbfMap {                                                    // exp(-gamma_l ||x_i - x_j||^2), l < L: d^2 stays in the registers, L sums per bucket
     static constexpr int MAX_L = RBF_MAX_L;
     static constexpr bool SCALED = false;
+    static constexpr bool WEIGHTED = false;
     using RowsP = PairRowsRbfP;
     template <class Params> static __device__ __forceinline__ int n_sums(const Params& p) { return p.L; }
     static __device__ __forceinline__ float pre(float d2) { return d2; }
@@ -139,6 +145,12 @@ struct RbfMap {                                                    // exp(-gamma
     // (|c d^2| < 2^-96 there: exp2 gives 1 either way)
     static __device__ __forceinline__ float self_pair() { return __builtin_inff(); }
     static __device__ __forceinline__ float self_coef(float c) { return fminf(c, -1.17549435e-38f); }
+};
+// The rows kernel only: RbfMap's kernel values at ONE bandwidth, each column j weighted by v[j][c] for c < G weight columns instead of
+// being bucketed by a label: R[i][c] = sum over j != i of exp(-gamma ||x_i - x_j||^2) v[j][c], the kernel-matrix product
+struct RbfMatvecMap : RbfMap {
+    static constexpr bool WEIGHTED = true;
+    using RowsP = PairRowsMatvecP;
 };
 
 template <class Map>
@@ -319,7 +331,7 @@ int bucket_sums(const float* x, const int64_t* groups, const float* center, cons
     const int g1 = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
     hipLaunchKernelGGL(pairdist_absmax_kernel, dim3(g1), dim3(256), 0, s, x, center, n4, (int)(D / 4), amax);
     DBMM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pairdist_split_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
+    hipLaunchKernelGGL(pairdist_split_kernel<true>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
                        (int)G);
     DBMM_CHECK_LAUNCH();
     PairDistP p{};
@@ -396,6 +408,14 @@ extern "C" int dbmm_pairdist_rbf_group_sums(const float* x, const int64_t* group
 // reduction above runs once per l in a runtime loop: the partials are part [C][L][N][G], the owner thread's update runs once per (l, label
 // present).  The predicated path forms the exponentials again for every label (the ring leaves no registers to keep L x 128 values), with
 // the coefficient opaque per label so that they are not hoisted and d^2 is not spilled; neither instantiation uses scratch.
+//
+// A third map, RbfMatvecMap (dbmm_pairdist_rbf_matvec, include/dbmm_kernel_ops.h): the kernel matrix times C <= 16 dense columns,
+// R[i][c] = sum over j != i of exp(-gamma ||x_i - x_j||^2) v[j][c], what conjugate gradients on (K + lambda I) alpha = T need.  No labels: the
+// tile's weights (v fp32 [N][C], zero for a column past N) go to LDS, 16 KB beside the ring, and e_mask holds the weight columns with a
+// non-zero weight in the tile -- the others are skipped, which adds nothing and changes no value (one-hot columns, frozen CG columns and
+// the zero weights of appended query rows cost nothing).  ONE bandwidth: the kernel values are formed once, in place in the accumulators,
+// and a weight column is w0 k0 + w1 k1 per lane, then the same tree, e_rsum, barrier and owner update as a label's sum, in a runtime loop:
+// a column's sums are formed by the same instructions whatever C is.  part is [chunk][N][C]; no scratch, 157,700 bytes of LDS.
 namespace {
 
 constexpr int ROWS_MAX_G = 16;                                     // labels live in a byte; 16 = the k-means kernels' K
@@ -409,6 +429,9 @@ struct PairRowsP {
 };
 struct PairRowsRbfP : PairRowsP {                                  // RbfMap's: the distance instantiation keeps its kernel arguments
     const unsigned* amax_bits; double gamma[RBF_MAX_L]; int L;     // as in PairDistP
+};
+struct PairRowsMatvecP : PairRowsRbfP {                            // RbfMatvecMap's: L = 1, groups is null, G counts the weight columns
+    const float* v;                                                // the weights [N][G], row-major
 };
 
 // v[16 ii + r] (ii = 0 / 1, r < 16) of the 32 lanes with the same fh -> the sums over those lanes, one per lane: afterwards lane fr holds in
@@ -433,6 +456,9 @@ __global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const typena
     __shared__ unsigned char e_grp[256];                           // labels of the tile's columns
     __shared__ unsigned e_mask;                                    // labels present among the columns; bit 16: a column in no group
     __shared__ float e_rsum[2][4][256];                            // [parity][column wave][row]: a wave's sums over its 64 columns
+    // RbfMatvecMap: [weight column][tile column], 16 KB: 154.3 KB of LDS with the ring and the arrays above, under the CU's 160 KB.  The other
+    // maps never name it and their instantiations do not allocate it (138.3 KB, as before)
+    __shared__ float e_w[Map::WEIGHTED ? ROWS_MAX_G : 1][256];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wid >> 2, wc = wid & 3;
     const int fr = lane & 31, fh = lane >> 5;
@@ -494,7 +520,19 @@ __global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const typena
         {
             const int src = (te < 256 ? em0 : en0 - 256) + te;      // threads 0 .. 255: the tile's rows, 256 .. 511: its columns
             e_norm[te] = src < p.N ? p.info[src].norm : 0.f;
-            if (te >= 256) {
+            if constexpr (Map::WEIGHTED) {
+                // the tile's weights, zero for a column past N (its kernel value is some finite number); e_mask: the weight columns that
+                // have a non-zero weight in this tile.  The others are skipped below, which adds nothing and so changes no value
+                if (te >= 256) {
+                    unsigned nz = 0u;
+                    for (int c = 0; c < p.G; ++c) {
+                        const float w = src < p.N ? p.v[(size_t)src * p.G + c] : 0.f;
+                        e_w[c][te - 256] = w;
+                        nz |= w != 0.f ? 1u << c : 0u;
+                    }
+                    if (nz) atomicOr(&e_mask, nz);                    // integer, order-free
+                }
+            } else if (te >= 256) {
                 int g = ROWS_NO_GROUP;
                 if (src < p.N) {
                     const int64_t gv = p.groups[src];
@@ -556,7 +594,34 @@ __global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const typena
 #pragma unroll 1
         do {
             const float cf = Map::self_coef(Map::coef(p, l));
-            if (fast) {                                               // one label, all 256 columns: no predicates
+            if constexpr (Map::WEIGHTED) {
+                // the kernel values once, in place (the diagonal's +inf gives an exact 0); a weight column then costs one multiply-add per
+                // element and no second exponential.  One bandwidth: this body runs once
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        acc[i][0][r] = Map::val(acc[i][0][r], cf);
+                        acc[i][1][r] = Map::val(acc[i][1][r], cf);
+                    }
+                // once per weight column with a non-zero weight in this tile: a runtime loop, never unrolled, so a column's sums are formed
+                // by the same instructions whatever the other columns of the call are
+#pragma unroll 1
+                for (unsigned mb = mB & 0xffffu; mb; mb &= mb - 1) {
+                    const int c = __builtin_ctz(mb);
+                    const float w0 = e_w[c][c0], w1 = e_w[c][c0 + 1];
+#pragma unroll
+                    for (int hh = 0; hh < 2; ++hh) {
+                        float v[32];
+#pragma unroll
+                        for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) v[16 * ii + r] = fmaf(w1, acc[2 * hh + ii][1][r], w0 * acc[2 * hh + ii][0][r]);
+                        fold_store(v, hh);
+                    }
+                    add_label(l, c);
+                }
+            } else if (fast) {                                        // one label, all 256 columns: no predicates
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     float v[32];
@@ -624,10 +689,11 @@ inline size_t rows_workspace_bytes(int64_t N, int64_t D, int64_t G, int64_t L) {
            (size_t)ROWS_MAX_CHUNKS * (size_t)L * (size_t)N * (size_t)G * sizeof(double);
 }
 
-// absmax, split, tiles, fold for one element map; the operands have been checked.  gammas: RbfMap's L bandwidths (host), else null and L = 1
+// absmax, split, tiles, fold for one element map; the operands have been checked.  gammas: RbfMap's L bandwidths (host), else null and L = 1;
+// v: RbfMatvecMap's weights [N][G], with groups null and L = 1
 template <class Map>
 int row_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums, int64_t N, int64_t D, int64_t G,
-             void* workspace, void* stream) {
+             void* workspace, void* stream, const float* v = nullptr) {
     const long long Dp = padded_dim(D);
     char* ws = (char*)workspace;
     unsigned* amax = (unsigned*)ws;
@@ -642,7 +708,7 @@ int row_sums(const float* x, const int64_t* groups, const float* center, const d
     hipLaunchKernelGGL(pairdist_absmax_kernel, dim3(g1), dim3(256), 0, s, x, center, n4, (int)(D / 4), amax);
     DBMM_CHECK_LAUNCH();
     // (the split's own group column is not read here: the tile kernel takes the labels from `groups`)
-    hipLaunchKernelGGL(pairdist_split_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
+    hipLaunchKernelGGL(pairdist_split_kernel<!Map::WEIGHTED>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
                        (int)G);
     DBMM_CHECK_LAUNCH();
     typename Map::RowsP p{};
@@ -655,6 +721,7 @@ int row_sums(const float* x, const int64_t* groups, const float* center, const d
         p.amax_bits = amax; p.L = (int)L;
         for (int l = 0; l < L; ++l) p.gamma[l] = gammas[l];
     }
+    if constexpr (Map::WEIGHTED) p.v = v;
     const long long n_out = L * N * G;
     e = hipMemsetAsync(part, 0, (size_t)p.C * (size_t)n_out * sizeof(double), s);            // the units' running sums start at zero
     if (e != hipSuccess) return (int)e;
@@ -703,4 +770,22 @@ extern "C" int dbmm_pairdist_rbf_row_group_sums(const float* x, const int64_t* g
     if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
     if (workspace_bytes < dbmm_workspace_bytes_pairdist_rbf_rows(N, D, G, L)) return DBMM_E_WORKSPACE;
     return row_sums<RbfMap>(x, groups, center, gammas, L, sums, N, D, G, workspace, stream);
+}
+
+// see include/dbmm_kernel_ops.h
+extern "C" size_t dbmm_workspace_bytes_pairdist_rbf_matvec(int64_t N, int64_t D, int64_t C) {
+    if (N <= 0 || D <= 0 || C < 1 || C > ROWS_MAX_G) return 0;
+    return rows_workspace_bytes(N, D, C, 1);
+}
+
+// see include/dbmm_kernel_ops.h
+extern "C" int dbmm_pairdist_rbf_matvec(const float* x, const float* v, const float* center, double gamma, double* out, int64_t N, int64_t D, int64_t C,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (N <= 0 || D <= 0 || N > (1 << 23) || C < 1 || C > ROWS_MAX_G) return DBMM_E_SHAPE;
+    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
+    if (!x || !v || !center || !out || !workspace) return DBMM_E_ARG;
+    if (!(gamma > 0.0) || !(gamma <= 1.79769313486231570e308)) return DBMM_E_ARG;                 // finite and positive
+    if (!dbmm_aligned16(x) || !dbmm_aligned16(v) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
+    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rbf_matvec(N, D, C)) return DBMM_E_WORKSPACE;
+    return row_sums<RbfMatvecMap>(x, nullptr, center, &gamma, 1, out, N, D, C, workspace, stream, v);
 }

@@ -1806,6 +1806,35 @@ def pairdist_rbf_row_group_sums(x, groups, n_groups, center, gammas):
     return out
 
 
+PAIRDIST_MATVEC_MAX_C = 16          # weight columns of one kernel-matrix product (csrc/pairdist.hip: ROWS_MAX_G)
+
+
+def pairdist_rbf_matvec(x, v, center, gamma):
+    """R float64 [N, C]: R[i, c] = sum over j != i of exp(-gamma ||x[i] - x[j]||^2) v[j, c], the product of the RBF kernel matrix of
+    the rows (zero diagonal) with C dense columns, on the fused Gram kernel (dbmm_pairdist_rbf_matvec): pairdist_rbf_row_group_sums'
+    pass with the weights v in place of the labels -- no N x N matrix, the kernel values formed once per tile and a further column
+    one multiply-add per pair, float64 sums in a fixed order, the same bits on every call, and a column's result does not depend on
+    the other columns of the call.  x, center as pairdist_row_group_sums; v fp32 [N, C] contiguous, 1 <= C <= 16, signed; gamma:
+    one finite number > 0 (a host value).  A 256-row block of v that is zero in a column costs that column nothing: one-hot
+    columns and zero weights on appended query rows are cheap.  An entry is good to 1e-4 sum_j k_ij |v_jc|; the kernel matrix with
+    its unit diagonal is R + v."""
+    gam = _rbf_gammas("pairdist_rbf_matvec", [gamma])                               # a host value: refused before any device is touched
+    N, D = _rows_operand("pairdist_rbf_matvec", x)
+    _f32_operand("pairdist_rbf_matvec", "v", v, x)
+    if v.dim() != 2 or v.shape[0] != N or not 1 <= v.shape[1] <= PAIRDIST_MATVEC_MAX_C:
+        raise _lib.DbmmError(f"pairdist_rbf_matvec: v must be [{N}, C] with C in 1..{PAIRDIST_MATVEC_MAX_C}, got {tuple(v.shape)}")
+    _f32_operand("pairdist_rbf_matvec", "center", center, x, D)
+    C = v.shape[1]
+    L = _lib.lib()
+    nbytes = L.dbmm_workspace_bytes_pairdist_rbf_matvec(N, D, C)
+    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # planes and partials: sized by the call, not cached
+    out = _empty((N, C), device=x.device, dtype=torch.float64)
+    rc = L.dbmm_pairdist_rbf_matvec(x.data_ptr(), v.data_ptr(), center.data_ptr(), gam[0], out.data_ptr(), N, D, C, ws.data_ptr(),
+                                    ws.numel() * 4, stream())
+    _served(rc, "pairdist_rbf_matvec", f"N = {N}, D = {D}")
+    return out
+
+
 def covariance(x, center):
     """S float64 [D, D]: S[a, b] = sum_i (x[i, a] - center[a]) (x[i, b] - center[b]), about the given center exactly, on the fused
     scatter kernel (dbmm_covariance): no centred copy of x, exact fp32 products, no fp32 chain longer than 1024 rows, float64 sums
