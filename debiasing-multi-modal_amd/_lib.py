@@ -44,7 +44,7 @@ KERNEL_SOURCES = (
     ("linear_sweep_", ("linear_sweep.hip", "linear_bodies.inc", "common.h")),
     ("linear_prox_", ("linear_prox.hip", "linear_bodies.inc", "common.h")),
     ("linear_", ("linear_step.hip", "linear_bodies.inc", "common.h")),
-    ("pairdist_", ("pairdist.hip", "fp16_ring.inc", "persistent_tiles.h", "common.h")),
+    ("pairdist_", ("pairdist.hip", "pairdist_ring.inc", "fp16_ring.inc", "persistent_tiles.h", "common.h")),
     ("covariance_", ("covariance.hip", "common.h")),
     ("project_rows_", ("covariance.hip", "common.h")),
     ("sym_eig_", ("sym_eig.hip", "common.h")),

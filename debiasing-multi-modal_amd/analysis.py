@@ -17,20 +17,55 @@ TABLE_INDEX = ["Acc.", "Div.", "Centr. Norm."]
 TABLE_COLUMNS = ["Avg.", "Worst", "group0", "group1", "group2", "group3"]
 
 
-def _rows_and_groups(embeddings, groups):
-    if isinstance(embeddings, trainer.EmbeddingTable):
-        x = embeddings.embeddings
-        groups = embeddings.targets_group if groups is None else groups
-    else:
-        x = embeddings
-    if groups is None:
-        raise ValueError("a device tensor of embeddings needs its `groups` array")
+def _need_device(x):
     if not torch.is_tensor(x) or not x.is_cuda:
         raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
-    g_np = groups.detach().cpu().numpy() if torch.is_tensor(groups) else np.asarray(groups)
-    if g_np.ndim != 1 or g_np.shape[0] != x.shape[0]:
-        raise ValueError(f"groups has shape {g_np.shape} for {x.shape[0]} rows")
-    return x, g_np
+
+
+def _labelled_rows(what, embeddings, labels, max_labels=None, min_labels=2, device="first"):
+    """(x, unique labels, dense ids int64 [N], counts) of an EmbeddingTable (its targets_group unless `labels` is given) or a tensor
+    [N, D] with `labels` [N]: any integers, through np.unique.  More than `max_labels` of them raise DbmmUnsupported, fewer than
+    `min_labels` ValueError.  `device` says where the refusal of rows that are not device-resident falls: "first" -- before the
+    labels are looked at, and the labels must then be one-dimensional --, "last" -- after every refusal of the labels --, or None:
+    left to a caller that has refusals of its own to make first (_need_device)."""
+    if isinstance(embeddings, trainer.EmbeddingTable):
+        x = embeddings.embeddings
+        labels = embeddings.targets_group if labels is None else labels
+    else:
+        x = embeddings
+    if labels is None:
+        raise ValueError(f"{what}: a device tensor of embeddings needs its labels array")
+    if device == "first":
+        _need_device(x)
+    elif not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError(f"{what}: the rows must be an EmbeddingTable or a tensor [N, D]")
+    l_np = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if device != "first":
+        l_np = l_np.ravel()
+    if l_np.ndim != 1 or l_np.shape[0] != x.shape[0]:
+        raise ValueError(f"{what}: labels of shape {l_np.shape} for {x.shape[0]} rows")
+    uniq, dense, counts = np.unique(l_np, return_inverse=True, return_counts=True)
+    if max_labels is not None and len(uniq) > max_labels:
+        raise ops.DbmmUnsupported(f"{what}: {len(uniq)} labels; the kernel takes at most {max_labels}")
+    if len(uniq) < min_labels:
+        raise ValueError(f"{what} needs at least {min_labels} labels with rows, got {len(uniq)}")
+    if device == "last":
+        _need_device(x)
+    return x, uniq, dense.reshape(-1).astype(np.int64), counts
+
+
+TRANSFORM_ROWS = 4096     # rows per batch of `transform`
+
+
+def _prepared(x, transform=None):
+    """the rows as the kernels take them: fp32, contiguous, after `transform` (a callable emb -> emb, batch by batch in eval mode)"""
+    x = x.float().contiguous()
+    return x if transform is None else _transformed_rows(x, transform, TRANSFORM_ROWS)
+
+
+def _resolved_gammas(x, gammas, scales):
+    """the bandwidths of a call, float64 [L]: the caller's, or rbf_gammas(scales) of the prepared rows"""
+    return rbf_gammas(x, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
 
 
 SUM_ROWS = 512
@@ -46,6 +81,35 @@ def _column_sums(rows):
     return acc.cpu().numpy()
 
 
+def _sorted_pass(x, dense, kernel, per_row=False, extra=None, counts=None):
+    """One pass of a pairwise kernel over the rows x sorted by their dense label (a stable sort and ONE gather: nearly every tile
+    then holds one label), followed by the rows `extra` with label -1.  kernel(xs, ids, center) -> a device tensor; the centre is the
+    fp32 mean of what is passed, from _column_sums of it -- with `counts`, of each label's slice, and those sums [G, D] are returned
+    beside the result (group_stats' means).  The result comes back on the host, per_row: [..., N (+ M), G] in the INPUT's row order,
+    x's rows first.  kernel None: the gather and the sums only."""
+    order = np.argsort(dense, kind="stable")
+    ids = dense[order]
+    if extra is not None:
+        order = np.concatenate([order, x.shape[0] + np.arange(extra.shape[0], dtype=np.int64)])
+        ids = np.concatenate([ids, np.full(extra.shape[0], -1, dtype=np.int64)])
+        x = torch.cat([x, extra])
+    xs = ops.gather_rows(x, torch.from_numpy(order).to(x.device))
+    if counts is None:
+        sums = total = _column_sums(xs)
+    else:
+        bounds = np.concatenate([[0], np.cumsum(counts)])
+        sums = np.stack([_column_sums(xs[bounds[k]:bounds[k + 1]]) for k in range(len(counts))])        # [G, D] float64, fixed order
+        total = sums.sum(0)
+    if kernel is None:
+        return None, sums
+    center = torch.from_numpy((total / xs.shape[0]).astype(np.float32)).to(x.device)
+    out = kernel(xs, torch.from_numpy(ids.astype(np.int64)).to(x.device), center).cpu().numpy()
+    if per_row:
+        sorted_out, out = out, np.empty_like(out)
+        out[..., order, :] = sorted_out
+    return out, sums
+
+
 def group_stats(embeddings, groups=None, return_dist=True):
     """GetGroupWiseStatEbd: {'mean_vector': {'full': v, g: v, ...}, 'mean_vector_norm': {...}, 'pairwise_distance': {...}} with the
     groups in np.unique order and numpy values; 'pairwise_distance' is sum over ordered pairs / (n (n - 1)) of the Euclidean distance
@@ -56,15 +120,10 @@ def group_stats(embeddings, groups=None, return_dist=True):
     `embeddings`: an EmbeddingTable (its targets_group unless `groups` is given) or a device tensor [N, D] with `groups` [N].
     The rows are sorted by group first (one gather), so that a group's mean is a slice's column sum and nearly every tile of the
     distance kernel holds one bucket."""
-    x, g_np = _rows_and_groups(embeddings, groups)
-    uniq, dense, counts = np.unique(g_np, return_inverse=True, return_counts=True)
+    x, uniq, dense, counts = _labelled_rows("group_stats", embeddings, groups, 8 if return_dist else None, min_labels=1)
     G, N = len(uniq), x.shape[0]
-    if return_dist and G > 8:
-        raise ops.DbmmUnsupported(f"group_stats: {G} groups; the distance kernel buckets at most 8")
-    order = np.argsort(dense, kind="stable")
-    xs = ops.gather_rows(x.float().contiguous(), torch.from_numpy(order).to(x.device))
-    bounds = np.concatenate([[0], np.cumsum(counts)])
-    sums = np.stack([_column_sums(xs[bounds[k]:bounds[k + 1]]) for k in range(G)])                       # [G, D] float64, fixed order
+    kernel = (lambda xs, ids, center: ops.pairdist_group_sums(xs, ids, G, center)) if return_dist else None
+    S, sums = _sorted_pass(_prepared(x), dense, kernel, counts=counts)
     mean_full = sums.sum(0) / N
     means = sums / counts.astype(np.float64)[:, None]
     norms = np.linalg.norm(np.concatenate([mean_full[None], means]), axis=1)
@@ -76,8 +135,6 @@ def group_stats(embeddings, groups=None, return_dist=True):
         stats["mean_vector_norm"][g] = np.float32(norms[k + 1])
     if not return_dist:
         return stats
-    gs = torch.from_numpy(dense[order].astype(np.int64)).to(x.device)
-    S = ops.pairdist_group_sums(xs, gs, G, torch.from_numpy(stats["mean_vector"]["full"]).to(x.device)).cpu().numpy()
     n = counts.astype(np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
         stats["pairwise_distance"]["full"] = 2.0 * np.triu(S).sum() / np.float64(N * (N - 1.0))
@@ -264,8 +321,8 @@ def pca(embeddings, groups=None, k=2, solver="host", tol=1e-10, max_iter=256):
     is launched."""
     if solver not in SOLVERS:
         raise ValueError(f"pca: solver = {solver!r}; one of {SOLVERS}")
-    x, g_np = _rows_and_groups(embeddings, groups)
-    x = x.float().contiguous()
+    x, uniq, dense, counts = _labelled_rows("pca", embeddings, groups, min_labels=1)
+    x = _prepared(x)
     n = x.shape[0]
     if not 1 <= k <= min(x.shape[1], 8):
         raise ValueError(f"pca: k = {k} (1..8)")
@@ -286,7 +343,6 @@ def pca(embeddings, groups=None, k=2, solver="host", tol=1e-10, max_iter=256):
     if eig is not None:
         fit["eig"] = eig
     fit["coords"] = ops.project_rows(x, c_dev, torch.from_numpy(comp).to(x.device))
-    uniq, dense, counts = np.unique(g_np, return_inverse=True, return_counts=True)
     cent = _group_means(x, dense, counts, c_dev) @ comp.astype(np.float64).T
     fit["centroids"] = {"full": np.zeros(k, dtype=np.float64)}
     for i, g in enumerate(uniq):
@@ -297,9 +353,8 @@ def pca(embeddings, groups=None, k=2, solver="host", tol=1e-10, max_iter=256):
 def pca_project(fit, embeddings):
     """coordinates (device tensor [N, k]) of another split, or of transformed embeddings, in the frame of an existing `pca` fit"""
     x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
-    return ops.project_rows(x.float().contiguous(), torch.from_numpy(fit["mean"]).to(x.device), torch.from_numpy(fit["components"]).to(x.device))
+    _need_device(x)
+    return ops.project_rows(_prepared(x), torch.from_numpy(fit["mean"]).to(x.device), torch.from_numpy(fit["components"]).to(x.device))
 
 
 def sample_rows(n, num_data, seed=42, offset=0):
@@ -341,9 +396,6 @@ def projection_report(opt, train_table, val_table, test_table, transform=None, k
 # Cluster the embeddings of each class, train on the clusters as groups; and the report's open question in one number: does a
 # representation, before or after the adapter, separate the spurious attribute at all (cluster_agreement)?
 
-TRANSFORM_ROWS = 4096     # rows per batch of `transform`
-
-
 def kmeans_pp_rows(x, k, rng):
     """k-means++ (Arthur & Vassilvitskii 2007): the indices (numpy int64 [k]) of k rows of the device tensor x as start centres,
     drawn from `rng` (a numpy RandomState).  The first uniformly; each further one by D^2 sampling from dmin of ops.kmeans_assign
@@ -378,16 +430,13 @@ def kmeans(embeddings, k, init="k-means++", seed=0, n_init=1, max_iter=100, tran
     'iterations', 'converged'}; the clusters are renumbered by size, descending (size_order), so cluster 0 is the majority.  A fit
     that reaches max_iter reports converged False; nothing is raised."""
     x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+    _need_device(x)
     k, n_init = int(k), int(n_init)
     if not 1 <= k <= ops.KMEANS_MAX_K:
         raise ValueError(f"kmeans: k = {k} (1..{ops.KMEANS_MAX_K})")
     if x.shape[0] < k:
         raise ValueError(f"kmeans: {x.shape[0]} rows for {k} clusters")
-    x = x.float().contiguous()
-    if transform is not None:
-        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
+    x = _prepared(x, transform)
     best = None
     if isinstance(init, str):
         if init != "k-means++" or n_init < 1:
@@ -509,24 +558,9 @@ def silhouette(embeddings, labels=None, transform=None):
     {'samples': float64 [N], 'score': their mean, 'per_label': {label: mean of its rows}, 'a', 'b': float64 [N] (the mean distance
     to the row's own label and to the nearest other one), 'nearest': [N], the nearest other label of every row (a value of
     `labels`), 'labels': the unique labels, 'counts'}.  The conventions are silhouette_from_sums'."""
-    x, l_np = _rows_and_groups(embeddings, labels)
-    uniq, dense, counts = np.unique(l_np, return_inverse=True, return_counts=True)
-    G, N = len(uniq), x.shape[0]
-    if G > ops.PAIRDIST_ROWS_MAX_G:
-        raise ops.DbmmUnsupported(f"silhouette: {G} labels; the distance kernel sums at most {ops.PAIRDIST_ROWS_MAX_G}")
-    if G < 2:
-        raise ValueError(f"a silhouette needs at least two labels with rows, got {G}")
-    x = x.float().contiguous()
-    if transform is not None:
-        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
-    dense = dense.reshape(-1)
-    order = np.argsort(dense, kind="stable")
-    xs = ops.gather_rows(x, torch.from_numpy(order).to(x.device))
-    center = torch.from_numpy((_column_sums(xs) / N).astype(np.float32)).to(x.device)
-    gs = torch.from_numpy(dense[order].astype(np.int64)).to(x.device)
-    sorted_sums = ops.pairdist_row_group_sums(xs, gs, G, center).cpu().numpy()
-    R = np.empty_like(sorted_sums)
-    R[order] = sorted_sums
+    x, uniq, dense, counts = _labelled_rows("silhouette", embeddings, labels, ops.PAIRDIST_ROWS_MAX_G)
+    G = len(uniq)
+    R, _ = _sorted_pass(_prepared(x, transform), dense, lambda xs, ids, center: ops.pairdist_row_group_sums(xs, ids, G, center), per_row=True)
     out = silhouette_from_sums(R, dense, counts)
     s = out["samples"]
     return {"samples": s, "score": float(s.mean()), "per_label": {lab: float(s[dense == i].mean()) for i, lab in enumerate(uniq)},
@@ -535,10 +569,8 @@ def silhouette(embeddings, labels=None, transform=None):
 
 def _device_rows(embeddings, transform):
     x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
-    x = x.float().contiguous()
-    return x if transform is None else _transformed_rows(x, transform, TRANSFORM_ROWS)
+    _need_device(x)
+    return _prepared(x, transform)
 
 
 def kmeans_select_k(embeddings, ks=(2, 3, 4, 5, 6, 7, 8), transform=None, **kmeans_kw):
@@ -694,26 +726,30 @@ def mmd(embeddings, groups=None, gammas=None, scales=RBF_SCALES, transform=None,
     Returns mmd_from_sums' dict (indexed by the labels in np.unique order) plus 'hsic': [L] (hsic_from_sums), 'gammas', 'labels',
     'counts'.  The kernel's precondition for its 1e-4 bound is gamma (|a|^2 + |b|^2) <= 64 for centred rows a, b: the default
     ladder's largest gamma, 4 / m, keeps it as long as no row lies more than 4 root-mean-square radii from the centre (m is twice the mean squared radius)."""
-    x, g_np = _rows_and_groups(embeddings, groups)
-    uniq, dense, counts = np.unique(g_np, return_inverse=True, return_counts=True)
-    G, N = len(uniq), x.shape[0]
-    if G > 8:
-        raise ops.DbmmUnsupported(f"mmd: {G} labels; the kernel buckets at most 8")
-    if G < 2:
-        raise ValueError(f"mmd needs at least two labels with rows, got {G}")
-    x = x.float().contiguous()
-    if transform is not None:
-        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
-    gammas = rbf_gammas(x, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
-    dense = dense.reshape(-1)
-    order = np.argsort(dense, kind="stable")
-    xs = ops.gather_rows(x, torch.from_numpy(order).to(x.device))
-    center = torch.from_numpy((_column_sums(xs) / N).astype(np.float32)).to(x.device)
-    gs = torch.from_numpy(dense[order].astype(np.int64)).to(x.device)
-    K = ops.pairdist_rbf_group_sums(xs, gs, G, center, gammas.tolist()).cpu().numpy()
+    x, uniq, dense, counts = _labelled_rows("mmd", embeddings, groups, 8)
+    G = len(uniq)
+    x = _prepared(x, transform)
+    gammas = _resolved_gammas(x, gammas, scales)
+    K, _ = _sorted_pass(x, dense, lambda xs, ids, center: ops.pairdist_rbf_group_sums(xs, ids, G, center, gammas.tolist()))
     out = mmd_from_sums(K, counts, unbiased=unbiased)
     out.update(hsic=hsic_from_sums(K, counts), gammas=gammas, labels=uniq, counts=counts)
     return out
+
+
+def _pooled_pair(what, embeddings, groups, pair, transform):
+    """The rows of the two labels in `pair`, pooled: (their indices in the input, the rows -- one gather, `transform` applied once --,
+    their labels 0 / 1 for pair[0] / pair[1] in row order).  One label named twice, or fewer than two rows of either: ValueError."""
+    x, uniq, dense, _ = _labelled_rows(what, embeddings, groups, min_labels=1)
+    g_np = uniq[dense]
+    a, b = pair
+    if a == b:
+        raise ValueError(f"{what}: pair = {pair!r} names one label twice")
+    idx = np.flatnonzero((g_np == a) | (g_np == b))
+    labels = (g_np[idx] == b).astype(np.int64)
+    if labels.sum() < 2 or (1 - labels).sum() < 2:
+        raise ValueError(f"{what}: labels {a!r} and {b!r} need at least two rows each")
+    xp = ops.gather_rows(_prepared(x), torch.from_numpy(idx).to(x.device))
+    return idx, xp if transform is None else _transformed_rows(xp, transform, TRANSFORM_ROWS), labels
 
 
 def mmd_permutation_test(embeddings, groups, pair, n_perm=20, seed=0, **mmd_kw):
@@ -723,21 +759,8 @@ def mmd_permutation_test(embeddings, groups, pair, n_perm=20, seed=0, **mmd_kw):
     permutation in order, labels the pooled rows' 0 / 1 (pair[0] / pair[1]) in row order; each is one `mmd` call (rows re-sorted by
     the new labels, so the kernel's fast path holds).  Returns {'stat', 'null': float64 [n_perm], 'p': (1 + #{null >= stat}) /
     (1 + n_perm)}.  The cost is n_perm + 1 passes of the kernel over the pooled rows."""
-    x, g_np = _rows_and_groups(embeddings, groups)
-    a, b = pair
-    if a == b:
-        raise ValueError(f"mmd_permutation_test: pair = {pair!r} names one label twice")
-    idx = np.flatnonzero((g_np == a) | (g_np == b))
-    labels = (g_np[idx] == b).astype(np.int64)
-    if labels.sum() < 2 or (1 - labels).sum() < 2:
-        raise ValueError(f"mmd_permutation_test: labels {a!r} and {b!r} need at least two rows each")
-    transform = mmd_kw.pop("transform", None)
-    scales = mmd_kw.pop("scales", RBF_SCALES)
-    gammas = mmd_kw.pop("gammas", None)
-    xp = ops.gather_rows(x.float().contiguous(), torch.from_numpy(idx).to(x.device))
-    if transform is not None:
-        xp = _transformed_rows(xp, transform, TRANSFORM_ROWS)
-    gammas = rbf_gammas(xp, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    _, xp, labels = _pooled_pair("mmd_permutation_test", embeddings, groups, pair, mmd_kw.pop("transform", None))
+    gammas = _resolved_gammas(xp, mmd_kw.pop("gammas", None), mmd_kw.pop("scales", RBF_SCALES))
     stat = float(mmd(xp, labels, gammas=gammas, **mmd_kw)["mmd2_sum"][0, 1])
     rng = np.random.default_rng(seed)
     null = np.array([mmd(xp, labels[rng.permutation(len(labels))], gammas=gammas, **mmd_kw)["mmd2_sum"][0, 1] for _ in range(n_perm)],
@@ -886,48 +909,10 @@ def alignment_from_sums(K, K2_total, row_sq, counts):
     return {"alignment": alignment, "hsic": hsic, "hsic_kk": hsic_kk, "hsic_ll": float(hsic_ll), "rel_bound": rel_bound}
 
 
-def _labelled_rows(what, embeddings, labels, max_labels, device=True):
-    """(x, unique labels, dense ids [N], counts): the labels are counted and refused BEFORE the rows are looked at (more than
-    `max_labels`: DbmmUnsupported, fewer than two: ValueError), the rows must be device-resident (device=False leaves that check
-    to a caller that has refusals of its own to make first)"""
-    if isinstance(embeddings, trainer.EmbeddingTable):
-        x = embeddings.embeddings
-        labels = embeddings.targets_group if labels is None else labels
-    else:
-        x = embeddings
-    if labels is None:
-        raise ValueError(f"{what}: a device tensor of embeddings needs its `labels` array")
-    if not torch.is_tensor(x) or x.dim() != 2:
-        raise ValueError(f"{what}: the rows must be an EmbeddingTable or a tensor [N, D]")
-    l_np = (labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)).ravel()
-    if l_np.shape[0] != x.shape[0]:
-        raise ValueError(f"{what}: {l_np.shape[0]} labels for {x.shape[0]} rows")
-    uniq, dense, counts = np.unique(l_np, return_inverse=True, return_counts=True)
-    if len(uniq) > max_labels:
-        raise ops.DbmmUnsupported(f"{what}: {len(uniq)} labels; the kernel sums at most {max_labels}")
-    if len(uniq) < 2:
-        raise ValueError(f"{what} needs at least two labels with rows, got {len(uniq)}")
-    if device and not x.is_cuda:
-        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
-    return x, uniq, dense.reshape(-1).astype(np.int64), counts
-
-
 def _sorted_row_sums(x, dense, G, gammas, extra=None):
-    """ops.pairdist_rbf_row_group_sums of the rows x sorted by their dense label (one gather; nearly every tile of the kernel then
-    holds one label), followed by the rows `extra` with label -1, centred on the mean of what is passed; R float64 [L, N (+ M), G] on
-    the host in the INPUT's row order, x's rows first"""
-    order = np.argsort(dense, kind="stable")
-    gs = dense[order]
-    if extra is not None:
-        order = np.concatenate([order, x.shape[0] + np.arange(extra.shape[0], dtype=np.int64)])
-        gs = np.concatenate([gs, np.full(extra.shape[0], -1, dtype=np.int64)])
-        x = torch.cat([x, extra])
-    xs = ops.gather_rows(x, torch.from_numpy(order).to(x.device))
-    center = torch.from_numpy((_column_sums(xs) / xs.shape[0]).astype(np.float32)).to(x.device)
-    Rs = ops.pairdist_rbf_row_group_sums(xs, torch.from_numpy(gs).to(x.device), G, center, np.asarray(gammas, dtype=np.float64).tolist()).cpu().numpy()
-    R = np.empty_like(Rs)
-    R[:, order] = Rs
-    return R
+    """_sorted_pass of ops.pairdist_rbf_row_group_sums: R float64 [L, N (+ M), G] on the host in the INPUT's row order, x's rows first"""
+    return _sorted_pass(x, dense, lambda xs, ids, center: ops.pairdist_rbf_row_group_sums(xs, ids, G, center, np.asarray(gammas, dtype=np.float64).tolist()),
+                        per_row=True, extra=extra)[0]
 
 
 def _probe_scores(pred, true, G):
@@ -971,7 +956,7 @@ def kernel_probe(embeddings, labels=None, gammas=None, scales=RBF_SCALES, transf
         raise ValueError(f"kernel_probe: prior = {prior!r}; 'uniform' or 'empirical'")
     if query is not None and labels is None and not isinstance(embeddings, trainer.EmbeddingTable):
         raise ValueError("kernel_probe: `query` rows are scored against labelled reference rows; give `labels`")
-    x, uniq, dense, counts = _labelled_rows("kernel_probe", embeddings, labels, ops.PAIRDIST_ROWS_MAX_G)
+    x, uniq, dense, counts = _labelled_rows("kernel_probe", embeddings, labels, ops.PAIRDIST_ROWS_MAX_G, device="last")
     G, N = len(uniq), x.shape[0]
     true = dense
     if query is not None:
@@ -984,15 +969,9 @@ def kernel_probe(embeddings, labels=None, gammas=None, scales=RBF_SCALES, transf
             if q_np.shape[0] != query.shape[0] or not np.array_equal(uniq[pos], q_np):
                 raise ValueError("kernel_probe: query_labels must be one value of `labels` per query row")
             true = pos.astype(np.int64)
-    x = x.float().contiguous()
-    if transform is not None:
-        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
-    q = None
-    if query is not None:
-        q = query.float().contiguous()
-        if transform is not None:
-            q = _transformed_rows(q, transform, TRANSFORM_ROWS)
-    gammas = rbf_gammas(x, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    x = _prepared(x, transform)
+    q = None if query is None else _prepared(query, transform)
+    gammas = _resolved_gammas(x, gammas, scales)
     R = _sorted_row_sums(x, dense, G, gammas, extra=q)
     if q is None:
         fit = parzen_from_sums(R, dense, counts, prior)
@@ -1015,18 +994,8 @@ def mmd_witness(embeddings, groups, pair, top_k=8, gammas=None, scales=RBF_SCALE
     top_k rows with the largest and with the smallest witness (the most typical rows of pair[0] and of pair[1]; the lower index
     first on a tie), 'mmd2': [L], the unbiased MMD^2 by the identity mean over pair[0]'s rows - mean over pair[1]'s rows,
     'gammas'}."""
-    x, g_np = _rows_and_groups(embeddings, groups)
-    a, b = pair
-    if a == b:
-        raise ValueError(f"mmd_witness: pair = {pair!r} names one label twice")
-    idx = np.flatnonzero((g_np == a) | (g_np == b))
-    lab = (g_np[idx] == b).astype(np.int64)
-    if lab.sum() < 2 or (1 - lab).sum() < 2:
-        raise ValueError(f"mmd_witness: labels {a!r} and {b!r} need at least two rows each")
-    xp = ops.gather_rows(x.float().contiguous(), torch.from_numpy(idx).to(x.device))
-    if transform is not None:
-        xp = _transformed_rows(xp, transform, TRANSFORM_ROWS)
-    gammas = rbf_gammas(xp, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    idx, xp, lab = _pooled_pair("mmd_witness", embeddings, groups, pair, transform)
+    gammas = _resolved_gammas(xp, gammas, scales)
     counts = np.bincount(lab, minlength=2)
     w = witness_from_sums(_sorted_row_sums(xp, lab, 2, gammas), lab, counts, 0, 1)
     k = max(0, min(int(top_k), len(idx)))
@@ -1046,12 +1015,10 @@ def kernel_alignment(embeddings, labels=None, gammas=None, scales=RBF_SCALES, tr
     2 gamma with a single label (only the total of k^2 is needed; that pass walks half the tiles).  Returns alignment_from_sums'
     dict plus 'gammas', 'labels', 'counts'.  Because the second pass runs at 2 gamma the kernels' preconditions are halved:
     2 gamma_max max d^2 <= 80 and 2 gamma_max (|a|^2 + |b|^2) <= 64 for centred rows a, b.  Read 'rel_bound' with 'alignment'."""
-    x, uniq, dense, counts = _labelled_rows("kernel_alignment", embeddings, labels, ops.PAIRDIST_ROWS_MAX_G)
+    x, uniq, dense, counts = _labelled_rows("kernel_alignment", embeddings, labels, ops.PAIRDIST_ROWS_MAX_G, device="last")
     G, N = len(uniq), x.shape[0]
-    x = x.float().contiguous()
-    if transform is not None:
-        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
-    gammas = rbf_gammas(x, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    x = _prepared(x, transform)
+    gammas = _resolved_gammas(x, gammas, scales)
     R = _sorted_row_sums(x, dense, G, gammas)
     S = np.stack([R[:, dense == a].sum(1) for a in range(G)], axis=1)            # [L, G, G]: ordered pairs, row in a, column in b
     K = 0.5 * (S + S.transpose(0, 2, 1))
@@ -1207,15 +1174,12 @@ def kernel_ridge_fit(embeddings, labels=None, gammas=None, scales=RBF_SCALES, la
     recurrence reached `tol` within `max_iter`; non-convergence is reported, never raised --, 'transform', 'tol'}.  In the
     float64 study of this function CG took 5 - 50 iterations at lam in {0.1, 1} and up to 210 at lam = 1e-3."""
     lams = _ridge_lams("kernel_ridge_fit", lams, None)
-    x, uniq, dense, counts = _labelled_rows("kernel_ridge_fit", embeddings, labels, RIDGE_MAX_COLUMNS, device=False)
+    x, uniq, dense, counts = _labelled_rows("kernel_ridge_fit", embeddings, labels, RIDGE_MAX_COLUMNS, device=None)
     G = len(uniq)
     _ridge_lams("kernel_ridge_fit", lams, G)
-    if not x.is_cuda:
-        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
-    x = x.float().contiguous()
-    if transform is not None:
-        x = _transformed_rows(x, transform, TRANSFORM_ROWS)
-    gammas = rbf_gammas(x, scales) if gammas is None else np.asarray(gammas, dtype=np.float64).ravel()
+    _need_device(x)
+    x = _prepared(x, transform)
+    gammas = _resolved_gammas(x, gammas, scales)
     if gammas.size == 0 or not (np.isfinite(gammas).all() and (gammas > 0).all()):
         raise ValueError(f"kernel_ridge_fit: gammas = {gammas.tolist()}; at least one bandwidth, every one finite and > 0")
     center = torch.from_numpy((_column_sums(x) / x.shape[0]).astype(np.float32)).to(x.device)
@@ -1249,9 +1213,7 @@ def kernel_ridge_predict(fit, query):
     x = fit["rows"]
     if not torch.is_tensor(query) or not query.is_cuda or query.dim() != 2 or query.shape[0] < 1:
         raise ValueError("kernel_ridge_predict: query must be a device tensor [M, D]")
-    q = query.float().contiguous()
-    if fit["transform"] is not None:
-        q = _transformed_rows(q, fit["transform"], TRANSFORM_ROWS)
+    q = _prepared(query, fit["transform"])
     if q.shape[1] != x.shape[1]:
         raise ValueError(f"kernel_ridge_predict: query rows have {q.shape[1]} columns, the fit's {x.shape[1]}")
     rows = torch.cat([x, q])
@@ -1300,14 +1262,12 @@ def kernel_ridge_probe(embeddings, labels=None, query=None, query_labels=None, h
     if query is None:
         if not (isinstance(holdout, (int, float)) and 0.0 < holdout < 1.0):
             raise ValueError(f"kernel_ridge_probe: holdout = {holdout!r}; a share in (0, 1)")
-        x, _, dense, _ = _labelled_rows("kernel_ridge_probe", embeddings, labels, RIDGE_MAX_COLUMNS, device=False)
-        l_np = (embeddings.targets_group if labels is None else labels) if isinstance(embeddings, trainer.EmbeddingTable) else labels
-        l_np = (l_np.detach().cpu().numpy() if torch.is_tensor(l_np) else np.asarray(l_np)).ravel()
-        _ridge_lams("kernel_ridge_probe", fit_kw.get("lams", RIDGE_LAMS), len(np.unique(dense)))
-        if not x.is_cuda:
-            raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
+        x, uniq, dense, _ = _labelled_rows("kernel_ridge_probe", embeddings, labels, RIDGE_MAX_COLUMNS, device=None)
+        l_np = uniq[dense]
+        _ridge_lams("kernel_ridge_probe", fit_kw.get("lams", RIDGE_LAMS), len(uniq))
+        _need_device(x)
         keep, held = stratified_holdout(dense, holdout, seed)
-        x = x.float().contiguous()
+        x = _prepared(x)
         fit = kernel_ridge_fit(ops.gather_rows(x, torch.from_numpy(keep).to(x.device)), l_np[keep], **fit_kw)
         query, query_labels = ops.gather_rows(x, torch.from_numpy(held).to(x.device)), l_np[held]
     else:
@@ -1494,7 +1454,8 @@ def erasure_fit(embeddings, labels=None, method="leace", rows=None, transform=No
         raise ValueError(f"erasure: method = {method!r}; one of {ERASURE_METHODS}")
     if isinstance(embeddings, trainer.EmbeddingTable) and labels is None:
         labels = embeddings.targets_spurious
-    x, l_np = _rows_and_groups(embeddings, labels)
+    x, uniq, dense, _ = _labelled_rows("erasure_fit", embeddings, labels, min_labels=1)
+    l_np = uniq[dense]
     if rows is not None:
         rows = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows).astype(np.int64).ravel()
         if rows.size == 0 or rows.min() < 0 or rows.max() >= x.shape[0]:
@@ -1506,7 +1467,7 @@ def erasure_fit(embeddings, labels=None, method="leace", rows=None, transform=No
         raise ValueError(f"erasure_fit: {G} labels; at most {ERASURE_MAX_LABELS}")
     if l_np.shape[0] < 2:
         raise ValueError(f"erasure needs at least two rows, got {l_np.shape[0]}")
-    x = x.float().contiguous()
+    x = _prepared(x)
     if rows is not None:
         x = ops.gather_rows(x, torch.from_numpy(rows).to(x.device))
     if transform is not None:
@@ -1526,9 +1487,8 @@ def erase(fit, embeddings, out=None):
     kernel (ops.erase_rows: one read, one write, nothing else allocated): a device tensor [N, D], or `out` -- which may be the
     input tensor itself: in place.  Rank 0 returns a copy (or `out` filled with the rows) and launches no kernel of ours."""
     x = embeddings.embeddings if isinstance(embeddings, trainer.EmbeddingTable) else embeddings
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise ops._lib.DbmmError("analysis works on device-resident embeddings (an EmbeddingTable or a HIP tensor); there is no CPU path")
-    x = x.float().contiguous()
+    _need_device(x)
+    x = _prepared(x)
     if fit["rank"] == 0:
         if out is None:
             return x.clone()

@@ -153,6 +153,31 @@ struct RbfMatvecMap : RbfMap {
     using RowsP = PairRowsMatvecP;
 };
 
+// Two statements of both tile kernels, stated once -- as text, not as functions: each was tried as a lambda and as a __forceinline__
+// helper, and every form moved the register allocation around the ring (the rows kernel has two registers to spare there).
+// The stager's lane offsets of thread t for the tile at (m0, n0), per half-tile kind (Ah0, Bh0, Bh1, Ah1); rows >= N masked.  In scope: voff,
+// m0, n0, p
+#define PAIRDIST_LANE_OFFSETS(t)                                                                                    \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                 \
+        _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                                             \
+            int ra, rw;                                                                                             \
+            unsigned cb;                                                                                            \
+            ring_rows(t, i, h, ra, rw, cb);                                                                         \
+            voff[h ? 3 : 0][i] = m0 + ra < p.N ? (unsigned)ra * (unsigned)(p.ldp * 2) + cb : OOR;                   \
+            voff[h ? 2 : 1][i] = n0 + rw < p.N ? (unsigned)rw * (unsigned)(p.ldp * 2) + cb : OOR;                   \
+        }                                                                                                           \
+    }
+// The accumulators -> Map::pre(d^2) in place, d^2 = |a|^2 + |b|^2 - 2 a.b clamped at 0.  In scope: acc, e_norm (the tile's row norms, then
+// its column norms), wm0, c0 (the lane's first column), fh; defines cn0, cn1
+#define PAIRDIST_ACC_TO_D2()                                                                                        \
+    const float cn0 = e_norm[256 + c0], cn1 = e_norm[256 + c0 + 1];                                                 \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                            \
+            const float rn = e_norm[wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh];                                \
+            acc[i][0][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][0][r], rn + cn0), 0.f));                                \
+            acc[i][1][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][1][r], rn + cn1), 0.f));                                \
+        }
+
 template <class Map>
 __global__ __launch_bounds__(512, 1) void pairdist_tile_kernel(const PairDistP p) {
     __shared__ __attribute__((aligned(1024))) unsigned char lds[8 * PH_HALF];      // [buffer 2][Ah0, Bh0, Bh1, Ah1] = 128 KB
@@ -180,28 +205,9 @@ __global__ __launch_bounds__(512, 1) void pairdist_tile_kernel(const PairDistP p
         m0 = bi * 256; n0 = bj * 256;
         rsA = desc(p.P, p.p_total, (long long)m0 * p.ldp * 2);
         rsW = desc(p.P, p.p_total, (long long)n0 * p.ldp * 2);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                int ra, rw;
-                unsigned cb;
-                ring_rows(tid, i, h, ra, rw, cb);
-                voff[h ? 3 : 0][i] = m0 + ra < p.N ? (unsigned)ra * (unsigned)(p.ldp * 2) + cb : OOR;
-                voff[h ? 2 : 1][i] = n0 + rw < p.N ? (unsigned)rw * (unsigned)(p.ldp * 2) + cb : OOR;
-            }
-        }
+        PAIRDIST_LANE_OFFSETS(tid);
     };
-    const int nT = 3 * p.T;                                          // K tiles of the three products: hi.hi, hi.lo, lo.hi
-    // K tile t of half-tile kind `kind`: its K tile inside P's row (hi | lo); tiles past the end go through the zero-extent descriptor
-    auto ring_src = [&](int kind, int t, __amdgpu_buffer_rsrc_t& rs, unsigned (&vo)[2], unsigned& so) {
-        const bool isA = kind == 0 || kind == 3, valid = t < nT;
-        rs = valid ? (isA ? rsA : rsW) : rs0;
-        const int kt = isA ? (t < p.T ? t : t - p.T) : (t < 2 * p.T ? t : t - 2 * p.T);
-        vo[0] = voff[kind][0]; vo[1] = voff[kind][1];
-        so = (unsigned)kt * 128u;
-    };
-#include "fp16_ring.inc"
+#include "pairdist_ring.inc"
 
     const int n_items = walk.n_whole;
     const int wm0 = wr * 128, wn0 = wc * 64;
@@ -230,15 +236,7 @@ __global__ __launch_bounds__(512, 1) void pairdist_tile_kernel(const PairDistP p
         const bool diag = em0 == en0;
         const bool fast = !diag && em0 + 256 <= p.N && en0 + 256 <= p.N && __builtin_popcount(mA) == 1 && __builtin_popcount(mB) == 1;
         const int c0 = wn0 + 2 * fr;
-        const float cn0 = e_norm[256 + c0], cn1 = e_norm[256 + c0 + 1];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float rn = e_norm[wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh];
-                acc[i][0][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][0][r], rn + cn0), 0.f));
-                acc[i][1][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][1][r], rn + cn1), 0.f));
-            }
+        PAIRDIST_ACC_TO_D2();
         // one reduction per sum l, the same whatever nl is: l outside the lane's 128 elements, no second copy of the tile
 #pragma unroll 1
         for (int l = 0; l < nl; ++l) {
@@ -308,36 +306,72 @@ __global__ __launch_bounds__(64) void pairdist_fold_kernel(const double* __restr
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline long long padded_dim(long long D) { return (D + 127) / 128 * 128; }
 
-// the workspace of a bucket pass with L sums per bucket: head, RowInfo, planes, the workgroups' partials
-inline size_t bucket_workspace_bytes(int64_t N, int64_t D, int64_t L) {
-    const size_t Dp = (size_t)padded_dim(D);
-    return HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256) + align_up((size_t)N * 2 * Dp * 2, 256) + (size_t)MAX_WG * (size_t)L * 64 * sizeof(double);
+// The workspace of every pass: the head, RowInfo, the planes, then the pass's partials (part_bytes of them); byte offsets and the total
+struct Layout { size_t info, planes, part, total; };
+inline Layout layout(int64_t N, int64_t D, size_t part_bytes) {
+    Layout w;
+    w.info = HEAD_BYTES;
+    w.planes = w.info + align_up((size_t)N * sizeof(RowInfo), 256);
+    w.part = w.planes + align_up((size_t)N * 2 * (size_t)padded_dim(D) * 2, 256);
+    w.total = w.part + part_bytes;
+    return w;
 }
 
-// absmax, split, tiles, fold for one element map; the operands have been checked.  gammas: RbfMap's L bandwidths (host), else null and L = 1
-template <class Map>
-int bucket_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums, int64_t N, int64_t D, int64_t G,
-                void* workspace, void* stream) {
+// the partials of a bucket pass with L sums per bucket: 64 buckets per workgroup and sum
+inline size_t bucket_workspace_bytes(int64_t N, int64_t D, int64_t L) { return layout(N, D, (size_t)MAX_WG * (size_t)L * 64 * sizeof(double)).total; }
+
+// The operand check of every public entry, in the order the callers rely on: shape, unsupported width, null, gamma, alignment, workspace.
+// cap: the entry's most labels or weight columns G; groups / gammas / v: checked where the entry takes them (`takes`), gammas being L host
+// values; required: the entry's workspace size for this request
+enum : unsigned { TAKES_GROUPS = 1, TAKES_GAMMAS = 2, TAKES_V = 4 };
+int check_operands(unsigned takes, int64_t cap, const float* x, const int64_t* groups, const float* v, const float* center, const double* gammas, int64_t L,
+                   const double* sums, int64_t N, int64_t D, int64_t G, const void* workspace, size_t workspace_bytes, size_t required) {
+    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > cap || L < 1 || L > RBF_MAX_L) return DBMM_E_SHAPE;
+    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
+    if (!x || !center || !sums || !workspace) return DBMM_E_ARG;
+    if (((takes & TAKES_GROUPS) && !groups) || ((takes & TAKES_GAMMAS) && !gammas) || ((takes & TAKES_V) && !v)) return DBMM_E_ARG;
+    for (int l = 0; (takes & TAKES_GAMMAS) && l < L; ++l)
+        if (!(gammas[l] > 0.0) || !(gammas[l] <= 1.79769313486231570e308)) return DBMM_E_ARG;      // finite and positive
+    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace) || ((takes & TAKES_V) && !dbmm_aligned16(v))) return DBMM_E_ALIGN;
+    if (workspace_bytes < required) return DBMM_E_WORKSPACE;
+    return DBMM_OK;
+}
+
+// The start of every pass; the operands have been checked.  The head of the workspace zeroed, absmax, split (LABELS: it records groups[row],
+// the bucket kernel's labels), and the parameter fields both tile kernels have; amax: the head, the split's centred absmax
+template <bool LABELS, class Params>
+int prepare(Params& p, unsigned*& amax, const float* x, const int64_t* groups, const float* center, int64_t N, int64_t D, int64_t G, void* workspace,
+            hipStream_t s) {
     const long long Dp = padded_dim(D);
+    const Layout w = layout(N, D, 0);
     char* ws = (char*)workspace;
-    unsigned* amax = (unsigned*)ws;
-    RowInfo* info = (RowInfo*)(ws + HEAD_BYTES);
-    u16* P = (u16*)(ws + HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256));
-    double* part = (double*)((char*)P + align_up((size_t)N * 2 * Dp * 2, 256));
-    hipStream_t s = (hipStream_t)stream;
+    amax = (unsigned*)ws;
+    RowInfo* info = (RowInfo*)(ws + w.info);
+    u16* P = (u16*)(ws + w.planes);
     hipError_t e = hipMemsetAsync(amax, 0, HEAD_BYTES, s);
     if (e != hipSuccess) return (int)e;
     const long long n4 = N * D / 4;
     const int g1 = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
     hipLaunchKernelGGL(pairdist_absmax_kernel, dim3(g1), dim3(256), 0, s, x, center, n4, (int)(D / 4), amax);
     DBMM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pairdist_split_kernel<true>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
+    hipLaunchKernelGGL(pairdist_split_kernel<LABELS>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
                        (int)G);
     DBMM_CHECK_LAUNCH();
-    PairDistP p{};
-    p.P = P; p.info = info; p.part = part;
+    p.P = P; p.info = info; p.part = (double*)(ws + w.part);
     p.ldp = 2 * Dp; p.p_total = (long long)N * 2 * Dp * 2;
     p.N = (int)N; p.T = (int)(Dp / 64); p.nb = (int)((N + 255) / 256);
+    return DBMM_OK;
+}
+
+// prepare, tiles, fold for one element map; the operands have been checked.  gammas: RbfMap's L bandwidths (host), else null and L = 1
+template <class Map>
+int bucket_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums, int64_t N, int64_t D, int64_t G,
+                void* workspace, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    PairDistP p{};
+    unsigned* amax;
+    const int rc = prepare<true>(p, amax, x, groups, center, N, D, G, workspace, s);
+    if (rc != DBMM_OK) return rc;
     p.amax_bits = amax; p.L = (int)L;
     for (int l = 0; gammas && l < L; ++l) p.gamma[l] = gammas[l];
     const long long nt = (long long)p.nb * (p.nb + 1) / 2;
@@ -345,7 +379,7 @@ int bucket_sums(const float* x, const int64_t* groups, const float* center, cons
     const int grid = nt < MAX_WG ? (int)nt : MAX_WG;
     hipLaunchKernelGGL(pairdist_tile_kernel<Map>, dim3(grid), dim3(512), 0, s, p);
     DBMM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pairdist_fold_kernel, dim3((unsigned)L), dim3(64), 0, s, part, grid, Map::SCALED ? amax : (const unsigned*)nullptr, (int)G, sums);
+    hipLaunchKernelGGL(pairdist_fold_kernel, dim3((unsigned)L), dim3(64), 0, s, p.part, grid, Map::SCALED ? amax : (const unsigned*)nullptr, (int)G, sums);
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
 }
@@ -361,12 +395,9 @@ extern "C" size_t dbmm_workspace_bytes_pairdist(int64_t N, int64_t D) {
 // see include/dbmm.h
 extern "C" int dbmm_pairdist_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N, int64_t D,
                                         int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > 8) return DBMM_E_SHAPE;
-    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
-    if (!x || !groups || !center || !sums || !workspace) return DBMM_E_ARG;
-    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
-    if (workspace_bytes < dbmm_workspace_bytes_pairdist(N, D)) return DBMM_E_WORKSPACE;
-    return bucket_sums<DistanceMap>(x, groups, center, nullptr, 1, sums, N, D, G, workspace, stream);
+    const int rc = check_operands(TAKES_GROUPS, 8, x, groups, nullptr, center, nullptr, 1, sums, N, D, G, workspace, workspace_bytes,
+                                  bucket_workspace_bytes(N, D, 1));
+    return rc != DBMM_OK ? rc : bucket_sums<DistanceMap>(x, groups, center, nullptr, 1, sums, N, D, G, workspace, stream);
 }
 
 // see include/dbmm.h
@@ -378,14 +409,9 @@ extern "C" size_t dbmm_workspace_bytes_pairdist_rbf(int64_t N, int64_t D, int64_
 // see include/dbmm.h
 extern "C" int dbmm_pairdist_rbf_group_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums,
                                             int64_t N, int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > 8 || L < 1 || L > RBF_MAX_L) return DBMM_E_SHAPE;
-    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
-    if (!x || !groups || !center || !gammas || !sums || !workspace) return DBMM_E_ARG;
-    for (int l = 0; l < L; ++l)
-        if (!(gammas[l] > 0.0) || !(gammas[l] <= 1.79769313486231570e308)) return DBMM_E_ARG;      // finite and positive
-    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
-    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rbf(N, D, L)) return DBMM_E_WORKSPACE;
-    return bucket_sums<RbfMap>(x, groups, center, gammas, L, sums, N, D, G, workspace, stream);
+    const int rc = check_operands(TAKES_GROUPS | TAKES_GAMMAS, 8, x, groups, nullptr, center, gammas, L, sums, N, D, G, workspace, workspace_bytes,
+                                  bucket_workspace_bytes(N, D, L));
+    return rc != DBMM_OK ? rc : bucket_sums<RbfMap>(x, groups, center, gammas, L, sums, N, D, G, workspace, stream);
 }
 
 // ---- per-row, per-group sums: R[i][g] = sum over j != i with group[j] == g of ||x_i - x_j||_2, float64 [N][G] (the silhouette's input) -------
@@ -471,17 +497,7 @@ __global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const typena
         m0 = bi * 256; n0 = bj * 256;
         rsA = desc(p.P, p.p_total, (long long)m0 * p.ldp * 2);
         rsW = desc(p.P, p.p_total, (long long)n0 * p.ldp * 2);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                int ra, rw;
-                unsigned cb;
-                ring_rows(t, i, h, ra, rw, cb);
-                voff[h ? 3 : 0][i] = m0 + ra < p.N ? (unsigned)ra * (unsigned)(p.ldp * 2) + cb : OOR;
-                voff[h ? 2 : 1][i] = n0 + rw < p.N ? (unsigned)rw * (unsigned)(p.ldp * 2) + cb : OOR;
-            }
-        }
+        PAIRDIST_LANE_OFFSETS(t);
     };
     // unit number k of this workgroup -> its row block, chunk and column blocks [lo, hi)
     auto unit = [&](int k, int& bi, int& c, int& lo, int& hi) {
@@ -489,15 +505,7 @@ __global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const typena
         c = u / p.nb; bi = u - c * p.nb;
         lo = (int)((long long)c * p.nb / p.C); hi = (int)((long long)(c + 1) * p.nb / p.C);
     };
-    const int nT = 3 * p.T;                                          // K tiles of the three products: hi.hi, hi.lo, lo.hi
-    auto ring_src = [&](int kind, int t, __amdgpu_buffer_rsrc_t& rs, unsigned (&vo)[2], unsigned& so) {
-        const bool isA = kind == 0 || kind == 3, valid = t < nT;
-        rs = valid ? (isA ? rsA : rsW) : rs0;
-        const int kt = isA ? (t < p.T ? t : t - p.T) : (t < 2 * p.T ? t : t - 2 * p.T);
-        vo[0] = voff[kind][0]; vo[1] = voff[kind][1];
-        so = (unsigned)kt * 128u;
-    };
-#include "fp16_ring.inc"
+#include "pairdist_ring.inc"
 
     const int wm0 = wr * 128, wn0 = wc * 64;
     int k = 0, bi = 0, ch = 0, bj = 0, hi = 0, par = 0;
@@ -547,15 +555,7 @@ __global__ __launch_bounds__(512, 1) void pairdist_rows_tile_kernel(const typena
         const bool diag = em0 == en0;
         const bool fast = !diag && __builtin_popcount(mB) == 1 && mB < 0x10000u;
         const int c0 = wn0 + 2 * fr;
-        const float cn0 = e_norm[256 + c0], cn1 = e_norm[256 + c0 + 1];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float rn = e_norm[wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh];
-                acc[i][0][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][0][r], rn + cn0), 0.f));
-                acc[i][1][r] = Map::pre(fmaxf(fmaf(-2.f, acc[i][1][r], rn + cn1), 0.f));
-            }
+        PAIRDIST_ACC_TO_D2();
         if (diag) {                                                   // the pair (i, i) is in no sum: by index, whatever its value
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -681,40 +681,23 @@ inline int rows_chunks(long long nb) {
     return C;
 }
 
-// the workspace of a rows pass with L sums per (row, label): head, RowInfo, planes, the chunks' partials -- sized for 16 chunks whatever
-// rows_chunks picks: the size then grows with N
+// the partials of a rows pass with L sums per (row, label): sized for 16 chunks whatever rows_chunks picks: the size then grows with N
 inline size_t rows_workspace_bytes(int64_t N, int64_t D, int64_t G, int64_t L) {
-    const size_t Dp = (size_t)padded_dim(D);
-    return HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256) + align_up((size_t)N * 2 * Dp * 2, 256) +
-           (size_t)ROWS_MAX_CHUNKS * (size_t)L * (size_t)N * (size_t)G * sizeof(double);
+    return layout(N, D, (size_t)ROWS_MAX_CHUNKS * (size_t)L * (size_t)N * (size_t)G * sizeof(double)).total;
 }
 
-// absmax, split, tiles, fold for one element map; the operands have been checked.  gammas: RbfMap's L bandwidths (host), else null and L = 1;
+// prepare, tiles, fold for one element map; the operands have been checked.  gammas: RbfMap's L bandwidths (host), else null and L = 1;
 // v: RbfMatvecMap's weights [N][G], with groups null and L = 1
 template <class Map>
 int row_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums, int64_t N, int64_t D, int64_t G,
              void* workspace, void* stream, const float* v = nullptr) {
-    const long long Dp = padded_dim(D);
-    char* ws = (char*)workspace;
-    unsigned* amax = (unsigned*)ws;
-    RowInfo* info = (RowInfo*)(ws + HEAD_BYTES);
-    u16* P = (u16*)(ws + HEAD_BYTES + align_up((size_t)N * sizeof(RowInfo), 256));
-    double* part = (double*)((char*)P + align_up((size_t)N * 2 * Dp * 2, 256));
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(amax, 0, HEAD_BYTES, s);
-    if (e != hipSuccess) return (int)e;
-    const long long n4 = N * D / 4;
-    const int g1 = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(pairdist_absmax_kernel, dim3(g1), dim3(256), 0, s, x, center, n4, (int)(D / 4), amax);
-    DBMM_CHECK_LAUNCH();
-    // (the split's own group column is not read here: the tile kernel takes the labels from `groups`)
-    hipLaunchKernelGGL(pairdist_split_kernel<!Map::WEIGHTED>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, x, center, groups, amax, P, info, (int)N, (int)D, (int)Dp,
-                       (int)G);
-    DBMM_CHECK_LAUNCH();
     typename Map::RowsP p{};
-    p.P = P; p.info = info; p.groups = groups; p.part = part;
-    p.ldp = 2 * Dp; p.p_total = (long long)N * 2 * Dp * 2;
-    p.N = (int)N; p.T = (int)(Dp / 64); p.nb = (int)((N + 255) / 256); p.G = (int)G;
+    unsigned* amax;
+    // (the split's own group column is not read here: the tile kernel takes the labels from `groups`)
+    const int rc = prepare<!Map::WEIGHTED>(p, amax, x, groups, center, N, D, G, workspace, s);
+    if (rc != DBMM_OK) return rc;
+    p.groups = groups; p.G = (int)G;
     p.C = rows_chunks(p.nb);
     p.n_units = p.nb * p.C;
     if constexpr (!Map::SCALED) {
@@ -723,12 +706,12 @@ int row_sums(const float* x, const int64_t* groups, const float* center, const d
     }
     if constexpr (Map::WEIGHTED) p.v = v;
     const long long n_out = L * N * G;
-    e = hipMemsetAsync(part, 0, (size_t)p.C * (size_t)n_out * sizeof(double), s);            // the units' running sums start at zero
+    hipError_t e = hipMemsetAsync(p.part, 0, (size_t)p.C * (size_t)n_out * sizeof(double), s);  // the units' running sums start at zero
     if (e != hipSuccess) return (int)e;
     const int grid = p.n_units < MAX_WG ? p.n_units : MAX_WG;
     hipLaunchKernelGGL(pairdist_rows_tile_kernel<Map>, dim3(grid), dim3(512), 0, s, p);
     DBMM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pairdist_rows_fold_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, part, p.C, n_out,
+    hipLaunchKernelGGL(pairdist_rows_fold_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, p.part, p.C, n_out,
                        Map::SCALED ? amax : (const unsigned*)nullptr, sums);
     DBMM_CHECK_LAUNCH();
     return DBMM_OK;
@@ -745,12 +728,9 @@ extern "C" size_t dbmm_workspace_bytes_pairdist_rows(int64_t N, int64_t D, int64
 // see include/dbmm.h
 extern "C" int dbmm_pairdist_row_group_sums(const float* x, const int64_t* groups, const float* center, double* sums, int64_t N, int64_t D,
                                             int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > ROWS_MAX_G) return DBMM_E_SHAPE;
-    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
-    if (!x || !groups || !center || !sums || !workspace) return DBMM_E_ARG;
-    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
-    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rows(N, D, G)) return DBMM_E_WORKSPACE;
-    return row_sums<DistanceMap>(x, groups, center, nullptr, 1, sums, N, D, G, workspace, stream);
+    const int rc = check_operands(TAKES_GROUPS, ROWS_MAX_G, x, groups, nullptr, center, nullptr, 1, sums, N, D, G, workspace, workspace_bytes,
+                                  rows_workspace_bytes(N, D, G, 1));
+    return rc != DBMM_OK ? rc : row_sums<DistanceMap>(x, groups, center, nullptr, 1, sums, N, D, G, workspace, stream);
 }
 
 // see include/dbmm.h
@@ -762,14 +742,9 @@ extern "C" size_t dbmm_workspace_bytes_pairdist_rbf_rows(int64_t N, int64_t D, i
 // see include/dbmm.h
 extern "C" int dbmm_pairdist_rbf_row_group_sums(const float* x, const int64_t* groups, const float* center, const double* gammas, int64_t L, double* sums,
                                                 int64_t N, int64_t D, int64_t G, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N <= 0 || D <= 0 || N > (1 << 23) || G < 1 || G > ROWS_MAX_G || L < 1 || L > RBF_MAX_L) return DBMM_E_SHAPE;
-    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
-    if (!x || !groups || !center || !gammas || !sums || !workspace) return DBMM_E_ARG;
-    for (int l = 0; l < L; ++l)
-        if (!(gammas[l] > 0.0) || !(gammas[l] <= 1.79769313486231570e308)) return DBMM_E_ARG;      // finite and positive
-    if (!dbmm_aligned16(x) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
-    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rbf_rows(N, D, G, L)) return DBMM_E_WORKSPACE;
-    return row_sums<RbfMap>(x, groups, center, gammas, L, sums, N, D, G, workspace, stream);
+    const int rc = check_operands(TAKES_GROUPS | TAKES_GAMMAS, ROWS_MAX_G, x, groups, nullptr, center, gammas, L, sums, N, D, G, workspace, workspace_bytes,
+                                  rows_workspace_bytes(N, D, G, L));
+    return rc != DBMM_OK ? rc : row_sums<RbfMap>(x, groups, center, gammas, L, sums, N, D, G, workspace, stream);
 }
 
 // see include/dbmm_kernel_ops.h
@@ -781,11 +756,7 @@ extern "C" size_t dbmm_workspace_bytes_pairdist_rbf_matvec(int64_t N, int64_t D,
 // see include/dbmm_kernel_ops.h
 extern "C" int dbmm_pairdist_rbf_matvec(const float* x, const float* v, const float* center, double gamma, double* out, int64_t N, int64_t D, int64_t C,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (N <= 0 || D <= 0 || N > (1 << 23) || C < 1 || C > ROWS_MAX_G) return DBMM_E_SHAPE;
-    if ((D % 64) || D > 4096) return DBMM_E_UNSUPPORTED;
-    if (!x || !v || !center || !out || !workspace) return DBMM_E_ARG;
-    if (!(gamma > 0.0) || !(gamma <= 1.79769313486231570e308)) return DBMM_E_ARG;                 // finite and positive
-    if (!dbmm_aligned16(x) || !dbmm_aligned16(v) || !dbmm_aligned16(center) || !dbmm_aligned16(workspace)) return DBMM_E_ALIGN;
-    if (workspace_bytes < dbmm_workspace_bytes_pairdist_rbf_matvec(N, D, C)) return DBMM_E_WORKSPACE;
-    return row_sums<RbfMatvecMap>(x, nullptr, center, &gamma, 1, out, N, D, C, workspace, stream, v);
+    const int rc = check_operands(TAKES_GAMMAS | TAKES_V, ROWS_MAX_G, x, nullptr, v, center, &gamma, 1, out, N, D, C, workspace, workspace_bytes,
+                                  rows_workspace_bytes(N, D, C, 1));
+    return rc != DBMM_OK ? rc : row_sums<RbfMatvecMap>(x, nullptr, center, &gamma, 1, out, N, D, C, workspace, stream, v);
 }

@@ -1697,27 +1697,6 @@ def _served(rc, what, request):
     check(rc, what)
 
 
-def pairdist_group_sums(x, groups, n_groups, center):
-    """S float64 [G, G], symmetric: S[a, b] = sum over unordered pairs i < j with {groups[i], groups[j]} = {a, b} of
-    ||x[i] - x[j]||_2, on the fused Gram-and-distance kernel (dbmm_pairdist_group_sums): no N x N matrix, float64 sums in a fixed
-    order.  x fp32 [N, D] (D % 64 == 0, D <= 4096), groups int64 [N] in [0, n_groups) (n_groups <= 8), center fp32 [D]: a vector
-    near the rows' mean (the split's mean vector), subtracted before the products are formed.  The whole split's sum is
-    S.triu().sum(); group a's own is S[a, a]."""
-    N, D = _rows_operand("pairdist_group_sums", x)
-    _ids_operand("pairdist_group_sums", "groups", groups, x)
-    _f32_operand("pairdist_group_sums", "center", center, x, D)
-    if not 1 <= n_groups <= 8:
-        raise _lib.DbmmError(f"pairdist_group_sums: n_groups = {n_groups} outside 1..8")
-    L = _lib.lib()
-    nbytes = L.dbmm_workspace_bytes_pairdist(N, D)
-    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # the planes: sized by the call, not cached
-    out = _empty((n_groups, n_groups), device=x.device, dtype=torch.float64)
-    rc = L.dbmm_pairdist_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), out.data_ptr(), N, D, n_groups, ws.data_ptr(),
-                                    ws.numel() * 4, stream())
-    _served(rc, "pairdist_group_sums", f"N = {N}, D = {D}")
-    return out
-
-
 PAIRDIST_RBF_MAX_L = 4               # bandwidths of one RBF bucket pass (csrc/pairdist.hip: RBF_MAX_L)
 
 
@@ -1735,6 +1714,49 @@ def _rbf_gammas(what, gammas):
     return (ctypes.c_double * len(vals))(*vals)
 
 
+_NO_GAMMAS = object()                # a distance entry: it takes no bandwidths (None is a refused value of `gammas`)
+
+
+def _pairdist(what, sizer, x, center, cap, groups=None, n_groups=None, v=None, per_row=False, gammas=_NO_GAMMAS):
+    """The one frame of the five pairwise-kernel wrappers below (csrc/pairdist.hip); each says what is its own.  In this order: the
+    gammas, host values, refused before any device is touched; x; the ids `groups` (n_groups labels, at most `cap`) or the weights
+    `v` [N, C <= cap]; center; the workspace, sized by the library's `sizer`, then the result -- the call's two allocations --;
+    the C entry dbmm_<what>; _served.  The result is float64: [G, G] of a bucket pass, [N, G] with per_row, under a leading [L]
+    where the entry takes a ladder of bandwidths (with `v` it takes one, by value)."""
+    gam = None if gammas is _NO_GAMMAS else _rbf_gammas(what, gammas)
+    N, D = _rows_operand(what, x)
+    if v is None:
+        _ids_operand(what, "groups", groups, x)
+        _f32_operand(what, "center", center, x, D)
+        if not 1 <= n_groups <= cap:
+            raise _lib.DbmmError(f"{what}: n_groups = {n_groups} outside 1..{cap}")
+        second, n = groups, n_groups
+        lead, mid = ((), ()) if gam is None else ((len(gam),), (ctypes.addressof(gam), len(gam)))
+    else:
+        _f32_operand(what, "v", v, x)
+        if v.dim() != 2 or v.shape[0] != N or not 1 <= v.shape[1] <= cap:
+            raise _lib.DbmmError(f"{what}: v must be [{N}, C] with C in 1..{cap}, got {tuple(v.shape)}")
+        _f32_operand(what, "center", center, x, D)
+        second, n, lead, mid = v, v.shape[1], (), (gam[0],)
+    L = _lib.lib()
+    nbytes = getattr(L, sizer)(N, D, *((n,) if per_row else ()), *lead)
+    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # planes and partials: sized by the call, not cached
+    out = _empty(lead + ((N, n) if per_row else (n, n)), device=x.device, dtype=torch.float64)
+    rc = getattr(L, "dbmm_" + what)(x.data_ptr(), second.data_ptr(), center.data_ptr(), *mid, out.data_ptr(), N, D, n, ws.data_ptr(),
+                                    ws.numel() * 4, stream())
+    _served(rc, what, f"N = {N}, D = {D}")
+    return out
+
+
+def pairdist_group_sums(x, groups, n_groups, center):
+    """S float64 [G, G], symmetric: S[a, b] = sum over unordered pairs i < j with {groups[i], groups[j]} = {a, b} of
+    ||x[i] - x[j]||_2, on the fused Gram-and-distance kernel (dbmm_pairdist_group_sums): no N x N matrix, float64 sums in a fixed
+    order.  x fp32 [N, D] (D % 64 == 0, D <= 4096), groups int64 [N] in [0, n_groups) (n_groups <= 8), center fp32 [D]: a vector
+    near the rows' mean (the split's mean vector), subtracted before the products are formed.  The whole split's sum is
+    S.triu().sum(); group a's own is S[a, a]."""
+    return _pairdist("pairdist_group_sums", "dbmm_workspace_bytes_pairdist", x, center, groups=groups, n_groups=n_groups, cap=8)
+
+
 def pairdist_rbf_group_sums(x, groups, n_groups, center, gammas):
     """K float64 [L, G, G], symmetric in its last two axes: K[l, a, b] = sum over unordered pairs i < j with {groups[i], groups[j]} =
     {a, b} of exp(-gammas[l] ||x[i] - x[j]||^2), on the fused Gram kernel (dbmm_pairdist_rbf_group_sums): pairdist_group_sums'
@@ -1742,20 +1764,7 @@ def pairdist_rbf_group_sums(x, groups, n_groups, center, gammas):
     order -- the same bits on every call, and a bandwidth's sums do not depend on the others in the call.  Operands as
     pairdist_group_sums; gammas: 1..4 finite numbers > 0 (host values).  The diagonal is left out by index: a V-statistic adds the
     group's row count to K[l, a, a]."""
-    gam = _rbf_gammas("pairdist_rbf_group_sums", gammas)                            # host values: refused before any device is touched
-    N, D = _rows_operand("pairdist_rbf_group_sums", x)
-    _ids_operand("pairdist_rbf_group_sums", "groups", groups, x)
-    _f32_operand("pairdist_rbf_group_sums", "center", center, x, D)
-    if not 1 <= n_groups <= 8:
-        raise _lib.DbmmError(f"pairdist_rbf_group_sums: n_groups = {n_groups} outside 1..8")
-    L = _lib.lib()
-    nbytes = L.dbmm_workspace_bytes_pairdist_rbf(N, D, len(gam))
-    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # the planes: sized by the call, not cached
-    out = _empty((len(gam), n_groups, n_groups), device=x.device, dtype=torch.float64)
-    rc = L.dbmm_pairdist_rbf_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), ctypes.addressof(gam), len(gam), out.data_ptr(), N, D,
-                                        n_groups, ws.data_ptr(), ws.numel() * 4, stream())
-    _served(rc, "pairdist_rbf_group_sums", f"N = {N}, D = {D}")
-    return out
+    return _pairdist("pairdist_rbf_group_sums", "dbmm_workspace_bytes_pairdist_rbf", x, center, groups=groups, n_groups=n_groups, cap=8, gammas=gammas)
 
 
 PAIRDIST_ROWS_MAX_G = 16            # labels of the per-row distance sums (csrc/pairdist.hip); the value of KMEANS_MAX_K
@@ -1768,19 +1777,8 @@ def pairdist_row_group_sums(x, groups, n_groups, center):
     still gets its own), center fp32 [D]: a vector near the rows' mean (the split's mean vector), subtracted before the products
     are formed.  The diagonal is left out by index: R[i, groups[i]] of a group's only row and the column of an empty group are
     exactly 0.  Rows sorted by group take the kernel's fast path; any order gives the same sums to 1e-6."""
-    N, D = _rows_operand("pairdist_row_group_sums", x)
-    _ids_operand("pairdist_row_group_sums", "groups", groups, x)
-    _f32_operand("pairdist_row_group_sums", "center", center, x, D)
-    if not 1 <= n_groups <= PAIRDIST_ROWS_MAX_G:
-        raise _lib.DbmmError(f"pairdist_row_group_sums: n_groups = {n_groups} outside 1..{PAIRDIST_ROWS_MAX_G}")
-    L = _lib.lib()
-    nbytes = L.dbmm_workspace_bytes_pairdist_rows(N, D, n_groups)
-    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # planes and partials: sized by the call, not cached
-    out = _empty((N, n_groups), device=x.device, dtype=torch.float64)
-    rc = L.dbmm_pairdist_row_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), out.data_ptr(), N, D, n_groups, ws.data_ptr(),
-                                        ws.numel() * 4, stream())
-    _served(rc, "pairdist_row_group_sums", f"N = {N}, D = {D}")
-    return out
+    return _pairdist("pairdist_row_group_sums", "dbmm_workspace_bytes_pairdist_rows", x, center, groups=groups, n_groups=n_groups, cap=PAIRDIST_ROWS_MAX_G,
+                     per_row=True)
 
 
 def pairdist_rbf_row_group_sums(x, groups, n_groups, center, gammas):
@@ -1790,20 +1788,8 @@ def pairdist_rbf_row_group_sums(x, groups, n_groups, center, gammas):
     not depend on the others in the call.  Operands as pairdist_row_group_sums (n_groups <= 16; a row with a label outside
     [0, n_groups) is in nobody's sums and still gets its own: a query row); gammas: 1..4 finite numbers > 0 (host values).  The
     diagonal is left out by index: R[l, i, groups[i]] of a label's only row and the column of an empty label are exactly 0."""
-    gam = _rbf_gammas("pairdist_rbf_row_group_sums", gammas)                        # host values: refused before any device is touched
-    N, D = _rows_operand("pairdist_rbf_row_group_sums", x)
-    _ids_operand("pairdist_rbf_row_group_sums", "groups", groups, x)
-    _f32_operand("pairdist_rbf_row_group_sums", "center", center, x, D)
-    if not 1 <= n_groups <= PAIRDIST_ROWS_MAX_G:
-        raise _lib.DbmmError(f"pairdist_rbf_row_group_sums: n_groups = {n_groups} outside 1..{PAIRDIST_ROWS_MAX_G}")
-    L = _lib.lib()
-    nbytes = L.dbmm_workspace_bytes_pairdist_rbf_rows(N, D, n_groups, len(gam))
-    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # planes and partials: sized by the call, not cached
-    out = _empty((len(gam), N, n_groups), device=x.device, dtype=torch.float64)
-    rc = L.dbmm_pairdist_rbf_row_group_sums(x.data_ptr(), groups.data_ptr(), center.data_ptr(), ctypes.addressof(gam), len(gam), out.data_ptr(),
-                                            N, D, n_groups, ws.data_ptr(), ws.numel() * 4, stream())
-    _served(rc, "pairdist_rbf_row_group_sums", f"N = {N}, D = {D}")
-    return out
+    return _pairdist("pairdist_rbf_row_group_sums", "dbmm_workspace_bytes_pairdist_rbf_rows", x, center, groups=groups, n_groups=n_groups,
+                     cap=PAIRDIST_ROWS_MAX_G, per_row=True, gammas=gammas)
 
 
 PAIRDIST_MATVEC_MAX_C = 16          # weight columns of one kernel-matrix product (csrc/pairdist.hip: ROWS_MAX_G)
@@ -1818,21 +1804,7 @@ def pairdist_rbf_matvec(x, v, center, gamma):
     one finite number > 0 (a host value).  A 256-row block of v that is zero in a column costs that column nothing: one-hot
     columns and zero weights on appended query rows are cheap.  An entry is good to 1e-4 sum_j k_ij |v_jc|; the kernel matrix with
     its unit diagonal is R + v."""
-    gam = _rbf_gammas("pairdist_rbf_matvec", [gamma])                               # a host value: refused before any device is touched
-    N, D = _rows_operand("pairdist_rbf_matvec", x)
-    _f32_operand("pairdist_rbf_matvec", "v", v, x)
-    if v.dim() != 2 or v.shape[0] != N or not 1 <= v.shape[1] <= PAIRDIST_MATVEC_MAX_C:
-        raise _lib.DbmmError(f"pairdist_rbf_matvec: v must be [{N}, C] with C in 1..{PAIRDIST_MATVEC_MAX_C}, got {tuple(v.shape)}")
-    _f32_operand("pairdist_rbf_matvec", "center", center, x, D)
-    C = v.shape[1]
-    L = _lib.lib()
-    nbytes = L.dbmm_workspace_bytes_pairdist_rbf_matvec(N, D, C)
-    ws = _empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)           # planes and partials: sized by the call, not cached
-    out = _empty((N, C), device=x.device, dtype=torch.float64)
-    rc = L.dbmm_pairdist_rbf_matvec(x.data_ptr(), v.data_ptr(), center.data_ptr(), gam[0], out.data_ptr(), N, D, C, ws.data_ptr(),
-                                    ws.numel() * 4, stream())
-    _served(rc, "pairdist_rbf_matvec", f"N = {N}, D = {D}")
-    return out
+    return _pairdist("pairdist_rbf_matvec", "dbmm_workspace_bytes_pairdist_rbf_matvec", x, center, v=v, cap=PAIRDIST_MATVEC_MAX_C, per_row=True, gammas=[gamma])
 
 
 def covariance(x, center):

@@ -85,3 +85,20 @@ def test_label_sums_helper_defined_once(name):
 ])
 def test_label_sums_statement_stated_once(statement):
     assert _where(re.escape(statement)) == [("label_sums.h", 1)]
+
+
+# What the pairwise-kernel family shares in the library (csrc/pairdist.hip, csrc/pairdist_ring.inc): the ring's
+# source map, the accumulators' d^2 step, the operand check and the prepare step of every pass.  A further entry or tile kernel that
+# restates one of them fails here.
+@pytest.mark.parametrize("statement,where", [
+    ("const int kt = isA ? (t < p.T ? t : t - p.T)", "pairdist_ring.inc"),       # ring_src: the three products' K tiles inside a row of P
+    ("fmaf(-2.f, acc[i][0][r], rn + cn0)", "pairdist.hip"),                      # PAIRDIST_ACC_TO_D2
+    ("hipLaunchKernelGGL(pairdist_absmax_kernel", "pairdist.hip"),               # prepare
+])
+def test_pairdist_statement_stated_once(statement, where):
+    assert _where(re.escape(statement)) == [(where, 1)]
+
+
+def test_pairdist_row_limit_stated_once():
+    # check_operands; the other analysis kernels state their own limit (common.h: dbmm_rows_shape)
+    assert SOURCES["pairdist.hip"].count("N > (1 << 23)") == 1

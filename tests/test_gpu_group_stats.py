@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from pairdist_cases import rows
 from test_group_stats_host import SPLITS, regenerate
 
 pytestmark = pytest.mark.gpu
@@ -23,11 +24,6 @@ RTOL = 1e-4
 @pytest.fixture(scope="module")
 def fx(golden):
     return golden("group_stats.npz")
-
-
-def rows(n, d, seed, spread=0.5):
-    g = torch.Generator().manual_seed(seed)
-    return (spread * torch.randn(n, d, generator=g) + 0.1 * torch.randn(1, d, generator=g)).cuda()
 
 
 def bucket_sums_f64(x, groups, G, chunk=1024):

@@ -10,7 +10,7 @@ precondition, gamma_max * max d^2 <= 80, which also keeps every kernel value a n
 a wave's 64 columns adds 6 * 2^-24 = 4e-7.  Together < 6e-5 on every term; the terms are non-negative, so a sum is no worse than its
 worst term, however few terms it has.  An entry with no term (an empty label; a label's only row, for its own label; nothing at all
 for N = 1) must be exactly 0.  Both preconditions are asserted on every test's own inputs in float64, the generators and ladders
-are test_gpu_mmd.py's, and every test prints its figures before it asserts.
+are pairdist_cases.py's, and every test prints its figures before it asserts.
 
 A density is an entry over a count: 1e-4 relative.  A witness value is a difference of two densities: 1e-4 * (density_a +
 density_b) absolute.  An MMD^2 is a difference of three kernel means: 1e-4 * (k_aa + k_bb + 2 k_ab) absolute."""
@@ -18,49 +18,11 @@ import numpy as np
 import pytest
 import torch
 
+from pairdist_cases import DEV, GuardedAlloc, ISO_SCALES, SPREAD, check_preconditions, clustered_rows, ladder, onehot, rows, sq_dists
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda" if torch.cuda.is_available() else "cpu"   # the float64 side of every test runs anywhere
 RTOL = 1e-4
-SPREAD = 0.5
-ISO_SCALES = (0.25, 1.0, 4.0, 16.0)        # gamma = scale / (2 SPREAD^2 D): the mean squared distance of the isotropic rows
-CLU_SCALES = (0.5, 2.0, 8.0, 24.0)         # gamma = scale / (15.5 SPREAD^2 D): that of the clustered rows (2 within + 18 * 3/4 between)
-
-
-def rows(n, d, seed, spread=SPREAD):
-    g = torch.Generator().manual_seed(seed)
-    return (spread * torch.randn(n, d, generator=g) + 0.1 * torch.randn(1, d, generator=g)).to(DEV)
-
-
-def clustered_rows(n, d, seed, spread=SPREAD):
-    """four centres three spreads apart per coordinate plus noise: (rows, cluster of every row)"""
-    g = torch.Generator().manual_seed(seed)
-    centres = 3.0 * spread * torch.randn(4, d, generator=g)
-    which = torch.randint(0, 4, (n,), generator=g)
-    return (centres[which] + spread * torch.randn(n, d, generator=g) + 0.1 * torch.randn(1, d, generator=g)).to(DEV), which
-
-
-def ladder(kind, d):
-    return [s / ((2.0 if kind == "iso" else 15.5) * SPREAD ** 2 * d) for s in (ISO_SCALES if kind == "iso" else CLU_SCALES)]
-
-
-def sq_dists(x, y=None, chunk=1024):
-    """float64 squared distances from direct differences, row chunks of x against y (x itself by default)"""
-    xd = x.double()
-    yd = xd if y is None else y.double()
-    return torch.cat([torch.cdist(xd[i:i + chunk], yd, compute_mode="donot_use_mm_for_euclid_dist") for i in range(0, xd.shape[0], chunk)]) ** 2
-
-
-def check_preconditions(x, d2, gammas, what):
-    xc = x.double() - x.double().mean(0)
-    worst = 2.0 * (xc ** 2).sum(1).max().item()                          # max_ij (|a|^2 + |b|^2), centred
-    gmax = max(gammas)
-    print(f"{what}: gamma_max * max(|a|^2 + |b|^2) = {gmax * worst:.2f} (<= 64), gamma_max * max d^2 = {gmax * d2.max().item():.2f} (<= 80)")
-    assert gmax * worst <= 64.0 and gmax * d2.max().item() <= 80.0, f"{what}: the test's own inputs break the bound's preconditions"
-
-
-def onehot(g, G):
-    return (g.unsqueeze(1) == torch.arange(G, device=g.device).unsqueeze(0)).double()                  # [N, G]; labels outside: no column
 
 
 def row_sums_f64(d2, g, G, gammas):
@@ -252,29 +214,6 @@ def test_duplicated_rows():
     rel = ((R.sum(1) - ref.sum(1)).abs() / ref.sum(1))
     print(f"duplicates: whole-sum rel err per (bandwidth, label)\n{rel}")
     assert (rel <= RTOL).all()
-
-
-class GuardedAlloc:
-    """stand-in for ops._empty: every output and workspace sits between two sentinel-filled zones"""
-    S = -7.0
-
-    def __init__(self):
-        self.bufs = []
-
-    def __call__(self, shape, device=None, dtype=torch.float32, **kw):
-        shape = (shape,) if isinstance(shape, int) else tuple(shape)
-        n = int(np.prod(shape))
-        pad = 1 << 16                                                       # elements: a multiple of 16 bytes for every dtype used
-        raw = torch.full((n + 2 * pad,), self.S, device=device, dtype=dtype)
-        self.bufs.append((raw, pad, n))
-        return raw[pad:pad + n].view(shape)
-
-    def check(self):
-        assert self.bufs
-        for raw, pad, n in self.bufs:
-            lo, hi = raw[:pad], raw[pad + n:]
-            assert bool((lo == self.S).all()) and bool((hi == self.S).all()), \
-                f"guard zone of a {n}-element {raw.dtype} buffer was written: {(lo != self.S).sum().item()} before, {(hi != self.S).sum().item()} after"
 
 
 def test_nothing_is_written_outside_the_sums_and_the_workspace(monkeypatch):

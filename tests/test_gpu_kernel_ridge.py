@@ -8,7 +8,7 @@ gamma * max_ij (|a|^2 + |b|^2) <= 64 and gamma * max d^2 <= 80), plus the weight
 multiply-add in fp32: 2 * 2^-24), plus the fp32 tree over a wave's 64 columns (6 * 2^-24) -- relative to the sum of the ABSOLUTE terms,
 because the weights are signed and the terms may cancel.  An entry whose sum of absolute terms is 0 must be exactly 0.  Both
 preconditions are asserted on every test's own inputs in float64; the generators, the ladders and check_preconditions are
-test_gpu_kernel_probe.py's, and every test prints its figures before it asserts.
+pairdist_cases.py's, and every test prints its figures before it asserts.
 
 The fit is checked backward (the dense float64 residual of the returned coefficients, valid at any conditioning) and, at lam = 1
 only, forward: ||alpha^ - alpha|| <= kappa (1e-4 + tol) ||alpha|| with kappa = cond(K + lam I) from eigvalsh -- the operator's error is
@@ -20,46 +20,12 @@ import numpy as np
 import pytest
 import torch
 
+from pairdist_cases import DEV, GuardedAlloc, check_preconditions, clustered_rows, ladder, rows, sq_dists
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda" if torch.cuda.is_available() else "cpu"   # the float64 side of every test runs anywhere
 RTOL = 1e-4
 TOL = 1e-5                                 # kernel_ridge_fit's default stopping residual
-SPREAD = 0.5
-ISO_SCALES = (0.25, 1.0, 4.0, 16.0)        # gamma = scale / (2 SPREAD^2 D): the mean squared distance of the isotropic rows
-CLU_SCALES = (0.5, 2.0, 8.0, 24.0)         # gamma = scale / (15.5 SPREAD^2 D): that of the clustered rows (2 within + 18 * 3/4 between)
-
-
-def rows(n, d, seed, spread=SPREAD):
-    g = torch.Generator().manual_seed(seed)
-    return (spread * torch.randn(n, d, generator=g) + 0.1 * torch.randn(1, d, generator=g)).to(DEV)
-
-
-def clustered_rows(n, d, seed, spread=SPREAD):
-    """four centres three spreads apart per coordinate plus noise: (rows, cluster of every row)"""
-    g = torch.Generator().manual_seed(seed)
-    centres = 3.0 * spread * torch.randn(4, d, generator=g)
-    which = torch.randint(0, 4, (n,), generator=g)
-    return (centres[which] + spread * torch.randn(n, d, generator=g) + 0.1 * torch.randn(1, d, generator=g)).to(DEV), which
-
-
-def ladder(kind, d):
-    return [s / ((2.0 if kind == "iso" else 15.5) * SPREAD ** 2 * d) for s in (ISO_SCALES if kind == "iso" else CLU_SCALES)]
-
-
-def sq_dists(x, y=None, chunk=1024):
-    """float64 squared distances from direct differences, row chunks of x against y (x itself by default)"""
-    xd = x.double()
-    yd = xd if y is None else y.double()
-    return torch.cat([torch.cdist(xd[i:i + chunk], yd, compute_mode="donot_use_mm_for_euclid_dist") for i in range(0, xd.shape[0], chunk)]) ** 2
-
-
-def check_preconditions(x, d2, gammas, what):
-    xc = x.double() - x.double().mean(0)
-    worst = 2.0 * (xc ** 2).sum(1).max().item()                          # max_ij (|a|^2 + |b|^2), centred
-    gmax = max(gammas)
-    print(f"{what}: gamma_max * max(|a|^2 + |b|^2) = {gmax * worst:.2f} (<= 64), gamma_max * max d^2 = {gmax * d2.max().item():.2f} (<= 80)")
-    assert gmax * worst <= 64.0 and gmax * d2.max().item() <= 80.0, f"{what}: the test's own inputs break the bound's preconditions"
 
 
 def kernel_f64(d2, gam):
@@ -199,29 +165,6 @@ def test_the_product_is_symmetric_within_its_bound():
     ratio = ((a - b).abs() / unit).max().item()
     print(f"symmetry: worst |u^T K v - v^T K u| / |u|^T K |v| = {ratio:.3e} (<= 2e-4) over 16 column pairs")
     assert ratio <= 2e-4
-
-
-class GuardedAlloc:
-    """stand-in for ops._empty: every output and workspace sits between two sentinel-filled zones"""
-    S = -7.0
-
-    def __init__(self):
-        self.bufs = []
-
-    def __call__(self, shape, device=None, dtype=torch.float32, **kw):
-        shape = (shape,) if isinstance(shape, int) else tuple(shape)
-        n = int(np.prod(shape))
-        pad = 1 << 16                                                       # elements: a multiple of 16 bytes for every dtype used
-        raw = torch.full((n + 2 * pad,), self.S, device=device, dtype=dtype)
-        self.bufs.append((raw, pad, n))
-        return raw[pad:pad + n].view(shape)
-
-    def check(self):
-        assert self.bufs
-        for raw, pad, n in self.bufs:
-            lo, hi = raw[:pad], raw[pad + n:]
-            assert bool((lo == self.S).all()) and bool((hi == self.S).all()), \
-                f"guard zone of a {n}-element {raw.dtype} buffer was written: {(lo != self.S).sum().item()} before, {(hi != self.S).sum().item()} after"
 
 
 def test_nothing_is_written_outside_the_product_and_the_workspace(monkeypatch):

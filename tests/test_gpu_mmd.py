@@ -17,44 +17,11 @@ import numpy as np
 import pytest
 import torch
 
+from pairdist_cases import ISO_SCALES, SPREAD, check_preconditions, clustered_rows, ladder, rows, sq_dists
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-4
-SPREAD = 0.5
-ISO_SCALES = (0.25, 1.0, 4.0, 16.0)        # gamma = scale / (2 SPREAD^2 D): the mean squared distance of the isotropic rows
-CLU_SCALES = (0.5, 2.0, 8.0, 24.0)         # gamma = scale / (15.5 SPREAD^2 D): that of the clustered rows (2 within + 18 * 3/4 between)
-
-
-def rows(n, d, seed, spread=SPREAD):
-    """the isotropic rows of test_gpu_group_stats: d^2 is nearly constant in high D"""
-    g = torch.Generator().manual_seed(seed)
-    return (spread * torch.randn(n, d, generator=g) + 0.1 * torch.randn(1, d, generator=g)).cuda()
-
-
-def clustered_rows(n, d, seed, spread=SPREAD):
-    """four centres three spreads apart per coordinate plus noise: d^2 is 2 spread^2 D within a cluster and about 20 spread^2 D
-    between two, so kernel values span orders of magnitude and a wrong exponent scale cannot hide.  (rows, cluster of every row)"""
-    g = torch.Generator().manual_seed(seed)
-    centres = 3.0 * spread * torch.randn(4, d, generator=g)
-    which = torch.randint(0, 4, (n,), generator=g)
-    return (centres[which] + spread * torch.randn(n, d, generator=g) + 0.1 * torch.randn(1, d, generator=g)).cuda(), which
-
-
-def ladder(kind, d):
-    return [s / ((2.0 if kind == "iso" else 15.5) * SPREAD ** 2 * d) for s in (ISO_SCALES if kind == "iso" else CLU_SCALES)]
-
-
-def sq_dists(x):
-    xd = x.double()
-    return torch.cdist(xd, xd, compute_mode="donot_use_mm_for_euclid_dist") ** 2
-
-
-def check_preconditions(x, d2, gammas, what):
-    xc = x.double() - x.double().mean(0)
-    worst = 2.0 * (xc ** 2).sum(1).max().item()                          # max_ij (|a|^2 + |b|^2), centred
-    gmax = max(gammas)
-    print(f"{what}: gamma_max * max(|a|^2 + |b|^2) = {gmax * worst:.2f} (<= 64), gamma_max * max d^2 = {gmax * d2.max().item():.2f} (<= 80)")
-    assert gmax * worst <= 64.0 and gmax * d2.max().item() <= 80.0, f"{what}: the test's own inputs break the bound's preconditions"
 
 
 def bucket_sums_f64(d2, groups, G, gammas):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from pairdist_cases import GuardedAlloc, onehot, rows
 from test_silhouette_host import planted_rows, silhouette_f64
 
 pytestmark = pytest.mark.gpu
@@ -18,20 +19,11 @@ pytestmark = pytest.mark.gpu
 RTOL = 1e-4
 
 
-def rows(n, d, seed, spread=0.5):
-    g = torch.Generator().manual_seed(seed)
-    return (spread * torch.randn(n, d, generator=g) + 0.1 * torch.randn(1, d, generator=g)).cuda()
-
-
 def distances_f64(x, chunk=1024):
     """the N x N float64 distance matrix from direct differences (small N only), its diagonal exactly 0.  cdist's direct kernel
     launches one block per pair: chunk * N stays under 2^24 blocks."""
     xd = x.double()
     return torch.cat([torch.cdist(xd[i:i + chunk], xd, compute_mode="donot_use_mm_for_euclid_dist") for i in range(0, xd.shape[0], chunk)])
-
-
-def onehot(g, G):
-    return (g.unsqueeze(1) == torch.arange(G, device=g.device).unsqueeze(0)).double()                  # [N, G]; labels outside: no column
 
 
 def check_sums(R, ref, g, G, what):
@@ -122,29 +114,6 @@ def test_deterministic_and_order_independent():
     rel = ((R3 - R1).abs() / R1).max().item()
     print(f"sorted vs unsorted: max entry rel diff {rel:.3e}")
     assert rel <= 1e-6
-
-
-class GuardedAlloc:
-    """stand-in for ops._empty: every output and workspace sits between two sentinel-filled zones"""
-    S = -7.0
-
-    def __init__(self):
-        self.bufs = []
-
-    def __call__(self, shape, device=None, dtype=torch.float32, **kw):
-        shape = (shape,) if isinstance(shape, int) else tuple(shape)
-        n = int(np.prod(shape))
-        pad = 1 << 16                                                       # elements: a multiple of 16 bytes for every dtype used
-        raw = torch.full((n + 2 * pad,), self.S, device=device, dtype=dtype)
-        self.bufs.append((raw, pad, n))
-        return raw[pad:pad + n].view(shape)
-
-    def check(self):
-        assert self.bufs
-        for raw, pad, n in self.bufs:
-            lo, hi = raw[:pad], raw[pad + n:]
-            assert bool((lo == self.S).all()) and bool((hi == self.S).all()), \
-                f"guard zone of a {n}-element {raw.dtype} buffer was written: {(lo != self.S).sum().item()} before, {(hi != self.S).sum().item()} after"
 
 
 def test_nothing_is_written_outside_the_sums_and_the_workspace(monkeypatch):

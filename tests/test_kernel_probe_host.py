@@ -213,3 +213,25 @@ def test_entry_refuses_its_operands_without_a_device():
     assert call(1000, 64, 4, 2, g=(ctypes.c_double * 2)(float("nan"), 1.0)) == -4
     assert call(1000, 64, 4, 1, x=p + 4) == -2
     assert call(1000, 64, 4, 4, ws=L.dbmm_workspace_bytes_pairdist_rbf_rows(1000, 64, 4, 4) - 1) != 0
+
+
+# What the pairwise-kernel family shares on the Python side: one driver in ops.py, one labelled-rows front end, one
+# sorted-by-label pass and one spelling of each refusal in analysis.py.  A wrapper or report that carries its own copy again fails here
+# (source scan with the comments stripped, no compute), as tests/test_csrc_shared_helpers.py does for the library.
+def _python_source(name, section=None):
+    import os
+    import re
+    txt = open(os.path.join(os.path.dirname(os.path.abspath(ops.__file__)), name)).read()
+    if section is not None:
+        txt = txt[txt.index(section[0]):txt.index(section[1])]
+    return re.sub(r"#[^\n]*", "", txt)
+
+
+@pytest.mark.parametrize("name,section,statement", [
+    ("ops.py", ("PAIRDIST_RBF_MAX_L = 4", "def covariance("), "ws.numel() * 4"),                        # the C call of _pairdist
+    ("analysis.py", None, 'np.argsort(dense, kind="stable")'),                                         # _sorted_pass
+    ("analysis.py", None, "is None else np.asarray(gammas, dtype=np.float64).ravel()"),                # _resolved_gammas
+    ("analysis.py", None, "there is no CPU path"),                                                     # _need_device
+])
+def test_pairwise_family_statement_stated_once(name, section, statement):
+    assert _python_source(name, section).count(statement) == 1
